@@ -27,6 +27,11 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline`
 144*H*W per patch / time per step of the timed region) and `cpu_baseline` (the eager-PyTorch
 restatement of the reference's algorithm, oracle/eager_torch.py, timed on this box's
 host cores on a bounded sample).
+
+A PLAIN run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline needs: set-up, settle + W warm-up
+steps, ONE timed region of exactly N steps, the outputs of its last step (--dump-outputs), the line.  Everything else --
+the median of several short regions, the untimed follow-up legs, the secondary kernels, the CPU baseline -- runs with
+--full only; the line then carries those figures as before (None / "skipped" in a plain run).
 """
 import argparse
 import json
@@ -60,6 +65,17 @@ def parse_args():
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--random-scenes", type=int, default=3)
     ap.add_argument("--specular-scenes", type=int, default=6)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: short forms (--steps < 256) time --regions regions "
+                         "and report the median one, then the untimed follow-up legs, the secondary kernels and the CPU "
+                         "baseline run (the --no-* / --timed-only options below switch parts of it off).  Off by default: "
+                         "a plain run times one region of exactly --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path handed its caller in its last step -- the loss "
+                         "and the gradient w.r.t. the input maps (rank 0's shard) -- as DIR/loss.npy and DIR/grad.npy "
+                         "(float32, 64 MB at most: a larger gradient as DIR/grad_sample.npy, a fixed seeded sample).  The timed "
+                         "steps start from a freshly seeded scene stream at the first batch, so the same arguments give "
+                         "the same inputs in every run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--selftest", action="store_true",
                     help="first contact with a multi-GPU node (tools/scale_first_contact.md): after the bring-up, every rank "
@@ -69,9 +85,9 @@ def parse_args():
                          "exit code 3 with a diagnosis on stderr when a check fails or anything hangs past --bringup-timeout")
     ap.add_argument("--selftest-expect-distinct", action="store_true", help=argparse.SUPPRESS)   # tests: make the self-test fail
     ap.add_argument("--timed-only", action="store_true",
-                    help="settle, warm-up and the timed region(s) only: none of the untimed follow-up legs (clock probe, the other "
-                         "issue pattern, the other backward modes, copy bandwidth).  For profiler passes: every launch of the "
-                         "fused loss in the process is then a launch of the timed loop")
+                    help="with --full: settle, warm-up and the timed region(s) only: none of the untimed follow-up legs (clock "
+                         "probe, the other issue pattern, the other backward modes, copy bandwidth).  For profiler passes: every "
+                         "launch of the fused loss in the process is then a launch of the timed loop (as in a plain run)")
     ap.add_argument("--no-copy-peak", action="store_true", help="skip the 1 GiB copy-bandwidth leg (2 GiB of device memory)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the K1/K2 stand-alone rates (N=1 only)")
     ap.add_argument("--settle-ms", type=float, default=300.0,
@@ -101,7 +117,7 @@ def parse_args():
                     help="multi-rank control flow only (rank launch, rendezvous, barrier, MAX over ranks, one JSON line "
                          "with ranks_seen) without touching a GPU: what the CPU test suite runs with --backend gloo")
     ap.add_argument("--regions", type=int, default=15,
-                    help="short forms (--steps < 256): timed regions of --steps steps each, run back to back; `value` is the "
+                    help="with --full, short forms (--steps < 256): timed regions of --steps steps each, run back to back; `value` is the "
                          "median region (at least 9, default 15: a 20-step region is 0.74 ms and a host hiccup of a shared box "
                          "costs a whole one -- with N ranks the job's region time is the MAX over ranks, so one rank's hiccup "
                          "spoils it; the median of 15 tolerates seven; the 2000-step default form times one region)")
@@ -211,6 +227,33 @@ def median_region_index(job_elapsed):
     return order[len(order) // 2]
 
 
+def follow_up_legs(args):
+    """the untimed follow-up legs run with --full only, and not under --timed-only"""
+    return args.full and not args.timed_only
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(path, loss, grad, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the loss and the input gradient of the last timed step as float32 .npy files in `path`, at most
+    `limit` bytes in all: a gradient that does not fit is written as a sample of limit / 2 bytes at fixed positions (seed 0,
+    ascending flat indices) -> {file name: array written}"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    g = grad.detach().float().cpu().numpy()
+    out = {"loss.npy": loss.detach().float().cpu().numpy()}
+    if g.nbytes <= limit - 2 ** 20:                 # 1 MiB left for the loss and the .npy headers
+        out["grad.npy"] = g
+    else:
+        flat = g.reshape(-1)
+        idx = np.sort(np.random.default_rng(0).choice(flat.size, limit // 2 // flat.itemsize, replace=False))
+        out["grad_sample.npy"] = flat[idx]
+    for name, a in out.items():
+        np.save(os.path.join(path, name), a)
+    return out
+
+
 MEASURED_KEYS = (
     "B", "H", "S", "world", "n_batches", "elapsed", "job_elapsed", "median_region", "n_regions", "kernel_ms",
     "kernel_ms_avg", "region_ms_per_launch", "main_ns", "clock_ghz", "clock_note", "cycle_leg_ms",
@@ -294,7 +337,7 @@ def assemble_line(args, m):
         "valu_issue_frac": valu_issue["frac"] if valu_issue else None,      # what bounds K3 (also in roofline, with its inputs)
         "value_single_stream": rate(one["ms_per_step"], world),
         "value_two_streams_overlapped": rate(two["ms_per_step"], world),
-        "follow_up_legs": "skipped (--timed-only)" if args.timed_only else "run",
+        "follow_up_legs": "run" if follow_up_legs(args) else "skipped (%s)" % ("--timed-only" if args.full else "plain run"),
         "copy_peak_GBps_measured": copy_gbps,
         "timed_regions": {"count": n_regions, "steps_each": args.steps, "median_index": median_region,
                           "ms_per_step": [1e3 * e / args.steps for e in job_elapsed],
@@ -553,9 +596,9 @@ class StepLoop:
         self.loss_fn = losses.RenderingLoss(renderers.LocalRenderer())
         self.loss_fn.random_configuration_count = args.random_scenes
         self.loss_fn.specular_configuration_count = args.specular_scenes
-        torch.manual_seed(distributed.rank_seed(313, R.rank))    # per-rank scene RNG
+        self.scene_seed = distributed.rank_seed(313, R.rank)     # per-rank scene RNG
         self.ns = args.streams if args.streams > 1 else 0        # 0: every step on the current stream
-        self.k = 0
+        self.restart()
         self.ext = _hostext.module()                             # native host path: event pairs are recorded inside the extension
         self._pair = None                                        # (begin, end) torch events of the NEXT launch, or None
         _native.set_launch_hook(None)
@@ -569,6 +612,12 @@ class StepLoop:
         # `value` is the training-loop figure: loss.backward() through PyTorch's autograd engine (what a network output gets;
         # one kernel launch per step: losses._FusedLossTensor)
         losses._UNIT_GRADIENT = True
+
+    def restart(self):
+        """the next step is step 0 again: first batch, scene RNG freshly seeded (the settle phase runs for a time, not a
+        number of steps, so without this the timed steps' batches and scenes would differ from run to run)"""
+        torch.manual_seed(self.scene_seed)
+        self.k = 0
 
     def _hook(self, phase):                                      # ctypes host path: called around the launch
         if self._pair is not None:
@@ -631,12 +680,13 @@ class StepLoop:
 
 def timed_regions(args, R, loop):
     """THE measurement.  One region = EXACTLY --steps steps between barrier + synchronize on both sides, its time the MAX over
-    ranks.  The default form (2000 steps, 75 ms) times one.  A SHORT form (the driver's --steps 20 is 0.76 ms of GPU time)
-    times `--regions` such regions back to back and the MEDIAN region is reported: a single 0.8 ms region swung by +-6 %
-    between runs on one box in round 4 (197-224 k), SURVEY 8d asks for a median over >= 100 iterations, and a host hiccup of a
-    shared box costs a whole region.  Every region is listed in the JSON line (`timed_regions`).
+    ranks.  A plain run times ONE region, so --steps is the number of timed steps.  With --full, the default form (2000 steps,
+    75 ms) times one as well, and a SHORT form (--steps 20 is 0.76 ms of GPU time) times `--regions` such regions back to back
+    and the MEDIAN region is reported: a single 0.8 ms region swung by +-6 % between runs on one box in round 4 (197-224 k),
+    SURVEY 8d asks for a median over >= 100 iterations, and a host hiccup of a shared box costs a whole region.  Every region
+    is listed in the JSON line (`timed_regions`).
     -> n_regions, per-region local wall seconds, per-region HIP-event ms per launch (None with several streams), last losses"""
-    n_regions = 1 if args.steps >= 256 else max(9, args.regions)
+    n_regions = 1 if args.steps >= 256 or not args.full else max(9, args.regions)
     dev = loop.dev
     local_elapsed, region_ms, lasts = [], [], []
     # one HIP event pair around each WHOLE region, on the stream the kernels are launched on (one stream only: with N streams
@@ -797,17 +847,20 @@ def main():
 
     loop = StepLoop(args, R)
     loop.settle_and_warm_up(args.settle_ms, args.warmup)
+    loop.restart()
     n_regions, local_elapsed, region_ms, lasts = timed_regions(args, R, loop)
     job_elapsed, median_region, elapsed, region_ms_per_launch, mean_loss, per_rank = reduce_over_ranks(
         args, R, loop, local_elapsed, region_ms, lasts)
+    if args.dump_outputs and R.rank == 0:       # before any follow-up leg runs another step
+        dump_outputs(args.dump_outputs, lasts[-1], loop.batches[(loop.k - 1) % len(loop.batches)][0].grad)
 
-    # ---- untimed follow-up legs (same process, same tensors).  --timed-only skips them: the profiler passes, whose per-kernel
-    # average should be the timed loop's launches and nothing else
+    # ---- untimed follow-up legs (same process, same tensors), with --full only.  --timed-only skips them: the profiler
+    # passes, whose per-kernel average should be the timed loop's launches and nothing else
     main_ns = loop.ns
-    kernel_ms, clock_ghz, clock_note, cycle_leg_ms = [], None, "not measured (--timed-only)", None
+    kernel_ms, clock_ghz, clock_note, cycle_leg_ms = [], None, "not measured (no follow-up legs)", None
     other_ms_per_step, other_ms, other_steps, leg_steps = None, [], 0, 0
     engine_ms_per_step = engine_plain_ms_per_step = copy = None
-    if not args.timed_only:
+    if follow_up_legs(args):
         kernel_ms, _ = loop.run_sampled(512, 16)                 # event pairs around every 16th launch of 512 untimed steps
         clock_ghz, clock_note, cycle_leg_ms = clock_leg(loop, min(local_elapsed) * 1e3 / args.steps)
         other_ms_per_step, other_ms, other_steps = other_issue_pattern_leg(loop, args.steps)
@@ -835,10 +888,10 @@ def main():
                                                           R.dist.get_world_size())) if R.dist is not None else None,
             "host_path": "native C++ extension (csrc/host_ext.cpp)" if loop.ext is not None else "python + ctypes"})
         t_main = time.perf_counter()
-        if R.world == 1 and not args.no_secondary:
+        if R.world == 1 and args.full and not args.no_secondary:
             out["secondary"] = secondary_kernels(loop.dev, args.size, copy_gbps)
         t_secondary = time.perf_counter()
-        if R.world == 1 and not args.no_cpu_baseline:
+        if R.world == 1 and args.full and not args.no_cpu_baseline:
             os.sched_setaffinity(0, R.host_cpus)      # "the host cores of the box", not the GPU's socket only
             table = loop.loss_fn.sample_scene_table(args.batch)
             out["cpu_baseline"] = cpu_baseline(args, loop.inp_h, loop.tgt_h, table)

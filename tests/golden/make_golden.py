@@ -515,6 +515,35 @@ def g13_unet_forward():
     save("g13_unet_forward.npz", **arrays)
 
 
+def g17_unet_models():
+    """row f4: the reference's SingleViewModel with and without coordinate channels and its MultiViewModel (N = 2
+    photos), each with a state dict the test can regenerate bit for bit (as g13), outputs on a stride-4 lattice and as
+    per-plane sums.  What tests/test_training_models.py compares the re-stated network with on the CPU."""
+    import models as ref_models
+    arrays = {}
+    for tag, cls, coords, shape, seed0 in (("single_coords", ref_models.SingleViewModel, True, (1, 3, 256, 256), 9600),
+                                           ("single_plain", ref_models.SingleViewModel, False, (1, 3, 256, 256), 9700),
+                                           ("multi_coords", ref_models.MultiViewModel, True, (1, 2, 3, 256, 256), 9800)):
+        torch.manual_seed(0)
+        model = cls(use_coords=coords).eval()
+        state, stats = _deterministic_state(model, seed0)
+        model.load_state_dict(state)
+        x = synth.uniform01(seed0 + 400, shape)
+        with torch.no_grad():
+            y = model(torch.from_numpy(x)).numpy()
+        arrays[tag + "__keys"] = np.array([k for k, _, _, _ in stats])
+        arrays[tag + "__shapes"] = np.array([",".join(map(str, sh)) for _, sh, _, _ in stats])
+        arrays[tag + "__mean"] = np.array([m for _, _, m, _ in stats], np.float32)
+        arrays[tag + "__std"] = np.array([sd for _, _, _, sd in stats], np.float32)
+        arrays[tag + "__seed0"] = np.int64(seed0)
+        arrays[tag + "__input_seed"] = np.int64(seed0 + 400)
+        arrays[tag + "__input_shape"] = np.array(shape, np.int64)
+        arrays[tag + "__out_shape"] = np.array(y.shape, np.int64)
+        arrays[tag + "__out_lattice"] = y[:, :, ::4, ::4].copy()
+        arrays[tag + "__out_plane_sums"] = y.astype(np.float64).sum(axis=(2, 3))
+    save("g17_unet_models.npz", **arrays)
+
+
 def _params(fn):
     """[[name, kind, default-or-None as repr]] of a callable, `self` dropped"""
     import inspect
@@ -739,6 +768,9 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--only-unet":           # row f4 network forward, added in round 2
         g13_unet_forward()
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "--only-unet-models":    # row f4, the CPU comparison without the reference tree
+        g17_unet_models()
+        return
     g1_render_64()
     g2_lattice(256, 8, 111)
     g2_lattice(512, 16, 112)
@@ -757,6 +789,7 @@ def main():
     g14_api()
     g15_float64()
     g16_second_order()
+    g17_unet_models()
     manifest = {
         "generator": "tests/golden/make_golden.py",
         "reference": "mworchel/svbrdf-estimation @ /root/reference (development/multiImage_pytorch)",

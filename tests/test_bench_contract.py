@@ -114,7 +114,8 @@ def test_bench_source_emits_the_contract_keys():
 
 
 def test_short_form_reports_the_median_region():
-    """bench.py's short forms time >= 9 regions and report the median one"""
+    """bench.py's short forms under --full time >= 9 regions and report the median one; a plain
+    run times one region of exactly --steps steps"""
     import bench
     assert bench.median_region_index([3.0]) == 0
     assert bench.median_region_index([5.0, 1.0, 3.0]) == 2
@@ -123,7 +124,7 @@ def test_short_form_reports_the_median_region():
     assert bench.median_region_index([1.0, 2.0, 3.0, 4.0]) == 2             # even count: the slower middle one
     with open(os.path.join(ROOT, "bench.py")) as f:
         src = f.read()
-    assert "n_regions = 1 if args.steps >= 256 else max(9, args.regions)" in src
+    assert "n_regions = 1 if args.steps >= 256 or not args.full else max(9, args.regions)" in src
 
 
 def _made_up_measurements(**over):
@@ -191,3 +192,79 @@ def test_line_assembly_one_clock_and_every_mode():
     json.loads(json.dumps(out))
     assert out["roofline"]["time_per_launch_ms"] is None and out["config"]["streams_per_gpu"] == 2
     assert abs(out["roofline"]["frac"] * 8e12 * out["ms_per_step"] * 1e-3 / alg - 1.0) < 1e-12
+
+
+def test_plain_run_is_lean_and_full_keeps_the_rest():
+    """`bench.py --gpus 1 --steps N --warmup W` measures the headline only; the follow-up legs, the secondary kernels and the
+    CPU baseline run with --full (off by default)"""
+    import bench
+    plain, full = _args("--steps", "20", "--warmup", "5"), _args("--steps", "20", "--warmup", "5", "--full")
+    assert not plain.full and plain.dump_outputs is None and full.full
+    assert not bench.follow_up_legs(plain) and bench.follow_up_legs(full)
+    assert not bench.follow_up_legs(_args("--full", "--timed-only"))
+    quiet = _made_up_measurements(clock_ghz=None, clock_note="not measured (no follow-up legs)", cycle_leg_ms=None,
+                                  other_ms_per_step=None, other_ms=[], other_steps=0, leg_steps=0,
+                                  engine_ms_per_step=None, engine_plain_ms_per_step=None, copy=None, kernel_ms=[],
+                                  kernel_ms_avg=None, job_elapsed=[0.00075], median_region=0, elapsed=0.00075, n_regions=1)
+    out, _ = bench.assemble_line(plain, quiet)
+    json.loads(json.dumps(out))
+    assert out["follow_up_legs"] == "skipped (plain run)" and out["timed_regions"]["count"] == 1
+    assert out["steps"] == 20 and out["warmup"] == 5 and abs(out["ms_per_step"] - 0.0375) < 1e-12
+    assert abs(out["value"] - 8 * 1e3 / out["ms_per_step"]) <= 1e-9 * out["value"]
+    assert out["metric"].startswith("rendered 256x256 patches/sec") and out["unit"] == "patches/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32"
+    with open(os.path.join(ROOT, "bench.py")) as f:
+        src = f.read()
+    assert "if R.world == 1 and args.full and not args.no_secondary:" in src
+    assert "if R.world == 1 and args.full and not args.no_cpu_baseline:" in src
+
+
+def test_dump_outputs_writes_float32_within_the_limit(tmp_path):
+    """--dump-outputs: the loss and the input gradient as float32 .npy; a gradient past the limit becomes a fixed sample"""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(5)
+    grad, loss = torch.randn(2, 12, 16, 16, generator=g), torch.tensor(0.25)
+    bench.dump_outputs(str(tmp_path / "a"), loss, grad)
+    assert sorted(os.listdir(tmp_path / "a")) == ["grad.npy", "loss.npy"]
+    got = np.load(tmp_path / "a" / "grad.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, grad.numpy()) and np.load(tmp_path / "a" / "loss.npy") == 0.25
+    big = torch.randn(4, 12, 64, 64, generator=g)                           # 768 KiB: past a limit of 1 MiB + 64 KiB
+    limit = 2 ** 20 + 2 ** 16
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), loss, big, limit=limit)
+    assert sorted(os.listdir(tmp_path / "b")) == ["grad_sample.npy", "loss.npy"]
+    s1, s2 = np.load(tmp_path / "b" / "grad_sample.npy"), np.load(tmp_path / "c" / "grad_sample.npy")
+    assert s1.dtype == np.float32 and s1.nbytes == limit // 2 and np.array_equal(s1, s2)        # the same positions each time
+    assert sum(os.path.getsize(tmp_path / "b" / n) for n in os.listdir(tmp_path / "b")) <= limit
+    assert np.isin(s1, big.numpy().reshape(-1)).all()
+
+
+@pytest.mark.gpu
+def test_plain_run_times_exactly_steps_and_dumps_the_same_outputs_every_run(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W --dump-outputs DIR` on the GPU: one timed region of exactly N steps, none of
+    the --full legs, and the loss and input gradient of the last timed step -- the same in two runs whose warm-up and settle
+    phases differ, so that two builds can be compared output for output"""
+    import subprocess
+    import sys
+    import numpy as np
+    lines = []
+    for name, warmup, settle in (("a", 5, 20), ("b", 12, 60)):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup",
+                            str(warmup), "--settle-ms", str(settle), "--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        found = [json.loads(l) for l in r.stdout.splitlines() if l.strip().startswith("{")]
+        assert len(found) == 1, r.stdout[-2000:]
+        lines.append(found[0])
+    for b in lines:
+        assert b["steps"] == 30 and b["timed_regions"]["count"] == 1 and b["follow_up_legs"] == "skipped (plain run)"
+        assert b["cpu_baseline"] is None and "secondary" not in b and b["copy_peak_GBps_measured"] is None
+        assert abs(b["value"] - 8 * 1e3 / b["ms_per_step"]) <= 1e-6 * b["value"]
+        assert abs(b["per_rank"]["elapsed_s"][0] * 1e3 / 30 - b["ms_per_step"]) <= 1e-9 * b["ms_per_step"]
+    ga, gb = np.load(tmp_path / "a" / "grad.npy"), np.load(tmp_path / "b" / "grad.npy")
+    la, lb = np.load(tmp_path / "a" / "loss.npy"), np.load(tmp_path / "b" / "loss.npy")
+    assert ga.dtype == np.float32 and ga.shape == (8, 12, 256, 256) and np.isfinite(ga).all() and np.abs(ga).max() > 0
+    assert np.array_equal(ga, gb) and np.array_equal(la, lb)
+    assert abs(float(la) - lines[0]["loss"]) <= 1e-6 * abs(float(la))

@@ -110,14 +110,14 @@ def test_bench_under_torch_distributed_run_with_the_kernels_in_it():
     """the driver's N > 1 command, word for word -- `python -m torch.distributed.run --nnodes=1 --nproc-per-node 2
     --master-addr 127.0.0.1 --master-port P bench.py --gpus 2 --steps 20 --warmup 5` -- on the one GPU a box has (plus the
     two flags that needs: gloo, every rank on cuda:0): the ranks come from the launcher's environment (no self-spawn),
-    LOCAL_RANK picks the device, the timed regions are the median of the job's (MAX over ranks), rank 0 alone prints"""
+    LOCAL_RANK picks the device, the timed regions (--full) are the median of the job's (MAX over ranks), rank 0 alone prints"""
     import socket
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                         "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                        "--warmup", "5", "--backend", "gloo", "--share-device", "--no-cpu-baseline", "--no-secondary"],
+                        "--warmup", "5", "--backend", "gloo", "--share-device", "--full", "--no-cpu-baseline", "--no-secondary"],
                        env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.strip().startswith("{") and l.strip().endswith("}")]

@@ -511,22 +511,86 @@ def test_a_fork_named_like_the_reference_renderer_is_a_plugin(monkeypatch):
     assert not losses.RenderingLoss(patched).uses_fused_kernel()
 
 
-_REFERENCE = "/root/reference/development/multiImage_pytorch"
+# stand-ins for the reference's flat modules (development/multiImage_pytorch): same module and class names and the call
+# shapes install() and the reference's scripts rely on, none of its code.  Their LocalRenderer is _FORK_SOURCE's class,
+# which has the reference's shape; the test pins ITS fingerprint in place of the recorded one (that the recorded one is
+# the reference's own renderer is what test_reference_code_identity_is_the_recorded_one checks against g14_api.json)
+_STAND_INS = {
+    "renderers.py": _FORK_SOURCE + """
+
+class RednerRenderer:
+    pass
+""",
+    "losses.py": """
+import renderers
+
+class SVBRDFL1Loss:
+    pass
+
+class RenderingLoss:
+    def __init__(self, renderer):
+        self.renderer = renderer
+
+class MixedLoss:
+    def __init__(self, renderer, l1_weight=0.1):
+        self.renderer, self.l1_weight = renderer, l1_weight
+""",
+    "environment.py": """
+class Camera:
+    def __init__(self, pos):
+        self.pos = pos
+
+class Light:
+    def __init__(self, pos, color):
+        self.pos, self.color = pos, color
+
+class Scene:
+    def __init__(self, camera, light):
+        self.camera, self.light = camera, light
+""",
+    "utils.py": """
+def gamma_encode(image):
+    return image ** (1.0 / 2.2)
+""",
+    "dataset.py": """
+import torch
+import environment
+import renderers
+
+class SvbrdfDataset:
+    def render_inputs(self, svbrdf, count):
+        # the dataloader's call shape: host [1,12,H,W] maps, tensor-valued positions and colour, one photo per call
+        renderer = renderers.LocalRenderer()
+        photos = []
+        for _ in range(count):
+            scene = environment.Scene(environment.Camera(torch.tensor([0.0, 0.0, 2.0])),
+                                      environment.Light(torch.tensor([0.3, -0.2, 2.0]), torch.tensor([20.0, 20.0, 20.0])))
+            photos.append(renderer.render(scene, svbrdf.unsqueeze(0)))
+        return torch.cat(photos, dim=0)
+""",
+}
 
 
-@pytest.mark.skipif(not os.path.isdir(_REFERENCE), reason="needs the reference checkout (build container only)")
-def test_install_patches_the_reference_modules_in_a_fresh_interpreter():
-    """INTEGRATION.md section 1 against the REAL reference, in a child interpreter (the reference's flat module names
-    would shadow this suite's): after ``svbrdf_estimation_amd.install()`` the reference's own import lines
+def test_install_patches_the_reference_modules_in_a_fresh_interpreter(tmp_path):
+    """INTEGRATION.md section 1 against modules laid out like the reference's, in a child interpreter (the flat module
+    names would shadow this suite's): after ``svbrdf_estimation_amd.install()`` the reference's own import lines
     (main.py:8,12; dataset.py:7,206) resolve to this engine's classes, RednerRenderer and the rest stay the
     reference's, and ``MixedLoss(LocalRenderer())`` (main.py:82-89) is wired to the fused kernel."""
     import subprocess
+    ref = str(tmp_path / "reference")
+    os.makedirs(ref)
+    for name, text in _STAND_INS.items():
+        with open(os.path.join(ref, name), "w") as f:
+            f.write(text)
     code = """
 import sys, types
 sys.dont_write_bytecode = True
 sys.modules.setdefault("cv2", types.ModuleType("cv2")); sys.modules.setdefault("pyredner", types.ModuleType("pyredner"))
 sys.path.insert(0, %r); sys.path.insert(0, %r)
 import svbrdf_estimation_amd as amd
+import renderers as ref_renderers
+from svbrdf_estimation_amd import _refcode
+_refcode.REFERENCE = dict(_refcode.REFERENCE, source=_refcode.fingerprint(ref_renderers.LocalRenderer)["source"])
 replaced = amd.install()
 from losses import MixedLoss                          # main.py:8
 from renderers import LocalRenderer, RednerRenderer   # main.py:12
@@ -540,16 +604,20 @@ loss_function = MixedLoss(LocalRenderer())            # main.py:82-89
 assert loss_function.rendering_loss.uses_fused_kernel() and loss_function.l1_weight == 0.1
 import dataset                                        # dataset.py:7 `import renderers` -> :206 renderers.LocalRenderer()
 assert dataset.renderers.LocalRenderer is LocalRenderer
-# the reference's OWN dataloader code reaches the patched renderer with its call shape (host [1,12,H,W] maps, tensor-valued
-# positions and colour, dataset.py:206-212): accepted up to the point where a GPU is needed, and on this GPU-less machine
-# the error names the way out (on an MI355X the call is served by K1: tests/test_gpu_parity.py)
+# the dataloader's call shape (host [1,12,H,W] maps, tensor-valued positions and colour, dataset.py:206-212) reaches the
+# patched renderer: on an MI355X it is served by K1 and a host tensor comes back; on a machine without a GPU the error
+# names the way out
 import torch
 class FakeSelf: use_augmentation = True
-try:
-    dataset.SvbrdfDataset.render_inputs(FakeSelf(), torch.rand(12, 16, 16), 2)
-    raise SystemExit("render_inputs computed something without a GPU")
-except amd.NativeLibraryError as e:
-    assert "patch_renderer=False" in str(e) and "no ROCm device" in str(e), e
+if torch.cuda.is_available():
+    photos = dataset.SvbrdfDataset.render_inputs(FakeSelf(), torch.rand(12, 16, 16), 2)
+    assert photos.device.type == "cpu" and photos.shape == (2, 3, 16, 16) and bool(torch.isfinite(photos).all())
+else:
+    try:
+        dataset.SvbrdfDataset.render_inputs(FakeSelf(), torch.rand(12, 16, 16), 2)
+        raise SystemExit("render_inputs computed something without a GPU")
+    except amd.NativeLibraryError as e:
+        assert "patch_renderer=False" in str(e) and "no ROCm device" in str(e), e
 # patch_renderer=False: the reference keeps ITS LocalRenderer (CPU dataloader workers), the losses still fuse
 renderers.LocalRenderer = replaced["renderers.LocalRenderer"]
 amd.install(patch_renderer=False)
@@ -574,6 +642,6 @@ renderers.normalize = lambda a: a
 assert not losses.RenderingLoss(renderers.LocalRenderer()).uses_fused_kernel()
 renderers.normalize = original
 print("INSTALL-OK")
-""" % (_REFERENCE, ROOT, _REFERENCE, _REFERENCE)
+""" % (ref, ROOT, ref, ref)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "INSTALL-OK" in r.stdout, r.stderr[-3000:]

@@ -1,15 +1,12 @@
 """CPU: row f4 -- the re-stated Deschaintre network.  Parameter counts are the reference's (SURVEY.md
-section 2 probe), and where the reference is mounted (the build container) the forward pass is
-compared with the reference's own models after converting its state dict."""
+section 2 probe), and the forward pass is compared with the reference's own models' (recorded in
+tests/golden/g17_unet_models.npz) after converting the state dict."""
 import os
-import sys
-import types
 
 import numpy as np
 import pytest
+import synth
 import torch
-
-REF = "/root/reference/development/multiImage_pytorch"
 
 
 def test_parameter_counts_match_the_reference():
@@ -20,51 +17,46 @@ def test_parameter_counts_match_the_reference():
     assert count(models.SingleViewModel(use_coords=True)) == 79985621 + 2 * (64 * 16 + 128)
 
 
-def _load_reference_models():
-    sys.dont_write_bytecode = True
-    sys.modules.setdefault("cv2", types.ModuleType("cv2"))
-    sys.modules.setdefault("pyredner", types.ModuleType("pyredner"))
-    saved = {k: sys.modules.get(k) for k in ("utils", "models")}
-    sys.path.insert(0, REF)
-    try:
-        for k in ("utils", "models"):
-            sys.modules.pop(k, None)
-        import models as ref_models
-        return ref_models
-    finally:
-        sys.path.remove(REF)
-        for k, v in saved.items():
-            if v is not None:
-                sys.modules[k] = v
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is only mounted in the build container")
-@pytest.mark.parametrize("use_coords", [True, False])
-def test_forward_equals_reference_models(use_coords):
+def _fixture_model(golden, cls, tag, use_coords):
+    """the re-stated network with the state dict of tests/golden/g17_unet_models.npz case `tag` (regenerated bit for bit,
+    keyed by the reference's parameter names), its input and the reference's output there"""
+    from test_dataset_golden import _regenerated_state
     from svbrdf_estimation_amd.training import models
-    ref_models = _load_reference_models()
-    torch.manual_seed(0)
-    ref = ref_models.SingleViewModel(use_coords=use_coords).eval()
-    mine = models.SingleViewModel(use_coords=use_coords).eval()
-    mine.load_state_dict(models.convert_reference_state_dict(ref.state_dict()))
-    x = torch.rand(1, 3, 256, 256)
+    g = golden("g17_unet_models.npz")
+    net = cls(use_coords=use_coords).eval()
+    net.load_state_dict(models.convert_reference_state_dict(_regenerated_state(g, tag)))
+    x = torch.from_numpy(synth.uniform01(int(g[tag + "__input_seed"]), tuple(int(v) for v in g[tag + "__input_shape"])))
+    return net, x, g
+
+
+def _assert_equals_reference(y, g, tag, rtol, atol):
+    assert y.shape == tuple(int(v) for v in g[tag + "__out_shape"])
+    np.testing.assert_allclose(y[:, :, ::4, ::4], g[tag + "__out_lattice"], rtol=rtol, atol=atol)
+    np.testing.assert_allclose(y.astype(np.float64).sum(axis=(2, 3)), g[tag + "__out_plane_sums"], rtol=rtol,
+                               atol=y.shape[2] * y.shape[3] * atol)
+
+
+@pytest.mark.parametrize("use_coords", [True, False])
+def test_forward_equals_reference_models(golden, use_coords):
+    """the reference's own models (models.py:322-411), recorded with regenerable weights by tests/golden/make_golden.py
+    (g17): the re-stated network loaded through convert_reference_state_dict computes their forward pass"""
+    from svbrdf_estimation_amd.training import models
+    tag = "single_coords" if use_coords else "single_plain"
+    mine, x, g = _fixture_model(golden, models.SingleViewModel, tag, use_coords)
     with torch.no_grad():
-        a, b = ref(x), mine(x)
-    assert a.shape == b.shape == (1, 12, 256, 256)
-    np.testing.assert_allclose(b.numpy(), a.numpy(), rtol=1e-5, atol=1e-6)
+        b = mine(x).numpy()
+    assert b.shape == (1, 12, 256, 256)
+    _assert_equals_reference(b, g, tag, rtol=1e-5, atol=1e-6)
     enc = models.SingleViewModel(use_coords=use_coords, decode=False).eval()
     enc.load_state_dict(mine.state_dict())
     with torch.no_grad():
         assert enc(x).shape == (1, 9, 256, 256)
     if use_coords:       # multi-view: N photos, max-pooled; the reference loops over photos, this batches them
-        torch.manual_seed(1)
-        ref_mv = ref_models.MultiViewModel(use_coords=True).eval()
-        mine_mv = models.MultiViewModel(use_coords=True).eval()
-        mine_mv.load_state_dict(models.convert_reference_state_dict(ref_mv.state_dict()))
-        xs = torch.rand(1, 2, 3, 256, 256)
+        mine_mv, xs, g = _fixture_model(golden, models.MultiViewModel, "multi_coords", True)
+        assert xs.shape == (1, 2, 3, 256, 256)
         with torch.no_grad():
             # batched generator pass vs the reference's per-photo loop: different conv blocking, fp32 noise
-            np.testing.assert_allclose(mine_mv(xs).numpy(), ref_mv(xs).numpy(), rtol=1e-4, atol=3e-5)
+            _assert_equals_reference(mine_mv(xs).numpy(), g, "multi_coords", rtol=1e-4, atol=3e-5)
 
 
 def test_tiled_png_round_trip(tmp_path):

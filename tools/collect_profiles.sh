@@ -16,22 +16,22 @@ if [ -z "${SKIP_SUITE:-}" ]; then
   tail -3 $OUT/${TAG}_gputest.txt
   cp $OUT/tolerance_uses.txt $OUT/${TAG}_tolerance_uses.txt 2>/dev/null
   # the driver's short form, twice on this box (`value` = the median of nine 20-step regions: the two must agree within 2 %)
-  python3 bench.py --steps 20 --warmup 5 > $OUT/${TAG}_bench_short.json 2> $OUT/${TAG}_bench_short.err
-  python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_short2.json 2> $OUT/${TAG}_bench_short2.err
+  python3 bench.py --full --steps 20 --warmup 5 > $OUT/${TAG}_bench_short.json 2> $OUT/${TAG}_bench_short.err
+  python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_short2.json 2> $OUT/${TAG}_bench_short2.err
   # training harness lines: RCCL world of one, and two DDP ranks sharing the device (the self-checking no_sync probe)
   python3 train.py --gpus 1 --force-dist --steps 10 --warmup 3 --batch 8 > $OUT/${TAG}_train_rccl_world1.json 2>/dev/null
   python3 train.py --gpus 2 --backend gloo --share-device --steps 10 --warmup 3 --batch 8 > $OUT/${TAG}_train_2ranks_share_device.json 2>/dev/null
 fi
 cd /tmp && export TMPDIR=/tmp
-BENCH="python3 $R/bench.py --no-cpu-baseline --no-secondary --timed-only"
+BENCH="python3 $R/bench.py --full --no-cpu-baseline --no-secondary --timed-only"
 # kernel-trace + stats (no counters in these passes): the default command (every step on one stream: the duration of a
 # launch on its own) and the same with the steps alternating on two streams (launches overlap, so the per-launch duration
 # exceeds a launch's share of the GPU: what bench.py reports as two_streams_overlapped)
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats --output-format csv -- $BENCH --steps 400 --warmup 50 > $OUT/${TAG}_stats.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats2 --output-format csv -- $BENCH --steps 400 --warmup 50 --streams 2 > $OUT/${TAG}_stats2.log 2>&1
-# ... and of the DEFAULT command as it is (2,000 steps, every untimed follow-up leg included): the verbatim average then mixes
-# in the overlapped launches of the two-stream leg, so the summary also splits the per-dispatch trace by stream
-timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_statsdef --output-format csv -- python3 $R/bench.py --no-cpu-baseline --no-secondary > $OUT/${TAG}_statsdef.log 2>&1
+# ... and of the default step counts with --full (2,000 steps, every untimed follow-up leg included): the verbatim average
+# then mixes in the overlapped launches of the two-stream leg, so the summary also splits the per-dispatch trace by stream
+timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_statsdef --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --no-secondary > $OUT/${TAG}_statsdef.log 2>&1
 # the counter passes run one launch at a time (--streams 1) over the six rotating batches (302 MB: beyond the Infinity Cache)
 BENCH="$BENCH --streams 1"
 # HBM traffic: FETCH_SIZE and WRITE_SIZE need separate passes (TCC slots)
@@ -56,7 +56,7 @@ for c in ${SQ_CASES:-k3_untied k3_config4 k3_config5}; do
 done
 cd $R
 # un-profiled bench line (with the CPU baseline) -- never compare profiled and un-profiled timings
-timeout 400 python3 bench.py > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
+timeout 400 python3 bench.py --full > $OUT/${TAG}_bench.json 2> $OUT/${TAG}_bench.err
 # back-to-back launches through the C ABI, cycles at the clock under load (the GPU suite's speed guard, as a script)
 PERF_GUARD_REPEATS=2 timeout 200 python3 tests/test_gpu_perf_guard.py > $OUT/${TAG}_perf_guard.txt 2>&1 && cp $OUT/perf_guard.json $OUT/${TAG}_perf_guard.json
 timeout 60 python3 tools/clock_timeline.py > $OUT/${TAG}_clock_timeline.txt 2>&1
