@@ -170,3 +170,23 @@ def loss_tie_map(input, target, scenes, eps=0.1, xrow=None):
     if rc:
         raise RuntimeError("oracle loss_tie_map rc=%d" % rc)
     return out
+
+
+def loss_tie_allowance(input, target, scenes, eps=0.1, l1_weight=0.0, xrow=None, tie_level=1e-6):
+    """[B,12,H,W] float64: per gradient element, 2 * sum over the pixel's tied terms of |sign-free contribution|.
+
+    A term (scene, channel) is tied where loss_tie_map counts it and |log difference| < tie_level (tests/tolerances.py
+    TIE_LEVEL): there its sign() is rounding noise and an fp32 gradient may carry either sign, which moves an element by
+    at most twice the term's contribution.  Zero at untied pixels.  `l1_weight` is accepted for symmetry with
+    mixed_loss: the L1 part of MixedLoss has no such ties and does not change the allowance."""
+    del l1_weight
+    input, scenes, B, S, H, W = _dims(input, scenes)
+    target = _f32(target)
+    assert target.shape == input.shape
+    xrow = make_xrow(W) if xrow is None else _f32(xrow)
+    out = np.empty((B, 12, H, W), dtype=np.float64)
+    rc = lib().svbrdf_oracle_loss_tie_allowance(_p(input), _p(target), _p(scenes), _p(xrow), ctypes.c_float(eps),
+                                                ctypes.c_double(tie_level), _p(out, _f64p), B, S, H, W)
+    if rc:
+        raise RuntimeError("oracle loss_tie_allowance rc=%d" % rc)
+    return out

@@ -275,11 +275,16 @@ static int FN(render_bwd)(const float *maps, const float *scenes, const float *x
 /* losses.py:29-52 with the scenes given explicitly ([B,S,9]); with l1_weight != 0 also
  * losses.py:7-19 (SVBRDFL1Loss: L1 of normals and roughness, L1 of log(x+eps_l1) for
  * diffuse and specular, each a mean over B*3*H*W) combined as in losses.py:62-63
- * (MixedLoss = l1_weight * L1 + rendering). */
+ * (MixedLoss = l1_weight * L1 + rendering).
+ * tie_allow (optional, [B,12,H,W]): per gradient element, 2 * sum over the pixel's tied terms -- those the tie map
+ * counts (not a structural zero) with |delta| < tie_level -- of |that term's sign-free contribution| (shade_bwd of
+ * g_rad = invN / ai in its one channel).  Where sign(delta) is rounding noise an fp32 evaluation may pick either sign
+ * (or 0), which moves the gradient by at most that much.  The L1 part never adds to it. */
 static int FN(rendering_loss)(const float *input, const float *target,
                               const float *scenes, const float *xrow, float eps,
                               float l1_weight, float eps_l1,
                               double *loss_out, OUT_T *grad_input, OUT_T *min_abs_delta,
+                              OUT_T *tie_allow, double tie_level,
                               int B, int S, int H, int W)
 {
     const size_t plane = (size_t)H * W;
@@ -301,6 +306,7 @@ static int FN(rendering_loss)(const float *input, const float *target,
             REAL n[3], d[3], r[3], s[3], tn[3], td[3], tr[3], ts[3];
             REAL gn[3] = {0, 0, 0}, gd[3] = {0, 0, 0}, gr[3] = {0, 0, 0}, gs[3] = {0, 0, 0};
             REAL tie = (REAL)1e30;      /* smallest |log difference| of this pixel: sign() is noise below ~1e-6 */
+            REAL al[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   /* tie allowance of the 12 gradient elements */
             FN(load_maps)(mi, plane, pix, n, d, r, s);
             FN(load_maps)(mt, plane, pix, tn, td, tr, ts);
             if (l1_weight != 0.0f) {
@@ -331,14 +337,26 @@ static int FN(rendering_loss)(const float *input, const float *target,
                     rowsum += (double)(delta < 0 ? -delta : delta);
                     /* structural zero: both renderings are exactly 0 because the light is clearly below
                      * both surfaces' horizon (LN+ clamp) -- sign(0) = 0 in every implementation */
-                    if (!(ci.ln_raw < (REAL)-1e-6 && ct.ln_raw < (REAL)-1e-6))
+                    int structural = ci.ln_raw < (REAL)-1e-6 && ct.ln_raw < (REAL)-1e-6;
+                    if (!structural)
                         if ((delta < 0 ? -delta : delta) < tie) tie = (delta < 0 ? -delta : delta);
                     g_rad[k] = sg * invN / ai;
+                    if (tie_allow && !structural && (double)(delta < 0 ? -delta : delta) < tie_level) {
+                        REAL one[3] = {0, 0, 0}, z[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                        int e;
+                        one[k] = invN / ai;
+                        FN(shade_bwd)(&g, &ci, d, r, one, z, z + 3, z + 6, z + 9);
+                        for (e = 0; e < 12; ++e)
+                            al[e] += z[e] < 0 ? -z[e] : z[e];
+                    }
                 }
                 if (grad_input)
                     FN(shade_bwd)(&g, &ci, d, r, g_rad, gn, gd, gr, gs);
             }
             if (min_abs_delta) min_abs_delta[(size_t)b * plane + pix] = (OUT_T)tie;
+            if (tie_allow)
+                for (k = 0; k < 12; ++k)
+                    tie_allow[(size_t)b * 12 * plane + (size_t)k * plane + pix] = (OUT_T)((REAL)2 * al[k]);
             if (grad_input) {
                 OUT_T *gm = grad_input + (size_t)b * 12 * plane + pix;
                 for (k = 0; k < 3; ++k) {

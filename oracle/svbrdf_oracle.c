@@ -121,7 +121,7 @@ EXPORT int svbrdf_oracle_rendering_loss(const float *input, const float *target,
                                         int B, int S, int H, int W)
 {
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f32(input, target, scenes, xrow, eps, 0.0f, 0.01f, loss_out, grad_input, NULL, B, S, H, W);
+    return e ? e : rendering_loss_f32(input, target, scenes, xrow, eps, 0.0f, 0.01f, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
 }
 
 /* losses.py:54-63 MixedLoss = l1_weight * SVBRDFL1Loss + RenderingLoss */
@@ -132,7 +132,7 @@ EXPORT int svbrdf_oracle_mixed_loss(const float *input, const float *target,
                                     int B, int S, int H, int W)
 {
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f32(input, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, grad_input, NULL, B, S, H, W);
+    return e ? e : rendering_loss_f32(input, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
 }
 
 /* per pixel: the smallest |log(render(input)+eps) - log(render(target)+eps)| over scenes and channels,
@@ -145,7 +145,20 @@ EXPORT int svbrdf_oracle_loss_tie_map(const float *input, const float *target, c
 {
     double loss;
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, 0.0f, 0.01f, &loss, NULL, min_abs_delta, B, S, H, W);
+    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, 0.0f, 0.01f, &loss, NULL, min_abs_delta, NULL, 0.0, B, S, H, W);
+}
+
+/* per gradient element of the rendering loss: the largest amount by which the sign() of tied terms (those
+ * svbrdf_oracle_loss_tie_map counts, with |delta| < tie_level) can move it -- 2 * sum of the absolute sign-free
+ * contributions of the pixel's tied terms, evaluated in double (svbrdf_core.inc).  0 at untied pixels. */
+EXPORT int svbrdf_oracle_loss_tie_allowance(const float *input, const float *target, const float *scenes,
+                                            const float *xrow, float eps, double tie_level, double *allowance,
+                                            int B, int S, int H, int W)
+{
+    double loss;
+    int e = check_dims(B, S, H, W);
+    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, 0.0f, 0.01f, &loss, NULL, NULL, allowance,
+                                      tie_level, B, S, H, W);
 }
 
 /* ---- network head: models.py:338-346 -> utils.py:73-98 ----------------
@@ -235,10 +248,10 @@ EXPORT int svbrdf_oracle_head_loss(const float *enc, const float *target, const 
     if (!maps || !len || (grad9 && !g64)) { free(maps); free(len); free(g64); return -5; }
     head_decode(enc, maps, len, B, H, W);
     if (f64) {
-        rc = rendering_loss_f64(maps, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, g64, NULL, B, S, H, W);
+        rc = rendering_loss_f64(maps, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, g64, NULL, NULL, 0.0, B, S, H, W);
     } else {
         if (grad9) g32 = (float *)malloc(n12 * sizeof(float));
-        rc = rendering_loss_f32(maps, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, g32, NULL, B, S, H, W);
+        rc = rendering_loss_f32(maps, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, g32, NULL, NULL, 0.0, B, S, H, W);
         if (grad9) for (i = 0; i < n12; ++i) g64[i] = (double)g32[i];
         free(g32);
     }
@@ -268,7 +281,7 @@ EXPORT int svbrdf_oracle_rendering_loss_f64(const float *input, const float *tar
                                             int B, int S, int H, int W)
 {
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, 0.0f, 0.01f, loss_out, grad_input, NULL, B, S, H, W);
+    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, 0.0f, 0.01f, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
 }
 
 EXPORT int svbrdf_oracle_mixed_loss_f64(const float *input, const float *target,
@@ -278,5 +291,5 @@ EXPORT int svbrdf_oracle_mixed_loss_f64(const float *input, const float *target,
                                         int B, int S, int H, int W)
 {
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, grad_input, NULL, B, S, H, W);
+    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
 }

@@ -155,6 +155,42 @@ def g3_loss(name, B, H, seed, rng_seed, n_random=3, n_specular=6, tiled=True):
          mixed_loss=np.float32(mixed.item()), mixed_grad=x3.grad.numpy())
 
 
+def g3_loss_at_size(name, B, H, seed, rng_seed, n_random, n_specular, stride, tags=("render", "mixed")):
+    """K3 at a BASELINE size.  Inputs are synth.make_maps(seed / seed + 1) stored as seed + sha256; the scene table is
+    what the loss drew under torch.manual_seed(rng_seed).  Per loss: the float32 loss, the gradient on a stride
+    lattice, its per-plane float64 sum and sum of |g| and the full-plane max|g| (the lattice's scale)."""
+    inp = synth.make_maps(seed, B, H)
+    tgt = synth.make_maps(seed + 1, B, H)
+    arrays = dict(synth_seed=np.int64(seed), B=np.int64(B), H=np.int64(H), stride=np.int64(stride),
+                  rng_seed=np.int64(rng_seed), n_random=np.int64(n_random), n_specular=np.int64(n_specular),
+                  input_sha256=np.array(synth.checksum(inp)), target_sha256=np.array(synth.checksum(tgt)))
+    for tag in tags:
+        x = torch.from_numpy(inp).clone().requires_grad_(True)
+        if tag == "render":
+            fn = rl = ref_losses.RenderingLoss(ref_renderers.LocalRenderer())
+        else:
+            fn = ref_losses.MixedLoss(ref_renderers.LocalRenderer())
+            rl = fn.rendering_loss
+        rl.random_configuration_count, rl.specular_configuration_count = n_random, n_specular
+        torch.manual_seed(rng_seed)
+        with _Recorder() as rec:
+            loss = fn(x, torch.from_numpy(tgt))
+        loss.backward()
+        table = rec.table()
+        if "scenes" in arrays:
+            assert np.array_equal(arrays["scenes"], table)
+        arrays["scenes"] = table
+        g = x.grad.numpy()
+        g64 = g.astype(np.float64)
+        arrays.update({tag + "_loss": np.float32(loss.item()),
+                       tag + "_grad_lattice": g[:, :, ::stride, ::stride].copy(),
+                       tag + "_grad_sum": g64.sum(axis=(2, 3)),
+                       tag + "_grad_abs_sum": np.abs(g64).sum(axis=(2, 3)),
+                       tag + "_grad_max": np.float32(np.abs(g).max())})
+        del x, loss, g, g64
+    save(name, **arrays)
+
+
 def g4_edge_cases():
     """small crafted patches; each case: maps [B,12,H,W], one scene, out, cotangent, grad"""
     H = 16
@@ -767,6 +803,10 @@ def main():
         return
     if len(sys.argv) > 1 and sys.argv[1] == "--only-unet":           # row f4 network forward, added in round 2
         g13_unet_forward()
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "--only-loss-at-size":    # K3 against the reference at BASELINE sizes
+        g3_loss_at_size("g3_loss_256_b8.npz", 8, 256, 151, 17, 3, 6, 8)                      # config 2 (bench.py)
+        g3_loss_at_size("g3_loss_512_s32.npz", 2, 512, 161, 19, 11, 21, 8, tags=("mixed",))  # config 5 per item
         return
     if len(sys.argv) > 1 and sys.argv[1] == "--only-unet-models":    # row f4, the CPU comparison without the reference tree
         g17_unet_models()

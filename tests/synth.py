@@ -59,3 +59,14 @@ def make_maps(seed, B, H, W=None, tilt=0.3, r_lo=0.0, r_hi=1.0, tiled_roughness=
 
 def checksum(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def loss_fixture_maps(g):
+    """input and target of a tests/golden/g3_loss_<size> fixture, regenerated from its seed (make_maps(seed) and
+    make_maps(seed + 1)) and checked against the stored sha256"""
+    B, H, seed = int(g["B"]), int(g["H"]), int(g["synth_seed"])
+    inp, tgt = make_maps(seed, B, H), make_maps(seed + 1, B, H)
+    assert checksum(inp) == str(g["input_sha256"]) and checksum(tgt) == str(g["target_sha256"]), \
+        "synthetic inputs are not bit-reproducible here"
+    return inp, tgt
+

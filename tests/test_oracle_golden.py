@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 import synth
-from tolerances import (assert_grad_close, assert_loss_close, assert_render_strict,
+from tolerances import (assert_grad_close, assert_loss_at_size, assert_loss_close, assert_render_strict,
                         assert_render_vs_reference)
 
 
@@ -73,6 +73,25 @@ def test_mixed_loss_and_gradient(oracle, golden, name):
     r, gr = oracle.rendering_loss(g["input"], g["target"], g["scenes"])
     assert_loss_close(l1 - r, g["l1_loss"], name + " l1")
     assert_grad_close(gl1 - gr, g["l1_grad"], name + " l1 grad")
+
+
+@pytest.mark.parametrize("name", ["g3_loss_256_b8.npz", "g3_loss_512_s32.npz"])
+def test_loss_at_baseline_size_against_the_reference(oracle, golden, name):
+    """K3's shapes at BASELINE size (config 2: B=8, 256x256, 9 scenes; config 5's per-item shape: 512x512, 11 + 21
+    scenes, MixedLoss): the oracle against the reference's own loss and gradient"""
+    g = golden(name)
+    inp, tgt = synth.loss_fixture_maps(g)
+    table = g["scenes"]
+    assert table.shape == (int(g["B"]), int(g["n_random"]) + int(g["n_specular"]), 9)
+    oracle.set_threads(oracle.max_threads())
+    tie, allow = oracle.loss_tie_map(inp, tgt, table), oracle.loss_tie_allowance(inp, tgt, table)
+    tags = [t for t, _ in (("render", 0), ("mixed", 0)) if t + "_loss" in g.files]
+    assert tags == (["render", "mixed"] if "256" in name else ["mixed"])
+    for tag in tags:
+        w = 0.1 if tag == "mixed" else 0.0
+        loss, grad = oracle.mixed_loss(inp, tgt, table, w)
+        _, g64 = oracle.mixed_loss(inp, tgt, table, w, f64=True)
+        assert_loss_at_size(g, tag, loss, grad, g64, tie, allow, "%s %s oracle" % (name, tag))
 
 
 def test_edge_cases(oracle, golden):
