@@ -158,6 +158,10 @@ __device__ __forceinline__ VConst make_vconst()
     return VConst{vreg(kMinDot), vreg(kPi), vreg(1.0f / kPi), vreg(0.693147180559945309417f), vreg(1.0e30f)};
 }
 
+// The rendering loss works on radiances scaled by 2^-10 (loss_pixel_scene): an exact power of two, folded into the light
+// factor of its geometry (v_ldexp with an inline-constant exponent: no literal operand)
+constexpr int kLossScaleExp = -10;
+
 // ------------------------------------------------------------------------------------------
 // per-pixel device code
 // ------------------------------------------------------------------------------------------
@@ -167,12 +171,15 @@ struct Geom {           // map-independent, shared by input and target and by th
     float wix, wiy, wiz;
     float hx, hy, hz;
     float p;            // (1 - VH)^5               renderers.py:32
-    float E[3];         // light_color * falloff     renderers.py:98-100
+    float E[3];         // light_color * falloff     renderers.py:98-100   (x 2^-10 in the loss kernels)
 };
 
 // renderers.py:73-82, 91-93, 45, 49, 99.  `sc` (9 floats) is wave-uniform.  Everything up to
 // h reproduces the reference's rounding sequence exactly (see the header of this file).
-__device__ __forceinline__ Geom geometry(const VConst &K, const float sc[9], float x, float y)
+// LOSS: E carries the loss's exact 2^-10 radiance scale (kLossScaleExp), one instruction per render instead of one per
+// channel and map.
+template <bool LOSS = false>
+__device__ __forceinline__ Geom geometry([[maybe_unused]] const VConst &K, const float sc[9], float x, float y)
 {
     Geom g;
     const float rcx = sc[0] - x, rcy = sc[1] - y, rcz = sc[2];   // z of the patch is 0
@@ -188,13 +195,13 @@ __device__ __forceinline__ Geom geometry(const VConst &K, const float sc[9], flo
     const float sx = g.wix + g.wox, sy = g.wiy + g.woy, sz = g.wiz + g.woz;
     const Recip ih = length_rn(dot3(sx, sy, sz, sx, sy, sz), yh);
     g.hx = div_rn(sx, ih); g.hy = div_rn(sy, ih); g.hz = div_rn(sz, ih);
-    // from here on the computation is well conditioned: 1-ULP primitives are enough
-    // (wo.h feeds only the Fresnel factor: no exact dot product needed)
-    const float VH = fmaxf(fma_(g.wox, g.hx, fma_(g.woy, g.hy, g.woz * g.hz)), K.tiny);
-    const float t = 1.0f - VH;
+    // from here on the computation is well conditioned: 1-ULP primitives are enough.  wo.h feeds only the Fresnel
+    // factor, and for unit wo, wi it is |wo + wi|/2 = ih.b/2 (wo.(wo + wi) = 1 + wo.wi = |wo + wi|^2/2): no dot product.
+    // 1 - max(VH, 1e-3) = min(1 - VH, 1 - 1e-3), and 1 - ih.b/2 is one rounding (the halving is exact).
+    const float t = fminf(fma_(-0.5f, ih.b, 1.0f), 1.0f - kMinDot);
     const float t2 = t * t;
     g.p = (t2 * t2) * t;
-    const float fall = yl * yl;                       // 1/|L|^2 (renderers.py:99), rsq seed squared
+    const float fall = LOSS ? __builtin_amdgcn_ldexpf(yl * yl, kLossScaleExp) : yl * yl;   // 1/|L|^2 (renderers.py:99), rsq seed squared
 #pragma unroll
     for (int k = 0; k < 3; ++k) g.E[k] = sc[6 + k] * fall;
     return g;
@@ -282,7 +289,9 @@ struct Lobe {
     float GD, KA, KV, KL, KN;
 };
 
-template <bool BWD>
+// FUSE_PX: PX = XN + sX as one FMA (one rounding, one instruction less per term).  The three-lobe loss loop keeps the
+// separate product: the FMA holds yX longer, and at its 128-VGPR limit that spilled around the loop.
+template <bool BWD, bool FUSE_PX = true>
 __device__ __forceinline__ Lobe lobe(const VConst &K, float A, float oA, const Dots &d)
 {
     Lobe l;
@@ -290,8 +299,8 @@ __device__ __forceinline__ Lobe lobe(const VConst &K, float A, float oA, const D
     // sqrt as y*rsq(y) in the forward-only and the forward+backward instantiation alike, so
     // that input and target shading are the SAME arithmetic (identical maps -> loss exactly 0)
     const float iV = rsq_(yV), iL = rsq_(yL);
-    const float sV = yV * iV, sL = yL * iL;
-    const float PV = d.VN + sV, PL = d.LN + sL;
+    const float PV = FUSE_PX ? fma_(yV, iV, d.VN) : d.VN + yV * iV;
+    const float PL = FUSE_PX ? fma_(yL, iL, d.LN) : d.LN + yL * iL;
     const float PP = PV * PL;                           // 4 VN LN / G
     const float den_raw = fma_(d.NH2, A, d.oN);
     const float den = fmaxf(den_raw, K.tiny);           // renderers.py:26 clamp
@@ -315,11 +324,11 @@ __device__ __forceinline__ Lobe lobe(const VConst &K, float A, float oA, const D
     return l;
 }
 
-// radiance of one pixel under one scene: renderers.py:43-65, 95-100.  NL = 3: one lobe per
-// colour channel (independent roughness channels); NL = 1: tied roughness, one lobe.
+// BRDF of one pixel under one scene: renderers.py:43-65.  NL = 3: one lobe per colour channel (independent roughness
+// channels); NL = 1: tied roughness, one lobe.
 template <int NL, bool BWD>
-__device__ __forceinline__ void shade(const VConst &K, const Geom &g, const MapK &m, const Dots &d, Lobe lb[NL],
-                                      float F[3], float f[3], float rad[3])
+__device__ __forceinline__ void brdf(const VConst &K, const Geom &g, const MapK &m, const Dots &d, Lobe lb[NL],
+                                     float F[3], float f[3])
 {
 #pragma unroll
     for (int l = 0; l < NL; ++l) lb[l] = lobe<BWD>(K, m.A[l], m.oA[l], d);
@@ -328,15 +337,46 @@ __device__ __forceinline__ void shade(const VConst &K, const Geom &g, const MapK
         F[k] = fma_(m.oms[k], g.p, m.s[k]);                               // Schlick, renderers.py:29-32
         // f = (1-F) d/pi + F GD (renderers.py:18-20, 62-65; GD carries the 1/(4 VN LN)) as d/pi + F (GD - d/pi)
         f[k] = fma_(F[k], lb[NL == 3 ? k : 0].GD - m.dpi[k], m.dpi[k]);
-        rad[k] = f[k] * (g.E[k] * d.LNp);
     }
+}
+
+// radiance of one pixel under one scene: renderers.py:43-65, 95-100
+template <int NL, bool BWD>
+__device__ __forceinline__ void shade(const VConst &K, const Geom &g, const MapK &m, const Dots &d, Lobe lb[NL],
+                                      float F[3], float f[3], float rad[3])
+{
+    brdf<NL, BWD>(K, g, m, d, lb, F, f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) rad[k] = f[k] * (g.E[k] * d.LNp);
+}
+
+// the same for the loss kernels, which need (radiance + eps) 2^-10 only: b = f (E 2^-10 LN+) + eps 2^-10 in one rounding
+// (the scale rides in g.E, geometry<true>; `ec` = eps 2^-10)
+template <int NL, bool BWD>
+__device__ __forceinline__ void shade_loss(const VConst &K, const Geom &g, const MapK &m, const Dots &d, Lobe lb[NL],
+                                           float F[3], float f[3], float ec, float b[3])
+{
+    brdf<NL, BWD>(K, g, m, d, lb, F, f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) b[k] = fma_(f[k], g.E[k] * d.LNp, ec);
+}
+
+// d|lg|/d b in the loss kernels' units: -sign(lg) M, M = N^-1/b (see loss_pixel_scene), sign(0) = 0.  |lg| * 1e30 is
+// >= 8e22 for every lg != 0 (a log2 of a quotient that is not 1: |lg| >= 2^-24 / ln 2) while M <= 1/(3 eps 2^-10) <= 4e11
+// (eps >= 1e-9, host check), so one clamp of -lg * 1e30 to [-M, M] gives exactly -M, +M or 0 (a NaN lg gives -M or +M,
+// like the select of the sign bit it replaces)
+__device__ __forceinline__ float loss_grad_of_b(const VConst &K, float lg, float M)
+{
+    return __builtin_amdgcn_fmed3f(-lg * K.huge, -M, M);
 }
 
 // adjoint of shade() with PyTorch's sub-gradient conventions: clamp(min=m) passes the
 // gradient iff x >= m (inclusive); xi() has zero gradient (renderers.py:15-16).
 // DEFER_D / DEFER_R: acc.d accumulates g_f (1-F) without the 1/pi and acc.r accumulates gGD KA without dA/dr_hat; the
-// caller applies the two per-pixel constants once after its scene loop (apply_deferred_scales).
-template <int NL, bool DEFER_D = false, bool DEFER_R = false>
+// caller applies the two per-pixel constants once after its scene loop (loss_scene_loop).  DEFER_S (with DEFER_D): acc.d
+// accumulates g_f (1-p) only, as 1 - F = 1 - s - (1-s) p = (1-s)(1-p); the caller applies (1-s) with the 1/pi.  g_f (1-p)
+// also serves the specular gradient g_f (GD - d/pi)(1-p): one instruction less per channel.
+template <int NL, bool DEFER_D = false, bool DEFER_R = false, bool DEFER_S = false>
 __device__ __forceinline__ void shade_bwd(const VConst &K, const Geom &g, const MapK &m, const Dots &d, const Lobe lb[NL],
                                           const float F[3], const float f[3], const float g_rad[3], Grad &acc)
 {
@@ -351,9 +391,15 @@ __device__ __forceinline__ void shade_bwd(const VConst &K, const Geom &g, const 
         const float gE = g_rad[k] * g.E[k];
         const float g_f = gE * d.LNp;
         g_LNp = k == 0 ? gE * f[k] : fma_(gE, f[k], g_LNp);
-        const float g_F = g_f * (l.GD - m.dpi[k]);                        // f = d/pi + F (GD - d/pi)
-        acc.s[k] = fma_(g_F, omp, acc.s[k]);
-        acc.d[k] = DEFER_D ? fma_(g_f, 1.0f - F[k], acc.d[k]) : fma_(g_f * (1.0f - F[k]), inv_pi, acc.d[k]);
+        if (DEFER_S) {
+            const float gfo = g_f * omp;
+            acc.s[k] = fma_(gfo, l.GD - m.dpi[k], acc.s[k]);
+            acc.d[k] += gfo;
+        } else {
+            const float g_F = g_f * (l.GD - m.dpi[k]);                    // f = d/pi + F (GD - d/pi)
+            acc.s[k] = fma_(g_F, omp, acc.s[k]);
+            acc.d[k] = DEFER_D ? fma_(g_f, 1.0f - F[k], acc.d[k]) : fma_(g_f * (1.0f - F[k]), inv_pi, acc.d[k]);
+        }
         const float gGD = g_f * F[k];                                     // d loss/d GD
         acc.r[k] = DEFER_R ? fma_(gGD, l.KA, acc.r[k]) : fma_(gGD * l.KA, m.r4m[k], acc.r[k]);
         if (NL == 3 || k == 0) W[NL == 3 ? k : 0] = gGD;
@@ -889,33 +935,30 @@ template <int NL, bool WITH_GRAD, int DEFER = 0>
 __device__ __forceinline__ void loss_pixel_scene(const VConst &K, const Geom &g, const MapK &mi,
                                                  const MapK &mt, float eps, float inv_count, float &lsum, Grad &acc)
 {
-    float rt[3];
+    const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
+    float bt[3];
     {
         const Dots dt = dots(K, g, mt);
         Lobe lt[NL];
         float Ft[3], ft[3];
-        shade<NL, false>(K, g, mt, dt, lt, Ft, ft, rt);
+        shade_loss<NL, false>(K, g, mt, dt, lt, Ft, ft, ec, bt);
     }
     const Dots di = dots(K, g, mi);
     Lobe li[NL];
-    float Fi[3], fi[3], ri[3], g_rad[3];
-    shade<NL, WITH_GRAD>(K, g, mi, di, li, Fi, fi, ri);
+    float Fi[3], fi[3], b[3], g_rad[3];
+    shade_loss<NL, WITH_GRAD>(K, g, mi, di, li, Fi, fi, ec, b);
     // losses.py:46-50: |log(ri + eps) - log(rt + eps)| and its derivative sign/(N (ri + eps)).
     // Transcendentals are what this kernel pays most for (~16 issue cycles each against ~2.5 for a
     // plain instruction once several waves share the SIMD: profiles/r01_k3_cycles.txt),
     // so the nine of the reference's formulation (six logs, three reciprocals) are done with four:
     //  * the three 1/ai come from ONE v_rcp of their product (6 multiplies).  Operands are scaled
-    //    by 2^-10 (exact) so that the product stays in range for eps <= ai <= 7e15, eps >= 1e-9
-    //    (checked on the host);
+    //    by 2^-10 (exact, carried by the light factor g.E) so that the product stays in range for
+    //    eps <= ai <= 7e15, eps >= 1e-9 (checked on the host);
     //  * log(ai) - log(at) = -log(at/ai): one log per channel on the quotient formed with that 1/ai.
     // ai == at must give exactly 0 like the reference's log(x) - log(x) (identical maps: zero loss,
     // zero gradient, sign(0) = 0), hence the explicit select.
     {
-        constexpr float c = 9.765625e-04f;               // 2^-10
-        const float ec = eps * c, nc = inv_count * c;
-        float b[3], bt[3], ib[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { b[k] = fma_(ri[k], c, ec); bt[k] = fma_(rt[k], c, ec); }   // = (r + eps) * c, one rounding
+        float ib[3];
         {
             const float P = b[0] * b[1];
             const float r = rcp_(P * b[2]);
@@ -925,18 +968,17 @@ __device__ __forceinline__ void loss_pixel_scene(const VConst &K, const Geom &g,
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             // lg = log2(at/ai) = -(log(ai) - log(at))/ln2.  The loss sums |lg| (scaled by ln2 ONCE, after the scene
-            // loop); d|delta|/d ri = sign(delta)/(N ai) = -sign(lg) nc/b: the magnitude nc*ib takes lg's sign bit with
-            // one v_and_or, and the minus rides as a source modifier on the product that consumes it.  sign(0) = 0 as in
-            // torch: equal operands select lg = 0 explicitly, and lg == 0 -- equal operands, or a quotient of unequal
-            // ones that rounds to exactly 1 -- selects magnitude 0 (a +0 there would otherwise always read as "input
-            // darker": a systematic sign at near-ties where the reference's rounded log difference gives 0).
+            // loop); d|delta|/d ri = sign(delta)/(N ai) = -sign(lg) 2^-10/(N b), and shade_bwd multiplies by g.E, which
+            // carries the 2^-10: g_rad = -sign(lg) N^-1 ib (loss_grad_of_b).  sign(0) = 0 as in torch: equal operands
+            // select lg = 0 explicitly, and lg == 0 -- equal operands, or a quotient of unequal ones that rounds to
+            // exactly 1 -- gives magnitude 0 (a +0 there would otherwise always read as "input darker": a systematic
+            // sign at near-ties where the reference's rounded log difference gives 0).
             const float lg = (b[k] != bt[k]) ? log2_(bt[k] * ib[k]) : 0.0f;
             lsum += fabsf(lg);
-            const float mag = (lg != 0.0f) ? nc * ib[k] : 0.0f;
-            g_rad[k] = -__builtin_bit_cast(float, __builtin_bit_cast(unsigned, mag) | (__builtin_bit_cast(unsigned, lg) & 0x80000000u));
+            g_rad[k] = loss_grad_of_b(K, lg, inv_count * ib[k]);
         }
     }
-    if (WITH_GRAD) shade_bwd<NL, (DEFER & 1) != 0, (DEFER & 2) != 0>(K, g, mi, di, li, Fi, fi, g_rad, acc);
+    if (WITH_GRAD) shade_bwd<NL, (DEFER & 1) != 0, (DEFER & 2) != 0, (DEFER & 4) != 0>(K, g, mi, di, li, Fi, fi, g_rad, acc);
 }
 
 // The same for independent roughness channels (three lobes per map), one colour channel after the other: target lobe,
@@ -951,33 +993,35 @@ __device__ __forceinline__ void loss_pixel_scene_by_channel(const VConst &K, con
 {
     const Dots dt = dots(K, g, mt);
     const Dots di = dots(K, g, mi);
-    constexpr float c = 9.765625e-04f;               // 2^-10, as in loss_pixel_scene
-    const float ec = eps * c, nc = inv_count * c;
+    const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);   // radiances x 2^-10 as in loss_pixel_scene
     const float omp = 1.0f - g.p;
     float g_LNp = 0.0f, g_VN = 0.0f, g_LN = 0.0f, sN = 0.0f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const Lobe lt = lobe<false>(K, mt.A[k], mt.oA[k], dt);
+        const Lobe lt = lobe<false, false>(K, mt.A[k], mt.oA[k], dt);
         const float Ft = fma_(mt.oms[k], g.p, mt.s[k]);
         const float ft = fma_(Ft, lt.GD - mt.dpi[k], mt.dpi[k]);
-        const float rt = ft * (g.E[k] * dt.LNp);
-        const Lobe li = lobe<WITH_GRAD>(K, mi.A[k], mi.oA[k], di);
+        const float bt = fma_(ft, g.E[k] * dt.LNp, ec);
+        const Lobe li = lobe<WITH_GRAD, false>(K, mi.A[k], mi.oA[k], di);
         const float Fi = fma_(mi.oms[k], g.p, mi.s[k]);
         const float fi = fma_(Fi, li.GD - mi.dpi[k], mi.dpi[k]);
-        const float ri = fi * (g.E[k] * di.LNp);
-        const float b = fma_(ri, c, ec), bt = fma_(rt, c, ec);
+        const float b = fma_(fi, g.E[k] * di.LNp, ec);
         const float ib = rcp_(b);
         const float lg = (b != bt) ? log2_(bt * ib) : 0.0f;             // see loss_pixel_scene
         lsum += fabsf(lg);
         if (WITH_GRAD) {
-            const float mag = (lg != 0.0f) ? nc * ib : 0.0f;
-            const float g_rad = -__builtin_bit_cast(float, __builtin_bit_cast(unsigned, mag) | (__builtin_bit_cast(unsigned, lg) & 0x80000000u));
-            const float gE = g_rad * g.E[k];
+            const float gE = loss_grad_of_b(K, lg, inv_count * ib) * g.E[k];
             const float g_f = gE * di.LNp;
             g_LNp = fma_(gE, fi, g_LNp);
-            const float g_F = g_f * (li.GD - mi.dpi[k]);
-            acc.s[k] = fma_(g_F, omp, acc.s[k]);
-            acc.d[k] = (DEFER & 1) ? fma_(g_f, 1.0f - Fi, acc.d[k]) : fma_(g_f * (1.0f - Fi), K.inv_pi, acc.d[k]);
+            if (DEFER & 4) {                                            // see shade_bwd
+                const float gfo = g_f * omp;
+                acc.s[k] = fma_(gfo, li.GD - mi.dpi[k], acc.s[k]);
+                acc.d[k] += gfo;
+            } else {
+                const float g_F = g_f * (li.GD - mi.dpi[k]);
+                acc.s[k] = fma_(g_F, omp, acc.s[k]);
+                acc.d[k] = (DEFER & 1) ? fma_(g_f, 1.0f - Fi, acc.d[k]) : fma_(g_f * (1.0f - Fi), K.inv_pi, acc.d[k]);
+            }
             const float gGD = g_f * Fi;
             acc.r[k] = (DEFER & 2) ? fma_(gGD, li.KA, acc.r[k]) : fma_(gGD * li.KA, mi.r4m[k], acc.r[k]);
             g_VN = fma_(gGD, li.KV, g_VN);
@@ -1046,7 +1090,7 @@ __device__ __forceinline__ float loss_scene_loop(const MapK &mi, const MapK &mt_
 #endif
     if (WITH_GRAD) {
         load_scene(scp, sc);
-        Geom ga = geometry(K, sc, x, y), gb;                     // render 0
+        Geom ga = geometry<true>(K, sc, x, y), gb;               // render 0
         load_scene(scp + (S > 1 ? ST : 0), sc);                  // scalars of render 1
         // One pass = shade render s with geometry G_CUR while the geometry of render s+1 goes into G_NEXT.  The loop
         // body holds TWO passes with the roles of ga / gb swapped, so the pipelined geometry never has to be copied
@@ -1060,7 +1104,7 @@ __device__ __forceinline__ float loss_scene_loop(const MapK &mi, const MapK &mt_
             scp += ((SI) + 1 < S) ? ST : 0;                                                                        \
             __builtin_amdgcn_sched_barrier(0);                                                                     \
             /* two independent streams from here to the end of the pass: */                                        \
-            G_NEXT = geometry(K, cur, x, y);                     /* render s+1 (a harmless repeat on the last pass) */ \
+            G_NEXT = geometry<true>(K, cur, x, y);               /* render s+1 (a harmless repeat on the last pass) */ \
             loss_pixel_scene_any<NL, WITH_GRAD, DEFER>(K, G_CUR, mi, mt_in, eps, inv_count, lsum, acc);                   \
         }
         for (int s = 0;;) {
@@ -1072,11 +1116,11 @@ __device__ __forceinline__ float loss_scene_loop(const MapK &mi, const MapK &mt_
 #undef SVBRDF_K3_PASS
     } else {
         load_scene(sc_lds, sc);
-        Geom g_next = geometry(K, sc, x, y);
+        Geom g_next = geometry<true>(K, sc, x, y);
         for (int s = 0; s < S; ++s) {
             const Geom g = g_next;
             load_scene(sc_lds + (s + 1 < S ? s + 1 : s) * 9, sc);
-            g_next = geometry(K, sc, x, y);
+            g_next = geometry<true>(K, sc, x, y);
             loss_pixel_scene_any<NL, WITH_GRAD, DEFER>(K, g, mi, mt_in, eps, inv_count, lsum, acc);
         }
     }
@@ -1084,7 +1128,8 @@ __device__ __forceinline__ float loss_scene_loop(const MapK &mi, const MapK &mt_
     if (WITH_GRAD && DEFER) {               // the per-pixel constants shade_bwd left out (see its DEFER_D / DEFER_R)
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            if (DEFER & 1) acc.d[k] *= K.inv_pi;
+            if (DEFER & 4) acc.d[k] *= mi.oms[k] * K.inv_pi;
+            else if (DEFER & 1) acc.d[k] *= K.inv_pi;
             if (DEFER & 2) acc.r[k] *= mi.r4m[k];
         }
     }
@@ -1309,8 +1354,9 @@ __device__ __forceinline__ void rendering_loss_body(const float *__restrict__ in
         zero_grad(acc);
         float l1sum = 0.0f;
         // deferred per-pixel constants of the adjoint (shade_bwd): 1/pi of the diffuse gradient always (an L1 start value
-        // is multiplied by pi here), dA/dr_hat of the roughness gradient only where acc.r starts from zero (it can be 0)
-        constexpr int kDefer = WITH_GRAD ? (WITH_L1 ? 1 : 3) : 0;
+        // is multiplied by pi here), dA/dr_hat of the roughness gradient and 1 - specular of the diffuse gradient only where
+        // acc.r and acc.d start from zero (either can be 0); the last in the tied loop only (kept three-lobe loop: it spilled)
+        constexpr int kDefer = WITH_GRAD ? (WITH_L1 ? 1 : 7) : 0;
         if (WITH_L1) {
             // losses.py:7-19.  Same economy of transcendentals as in loss_pixel_scene: the six 1/(x + eps)
             // of the log terms' derivatives come from ONE v_rcp of their product (all six lie in
@@ -1378,7 +1424,7 @@ __device__ __forceinline__ void rendering_loss_body(const float *__restrict__ in
         if (__all(tied))     // wave-uniform: every lane's input AND target roughness channels are tied
             lsum = loss_scene_loop<1, WITH_GRAD, kDefer>(mi, mt, x[0], y, scp, sc_lds, S, eps, inv_count, acc);
         else
-            lsum = loss_scene_loop<3, WITH_GRAD, kDefer>(mi, mt, x[0], y, scp, sc_lds, S, eps, inv_count, acc);
+            lsum = loss_scene_loop<3, WITH_GRAD, kDefer & 3>(mi, mt, x[0], y, scp, sc_lds, S, eps, inv_count, acc);
         if (WITH_L1) lsum = fma_(l1sum, l1.sum_scale, lsum);
 #if SVBRDF_TIMING
         if (WITH_GRAD && !HEAD) {       // timing build: entry / exit stamps of the wave beside the loop's (loss_scene_loop)
