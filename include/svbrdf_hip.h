@@ -102,7 +102,8 @@ SVBRDF_API int svbrdf_render_bwd_ragged(const float *maps, const float *scenes, 
                                         void *stream);
 
 /* Bytes of device scratch svbrdf_rendering_loss_fwd_bwd needs for these dims (65 64-bit
- * words: sharded fixed-point loss accumulators with arrival counts, and a ticket).  The scratch must be
+ * words: sharded fixed-point loss accumulators with arrival counts, and a tail word that
+ * sums the completed ones).  The scratch must be
  * 8-byte aligned and ZERO-INITIALISED ONCE by the caller (hipMemset) before its first use;
  * every completed call leaves it zeroed again, so it can be reused call after call on
  * the same stream.  Do not share one scratch buffer between concurrently running calls. */

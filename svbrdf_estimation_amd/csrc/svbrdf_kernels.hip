@@ -911,11 +911,13 @@ __global__ __launch_bounds__(kThreads) void k_render_bwd_inl([[maybe_unused]] co
 //   fixed-point integer to one of kLossSlots 64-bit accumulators (integer addition is
 //   associative, so the result is bitwise reproducible whatever the arrival order).  Each
 //   accumulator word also counts its arrivals in its top 16 bits, so ONE returning atomic
-//   per workgroup both adds and tells the workgroup whether it completed its slot; slot
-//   completers draw a global ticket (<= kLossSlots atomics in all) and the last of them sums
-//   the slots, writes the mean and re-zeroes the scratch.  (A single shared accumulator +
-//   ticket serialises 2 atomics per workgroup on one address and cost ~45 us at 2048
-//   workgroups -- measured; profiles/r01_k3_sweep.txt.)
+//   per workgroup both adds and tells the workgroup whether it completed its slot; a slot's
+//   completer knows the slot's sum from that return, re-zeroes the slot and adds the sum to
+//   a tail word that counts completed slots the same way (<= kLossSlots atomics in all); the
+//   completer of the last slot knows the total from ITS return, writes the mean and re-zeroes
+//   the tail word: two dependent round trips end a launch, nothing is read back (loss_arrive).
+//   (A single shared accumulator + ticket serialises 2 atomics per workgroup on one address
+//   and cost ~45 us at 2048 workgroups -- measured; profiles/r01_k3_sweep.txt.)
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_sum(float v)
 {
@@ -927,8 +929,11 @@ __device__ __forceinline__ float wave_sum(float v)
 constexpr int kLossSlots = 64;                    // sharded accumulators (power of two)
 constexpr int kLossCountShift = 48;               // word = arrivals << 48 | fixed-point sum
 constexpr unsigned long long kLossSumMask = (1ULL << kLossCountShift) - 1;
-constexpr unsigned long long kLossTicketMask = 0xffffffffULL;   // ws[kLossSlots]: low half counts slot completions,
-constexpr unsigned long long kLossNonFiniteFlag = 1ULL << 32;   // bit 32 = some workgroup's partial sum was not finite
+// the tail word ws[kLossSlots] = non-finite flag << 63 | completed slots << 56 | sum of the completed slots
+constexpr int kLossDoneShift = 56;
+constexpr unsigned kLossDoneMask = 0x7f;                         // <= kLossSlots completed slots
+constexpr unsigned long long kLossTotalMask = (1ULL << kLossDoneShift) - 1;
+constexpr unsigned long long kLossNonFiniteFlag = 1ULL << 63;    // sticky: some workgroup's partial sum was not finite
 
 // one (pixel, scene) of the fused loss: both shadings, log/L1, adjoint of the input shading
 template <int NL, bool WITH_GRAD, int DEFER = 0>
@@ -1201,10 +1206,20 @@ __device__ __forceinline__ void head_bwd(const Head &h, const Grad &g, float ge[
     ge[5] = 0.5f * ((g.r[0] + g.r[1]) + g.r[2]);
 }
 
-// Loss reduction, workgroup level: one lane adds its workgroup's partial sum `t` (fixed point) to the workgroup's slot
-// with ONE returning atomic that also counts the slot's arrivals; returns true for the workgroup that completed the
-// last slot of the launch (the finisher).
-__device__ __forceinline__ bool loss_arrive(float t, float fixed_scale, unsigned long long *__restrict__ ws)
+// Loss reduction, workgroup level, called by ONE lane per workgroup with the workgroup's partial sum `t`.  Two levels, both
+// finished by the returning atomic itself -- nothing is read back, nobody waits for anybody:
+//   1. `t` (fixed point) goes to the workgroup's slot with one returning atomic that also counts the slot's arrivals.  The
+//      workgroup whose add returns the last-but-one count completed the slot and knows its full sum: old sum + own term.
+//   2. The completer re-zeroes its slot (nobody arrives there after it; a store, not awaited) and adds
+//      (1 << kLossDoneShift) | slot sum to the tail word with a second returning atomic.  The completer whose add returns
+//      nslots - 1 completed slots is the finisher and knows the launch's total: old total + own slot sum.  It writes the
+//      mean and re-zeroes the tail word.
+// The chain that ends a launch is therefore two dependent memory-side round trips and two stores issued behind them
+// (until round 8: four round trips -- arrival, ticket, fetch-and-clear of the slots, fetch-and-clear of the ticket word --
+// a fence and a second workgroup barrier; profiles/HISTORY.md part A000, r08_k3_ab.txt).  The integer that is converted to the
+// loss is the same sum of the same fixed-point terms whatever the arrival order: bitwise reproducible.
+__device__ __forceinline__ void loss_arrive(float t, float fixed_scale, double loss_scale, unsigned long long *__restrict__ ws,
+                                            float *__restrict__ loss_out)
 {
     const unsigned nblocks = gridDim.x * gridDim.y, bid = blockIdx.y * gridDim.x + blockIdx.x;
     const unsigned slot = bid & (kLossSlots - 1);
@@ -1212,7 +1227,7 @@ __device__ __forceinline__ bool loss_arrive(float t, float fixed_scale, unsigned
     // The scale keeps every legitimate partial sum below 2^47 (loss_impl).  A partial sum that is NaN, infinite
     // or beyond that (NaN/inf maps, or radiances no renderer input can produce) must neither be cast (undefined
     // for NaN/inf) nor reach the arrival count in the word's top bits: it contributes 0 and raises the sticky
-    // non-finite flag next to the ticket counter instead, and the finisher reports NaN -- as the reference's
+    // non-finite flag in the tail word instead, and the finisher reports NaN -- as the reference's
     // log/L1 chain would (isfinite(loss) guards keep working) -- and leaves the scratch zeroed as always.
     // The bound is per workgroup: the slot_blocks partial sums of one slot must not carry into the arrival count
     // together either, so each stays below 2^47 / slot_blocks -- still above every legitimate value (the host picks
@@ -1224,33 +1239,25 @@ __device__ __forceinline__ bool loss_arrive(float t, float fixed_scale, unsigned
     const unsigned long long fixed = finite ? (unsigned long long)scaled : 0ULL;
     if (!finite) {
         atomicOr(&ws[kLossSlots], kLossNonFiniteFlag);
-        __threadfence();        // the flag is visible device-wide before this workgroup's arrival is
-    }
+        __threadfence();        // the flag is in the tail word before this workgroup's arrival is counted, hence before the
+    }                           // slot's completer adds to that word: every later add there returns it
     // device-scope returning atomic, performed at the memory side: add + arrival count in one
     const unsigned long long old = atomicAdd(&ws[slot], (1ULL << kLossCountShift) | fixed);
-    if ((unsigned)(old >> kLossCountShift) + 1 == slot_blocks) {
-        const unsigned nslots = nblocks < (unsigned)kLossSlots ? nblocks : (unsigned)kLossSlots;
-        const unsigned long long ticket = atomicAdd(&ws[kLossSlots], 1ULL);
-        if ((unsigned)(ticket & kLossTicketMask) + 1 == nslots) return true;
-    }
-    return false;
-}
-
-// the finisher's first wave (`lane` = 0..63): every slot is complete (its completer drew its ticket after its add had
-// returned): fetch-and-clear all slots in parallel, integer wave reduction, write the mean
-__device__ __forceinline__ void loss_finish(unsigned lane, unsigned long long *__restrict__ ws, float *__restrict__ loss_out,
-                                            double loss_scale)
-{
-    const unsigned nblocks = gridDim.x * gridDim.y;
-    unsigned long long v = 0;
-    if (lane < (unsigned)kLossSlots && lane < nblocks) v = atomicExch(&ws[lane], 0ULL) & kLossSumMask;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == 0) {
-        __threadfence();
-        const unsigned long long tail = atomicExch(&ws[kLossSlots], 0ULL);
-        loss_out[0] = (tail & kLossNonFiniteFlag) ? __builtin_nanf("") : (float)((double)v * loss_scale);
-    }
+    if ((unsigned)(old >> kLossCountShift) + 1 != slot_blocks) return;
+    const unsigned nslots = nblocks < (unsigned)kLossSlots ? nblocks : (unsigned)kLossSlots;
+    const unsigned long long sum = (old & kLossSumMask) + fixed;       // < 2^47: 64 of them stay below 2^53
+    // One lane is active, but the address is uniform and the value is not known to be: the compiler's atomic optimiser would
+    // wrap the add in a lane-scan loop (a third loop in the kernel, tests/test_isa_guard.py).  Made wave-uniform by hand.
+    // (the builtin returns int: through unsigned, or the low half's bit 31 is sign-extended over the high half)
+    const unsigned sum_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(sum >> 32));
+    const unsigned sum_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sum);
+    const unsigned long long slot_sum = ((unsigned long long)sum_hi << 32) | sum_lo;
+    const unsigned long long tail = atomicAdd(&ws[kLossSlots], (1ULL << kLossDoneShift) | slot_sum);
+    __hip_atomic_store(&ws[slot], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // behind the add: off the chain's wait
+    if ((unsigned)((tail >> kLossDoneShift) & kLossDoneMask) + 1 != nslots) return;
+    const unsigned long long total = (tail & kLossTotalMask) + slot_sum;
+    loss_out[0] = (tail & kLossNonFiniteFlag) ? __builtin_nanf("") : (float)((double)total * loss_scale);
+    __hip_atomic_store(&ws[kLossSlots], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // the gradient planes of one pixel: 12 channels, or the 9 of the encoded head output (chain rule through decode_head)
@@ -1440,18 +1447,21 @@ __device__ __forceinline__ void rendering_loss_body(const float *__restrict__ in
     }
     {
         __shared__ float wave_part[kLossThreads / 64];
-        __shared__ int finisher;
         lsum = wave_sum(lsum);
         if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = lsum;
         __syncthreads();
-        if (threadIdx.x == 0) {
+        if (threadIdx.x == 0) {     // the other waves retire here
             float t = 0.0f;
 #pragma unroll
             for (int w = 0; w < kLossThreads / 64; ++w) t += wave_part[w];
-            finisher = loss_arrive(t, fixed_scale, ws) ? 1 : 0;
+            loss_arrive(t, fixed_scale, loss_scale, ws, loss_out);
+#if SVBRDF_TIMING
+            if (WITH_GRAD && !HEAD && active) {     // timing build: end of the workgroup's reduction chain (its stores acknowledged)
+                __builtin_amdgcn_s_waitcnt(0x0f70);     // vmcnt(0): its stores are acknowledged
+                grad_input[((size_t)b * 12 + 6) * plane + pix] = (float)(wall_clock64() & 0xffffff);
+            }
+#endif
         }
-        __syncthreads();
-        if (finisher && threadIdx.x < 64) loss_finish(threadIdx.x, ws, loss_out, loss_scale);
     }
 }
 
@@ -1974,7 +1984,7 @@ int svbrdf_render_bwd_ragged(const float *maps, const float *scenes, const int *
 size_t svbrdf_rendering_loss_workspace_bytes(int B, int S, int H, int W)
 {
     if (B <= 0 || S <= 0 || H <= 0 || W <= 0) return 0;
-    return (kLossSlots + 1) * sizeof(unsigned long long);   // sharded fixed-point accumulators + ticket
+    return (kLossSlots + 1) * sizeof(unsigned long long);   // sharded fixed-point accumulators + tail word
 }
 
 static int loss_impl(const char *who, bool head, bool scenes_on_host, const float *input, const float *target,

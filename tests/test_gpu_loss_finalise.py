@@ -1,0 +1,155 @@
+"""The end of a fused-loss launch (svbrdf_kernels.hip, loss_arrive): every workgroup adds its fixed-point partial sum to one of
+64 slot words with a returning atomic that also counts arrivals; the completer of a slot re-zeroes it and adds the slot's sum
+to the tail word, which counts completed slots the same way; the completer of the last slot writes the loss and re-zeroes the
+tail word.  Nothing is read back, so every grid shape has to come out right from the two returns alone:
+
+  * one workgroup (one slot, its completer is the finisher at once), 63 / 64 / 65 workgroups (fewer slots than 64, exactly one
+    workgroup per slot, one slot with two arrivals), a grid whose last workgroup is partly empty, config 2 (2,048 workgroups,
+    scene table in the kernel arguments) and B = 65,535 (1,024 arrivals per slot, device table);
+  * the scratch is all zero after every call, a call with a NaN map included;
+  * two identical calls give bitwise equal loss and gradient (integer addition: the arrival order cannot matter);
+  * the clean call after a non-finite one equals the clean reference bitwise (the sticky flag left with the tail word);
+  * the same for the forward-only kernels (want_grad=False: another translation unit, same epilogue) and for MixedLoss;
+  * the loss of the small grids against the C oracle: a finisher that dropped a slot or fired early would be off by 1/64 or more.
+"""
+import numpy as np
+import pytest
+import torch
+
+import synth
+from tolerances import LOSS_RTOL, assert_loss_close
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need an MI355X (select CPU tests with -m 'not gpu')"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def native():
+    from svbrdf_estimation_amd import _native
+    _native._load()
+    return _native
+
+
+def _t(a, dev):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+
+
+def _np(t):
+    return t.detach().cpu().numpy()
+
+
+def _scratch_is_zero(native):
+    torch.cuda.synchronize()
+    assert native._workspace_cache, "no call has allocated the scratch yet"
+    for ws in native._workspace_cache.values():
+        assert ws.numel() * 8 >= 65 * 8
+        assert not ws.any().item(), "scratch left dirty: %s" % (ws.cpu().numpy()[:65],)
+
+
+def _table(B, n_random, n_specular, seed, on_device, dev):
+    from svbrdf_estimation_amd import environment
+    torch.manual_seed(seed)
+    if B > 1024:     # one scene per item: one row repeated with a small per-item offset (as tests/test_gpu_parity.py does)
+        one = environment.scene_table(1, 2).numpy()[:n_random + n_specular]
+        t = np.tile(one[None], (B, 1, 1)) + (np.arange(B, dtype=np.float32) % 7)[:, None, None] * np.float32(0.01)
+        t = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32))
+    else:
+        t = torch.stack([environment.scene_table(n_random, n_specular) for _ in range(B)]).contiguous()
+    return t.to(dev) if on_device else t
+
+
+# name: (B, H, random scenes, specular scenes, scene table on the device, workgroups)
+GRIDS = {
+    "one_workgroup": (1, 16, 1, 2, False, 1),
+    "63_workgroups": (63, 16, 1, 2, False, 63),
+    "64_workgroups": (64, 16, 1, 2, False, 64),
+    "65_workgroups": (65, 16, 1, 2, True, 65),
+    "ragged_last_workgroup": (3, 20, 1, 2, True, 6),         # 400 pixels per item: the second workgroup holds 144
+    "config_2": (8, 256, 3, 6, False, 2048),
+    "B_65535": (65535, 2, 0, 1, True, 65535),
+}
+
+
+def _case(name, dev):
+    B, H, nr, ns, on_device, groups = GRIDS[name]
+    assert ((H * H + 255) // 256) * B == groups
+    seed = 8100 + 2 * sorted(GRIDS).index(name)
+    inp, tgt = synth.make_maps(seed, B, H), synth.make_maps(seed + 1, B, H)
+    return inp, tgt, _table(B, nr, ns, seed, on_device, dev)
+
+
+def _with_nan(maps):
+    bad = maps.copy()
+    bad[-1, 4, -1, -1] = np.nan          # a diffuse value of the last pixel: its workgroup raises the flag
+    return bad
+
+
+@pytest.mark.parametrize("name", sorted(GRIDS))
+def test_loss_and_scratch_for_every_grid_shape(dev, native, oracle, name):
+    inp, tgt, table = _case(name, dev)
+    d_in, d_tg = _t(inp, dev), _t(tgt, dev)
+    l0, g0 = native.rendering_loss(d_in, d_tg, table)
+    _scratch_is_zero(native)
+    l0, g0 = l0.item(), _np(g0)
+    assert np.isfinite(l0) and l0 > 0.0 and np.isfinite(g0).all()
+    if GRIDS[name][5] <= 65:
+        ref_l, _ = oracle.rendering_loss(inp, tgt, _np(table))
+        print("[loss-finalise] %s: loss %.9g, oracle %.9g" % (name, l0, ref_l))
+        assert_loss_close(l0, ref_l, name)
+    # a second identical call: bitwise
+    l1, g1 = native.rendering_loss(d_in, d_tg, table)
+    _scratch_is_zero(native)
+    assert l1.item() == l0 and np.array_equal(_np(g1), g0)
+    # a NaN map: NaN loss, clean scratch, and nothing sticks
+    for want_grad in (True, False):
+        ln, _ = native.rendering_loss(d_in, _t(_with_nan(tgt), dev), table, want_grad=want_grad)
+        assert np.isnan(ln.item())
+        _scratch_is_zero(native)
+    l2, g2 = native.rendering_loss(d_in, d_tg, table)
+    _scratch_is_zero(native)
+    assert l2.item() == l0 and np.array_equal(_np(g2), g0)
+
+
+@pytest.mark.parametrize("name", ["one_workgroup", "65_workgroups", "config_2"])
+def test_forward_only_call(dev, native, name):
+    inp, tgt, table = _case(name, dev)
+    d_in, d_tg = _t(inp, dev), _t(tgt, dev)
+    with_grad = native.rendering_loss(d_in, d_tg, table)[0].item()
+    vals = []
+    for _ in range(2):
+        l, g = native.rendering_loss(d_in, d_tg, table, want_grad=False)
+        assert g is None
+        _scratch_is_zero(native)
+        vals.append(l.item())
+    assert vals[0] == vals[1] and np.isfinite(vals[0])
+    # two kernels, each within LOSS_RTOL of the oracle (tests/test_gpu_parity.py): within twice that of each other
+    assert_loss_close(vals[0], with_grad, name + " forward-only against forward+adjoint", rtol=2 * LOSS_RTOL)
+    ln, _ = native.rendering_loss(_t(_with_nan(inp), dev), d_tg, table, want_grad=False)
+    assert np.isnan(ln.item())
+    _scratch_is_zero(native)
+    assert native.rendering_loss(d_in, d_tg, table, want_grad=False)[0].item() == vals[0]
+    _scratch_is_zero(native)
+
+
+@pytest.mark.parametrize("name", ["65_workgroups", "config_2"])
+def test_mixed_loss_call(dev, native, name):
+    inp, tgt, table = _case(name, dev)
+    d_in, d_tg = _t(inp, dev), _t(tgt, dev)
+    l0, g0 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1)
+    _scratch_is_zero(native)
+    l0, g0 = l0.item(), _np(g0)
+    assert np.isfinite(l0) and np.isfinite(g0).all()
+    assert l0 > native.rendering_loss(d_in, d_tg, table)[0].item()       # the L1 part is in the sum
+    l1, g1 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1)
+    assert l1.item() == l0 and np.array_equal(_np(g1), g0)
+    ln, _ = native.rendering_loss(d_in, _t(_with_nan(tgt), dev), table, l1_weight=0.1)
+    assert np.isnan(ln.item())
+    _scratch_is_zero(native)
+    l2, g2 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1)
+    _scratch_is_zero(native)
+    assert l2.item() == l0 and np.array_equal(_np(g2), g0)

@@ -1,7 +1,10 @@
 """Occupancy over time of one K3 launch (config 2) from per-wave stamps of a -DSVBRDF_TIMING=1 build
 (SVBRDF_HIP_LIB=<that build>: `bash tools/build_variant.sh tim -DSVBRDF_TIMING=1`; the scene-split layouts this tool also
 read in round 4 left the source in round 5).  Prints waves resident / inside the
-scene loop per SIMD in 24 time bins, and where the first and last microseconds of the launch go."""
+scene loop per SIMD in 24 time bins, where the first and last microseconds of the launch go, and how long the reduction
+chain that ends the launch takes: thread 0 of every workgroup stamps the chip-wide 100 MHz counter once its last atomic has
+returned and its stores are acknowledged (the finisher: after the loss store); the latest of these stamps against the latest
+scene-loop exit is what the launch spends on gradient stores, barrier and atomics after its last render."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("SVBRDF_NO_HOST_EXT", "1")
@@ -56,6 +59,19 @@ if entry is not None:
     print("entry -> loop start (plane loads, prepare, first geometry): median %.2f us, first round %.2f us, second round %.2f us" % (
         np.median(start - entry) * TICK, np.median((start - entry)[np.argsort(entry)[:4096]]) * TICK,
         np.median((start - entry)[np.argsort(entry)[4096:]]) * TICK if len(entry) > 4096 else float("nan")))
+if G == 1:
+    done = g[:, 6].flatten().cpu().numpy()[::256]                       # thread 0 of every workgroup (256 pixels each)
+    if (done == np.floor(done)).all() and (done >= 0).all() and (done < M).all() and done.max() > 0:
+        done = (done.astype(np.int64) - t0) % M
+        last = int(np.argmax(done))
+        print("end of the launch: last scene-loop end %.2f us, last wave exit stamp %.2f us, last workgroup done (atomics returned, "
+              "stores acknowledged) %.2f us: chain after the last loop end %.2f us (the last workgroup's own: %.2f us after "
+              "its latest wave's loop end)" % (end.max() * TICK, exit_.max() * TICK, done.max() * TICK, (done.max() - end.max()) * TICK,
+                                               (done[last] - end[4 * last:4 * last + 4].max()) * TICK))
+        print("workgroup done stamp minus its latest wave's loop end: median %.2f us, 90 %% %.2f us, max %.2f us" % tuple(
+            np.percentile(done - end.reshape(-1, 4).max(axis=1), (50, 90, 100)) * TICK))
+    else:
+        print("end of the launch: plane 6 holds no done stamps (a timing build from before the stamp existed)")
 edges = np.linspace(0, T, 25)
 for a, b in zip(edges[:-1], edges[1:]):
     mid = 0.5 * (a + b)
