@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SVBRDF_ABI_VERSION 7
+#define SVBRDF_ABI_VERSION 8
 
 #if defined(__GNUC__)
 #define SVBRDF_API __attribute__((visibility("default")))
@@ -176,6 +176,31 @@ SVBRDF_API int svbrdf_head_loss_fwd_bwd_host_scenes(const float *encoded9, const
                                                     float *loss_out, float *grad_encoded9, void *workspace,
                                                     size_t workspace_bytes, int B, int S, int H, int W,
                                                     void *stream);
+
+/* Fused PHOTO loss (ABI version 8) -- the rendering loss against given photographs instead of against the renderings of
+ * target maps, and its backward, in ONE launch:
+ *   loss_out[0] = mean_{b,s,c,i,j} | log(render(scene[b,s], input[b]) + eps) - log(photos[b,s] + eps) |
+ *   grad_input  = d loss / d input  (for upstream gradient 1.0), or NULL for forward-only (same loss, bit for bit).
+ * What fitting maps to captured or synthesised photos, or self-supervised training on the input photos, needs when no
+ * ground-truth maps exist: `photos` [B,S,3,H,W] are the photographs and `scenes` [B,S,9] the light / view each was taken
+ * under (e.g. svbrdf_render_inputs' output and table).  The kernel reads the 12 input planes and the 3 S photo planes of a
+ * pixel once and writes the 12 gradient planes once -- (12 + 3 S + 12) * 4 bytes per pixel -- and shades each pixel-render
+ * once, where K3 shades twice.  Conventions as svbrdf_rendering_loss_fwd_bwd: PyTorch's sub-gradients (sign(0) = 0,
+ * inclusive clamp masks; a term whose two sides are equal is exactly 0 with gradient 0); a NaN or infinite value anywhere
+ * in `input` or `photos`, or a photo value at or below -eps (where torch.log gives NaN or -inf), gives loss_out[0] = NaN
+ * with the scratch still left zeroed; bitwise run-to-run reproducible; error codes, 4-byte alignment rule (every aligned
+ * pointer takes the same one-pixel-per-lane path: same results), eps in [1e-9, 1e9], and the scratch of
+ * svbrdf_rendering_loss_workspace_bytes() with its zero-once / left-zeroed contract.  No gradient w.r.t. photos or scenes.
+ * `_host_scenes`: the B*S rows in HOST memory travel by value in the launch's argument block
+ * (B*S <= SVBRDF_HOST_SCENES_MAX_ROWS, SVBRDF_ERR_DIMS beyond); bitwise the results of the device-table entry. */
+SVBRDF_API int svbrdf_photo_loss_fwd_bwd(const float *input, const float *photos, const float *scenes,
+                                         const float *xrow, float eps, float *loss_out, float *grad_input,
+                                         void *workspace, size_t workspace_bytes, int B, int S, int H, int W,
+                                         void *stream);
+SVBRDF_API int svbrdf_photo_loss_fwd_bwd_host_scenes(const float *input, const float *photos, const float *scenes_host,
+                                                     const float *xrow, float eps, float *loss_out, float *grad_input,
+                                                     void *workspace, size_t workspace_bytes, int B, int S, int H,
+                                                     int W, void *stream);
 
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd

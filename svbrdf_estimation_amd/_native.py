@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # SVBRDF_HIP_LIB: load another build of the same ABI (ablation/experiment builds of tools/); default in-tree
 _SO = os.environ.get("SVBRDF_HIP_LIB") or os.path.join(_HERE, "lib", "libsvbrdf_hip.so")
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _lock = threading.Lock()
 _lib = None
@@ -79,6 +79,9 @@ def _load():
             getattr(lib, name).argtypes = lib.svbrdf_mixed_loss_fwd_bwd.argtypes
             getattr(lib, name).restype = ctypes.c_int
         lib.svbrdf_host_scenes_max_rows.restype = ctypes.c_int
+        for name in ("svbrdf_photo_loss_fwd_bwd", "svbrdf_photo_loss_fwd_bwd_host_scenes"):
+            getattr(lib, name).argtypes = lib.svbrdf_rendering_loss_fwd_bwd.argtypes
+            getattr(lib, name).restype = ctypes.c_int
         lib.svbrdf_scale_inplace.argtypes = [_fp, _fp, ctypes.c_size_t, _fp]
         lib.svbrdf_scale_inplace.restype = ctypes.c_int
         lib.svbrdf_render_fwd_host_scenes.argtypes = [_fp, _fp, ctypes.c_int, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
@@ -521,6 +524,50 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
         # a failed launch may leave partial sums / arrival counts behind: the scratch contract ("every completed
         # call leaves it zeroed") only covers completed calls, so restore it before reporting the error
         ws.zero_()
+    _check(rc, entry)
+    return loss, grad
+
+
+def photo_loss(input, photos, scenes, eps=0.1, want_grad=True):
+    """Fused photo loss (svbrdf_photo_loss_fwd_bwd*): mean |log(render(scenes[b,s], input[b]) + eps) - log(photos[b,s] + eps)|
+    and d loss/d input in ONE launch.  input [B,12,H,W] and photos [B,S,3,H,W] device fp32; scenes [B,S,9] fp32 on the
+    maps' device, or on the HOST (at most host_scenes_max_rows() rows ride in the launch's argument block, a larger table
+    is uploaded).  Returns (loss [1] device tensor, grad or None)."""
+    _require_device_f32(input, "input")
+    _require_device_f32(photos, "photos")
+    host_scenes = isinstance(scenes, torch.Tensor) and not scenes.is_cuda
+    if host_scenes:
+        if scenes.dtype != torch.float32:
+            raise TypeError("scenes must be float32 (got %s)" % scenes.dtype)
+        if scenes.dim() == 3 and scenes.shape[0] * scenes.shape[1] > host_scenes_max_rows():
+            scenes, host_scenes = upload_scene_table(scenes, input.device), False
+    else:
+        _require_device_f32(scenes, "scenes")
+    if photos.device != input.device or (not host_scenes and scenes.device != input.device):
+        raise ValueError("input, photos and scenes must be on the same device")
+    input, photos, scenes = input.contiguous(), photos.contiguous(), scenes.contiguous()
+    B, S, H, W, shared = _dims(input, scenes)
+    if shared:
+        raise ValueError("the loss needs one scene row per photo: scenes must be [B,S,9]")
+    if tuple(photos.shape) != (B, S, 3, H, W):
+        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
+                         % ((B, S, 3, H, W), tuple(photos.shape)))
+    lib = _load()
+    ws = _workspace(input.device, lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
+    loss = torch.empty(1, dtype=torch.float32, device=input.device)
+    grad = torch.empty_like(input) if want_grad else None
+    entry = "svbrdf_photo_loss_fwd_bwd_host_scenes" if host_scenes else "svbrdf_photo_loss_fwd_bwd"
+    hook = _launch_hook
+    with _on_device(input.device):
+        if hook is not None:
+            hook("begin")
+        rc = getattr(lib, entry)(input.data_ptr(), photos.data_ptr(), scenes.data_ptr(), xrow(input.device, W).data_ptr(),
+                                 ctypes.c_float(eps), loss.data_ptr(), grad.data_ptr() if want_grad else None,
+                                 ws.data_ptr(), ws.numel() * 8, B, S, H, W, _stream(input.device))
+        if hook is not None:
+            hook("end")
+    if rc != 0:
+        ws.zero_()      # see rendering_loss
     _check(rc, entry)
     return loss, grad
 

@@ -1,0 +1,400 @@
+// svbrdf_photo_loss.hip -- translation unit of libsvbrdf_hip.so: the fused PHOTO loss (ABI version 8).
+//
+//   L = mean_{b,s,c,i,j} | log(render(scene[b,s], input[b]) + eps) - log(photo[b,s] + eps) |
+//
+// K3 (svbrdf_kernels.hip) compares the renderings of two sets of maps; this kernel compares the renderings of ONE set
+// of maps with given photographs -- the inverse-rendering use of the engine, where ground-truth maps do not exist.  Per
+// pixel it loads the 12 input planes once, loops the S scenes in registers, shades the input with K3's own primitives
+// (dots / lobe / shade_loss / shade_bwd: tied-roughness fast path and three-lobe path), takes the target side of every
+// term from three loads instead of a second shading, accumulates the analytic gradient in registers, stores the 12
+// gradient planes once and reduces the loss through K3's fixed-point finalise (loss_arrive: same 65-word scratch, left
+// zeroed for the next call).  HBM traffic (12 + 3 S + 12) * 4 bytes per pixel, one launch.
+//
+// The shared inline device code and the host-side argument checks come from svbrdf_kernels.hip, included with
+// SVBRDF_TU = 4 as svbrdf_aux_f64.hip does: none of its kernels, none of its entry points.  A unit of its own so that K3's
+// machine code cannot move (tests/test_counter_replay_guard.py hashes it) and so that this kernel takes its own scheduler
+// option set (csrc/Makefile: SCHED_PHOTO).  Numerics contract as K3: -ffp-contract=off, the coords -> NH path exact.
+#define SVBRDF_TU 4
+#include "svbrdf_kernels.hip"
+
+namespace {
+
+// (photo + eps) 2^-10 of one term in ONE instruction: fma(photo, 2^-10, eps 2^-10) rounds (photo + eps) 2^-10 once, and a
+// power-of-two scale commutes with the rounding: bitwise ldexp(fl(photo + eps), -10), the reference's fp32 photo + eps
+// in the loss kernels' units (kLossScaleExp).  A photo value of exactly 0 gives eps 2^-10 exactly -- what shade_loss
+// gives for a pixel the light does not reach (LN+ = 0), so such a term is exactly 0 with gradient 0.  A value below -eps
+// gives a negative operand and the log of a negative quotient: NaN, as torch.log does.
+__device__ __forceinline__ void photo_terms(const float ph[3], float s10, float ec, float bt[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) bt[k] = fma_(ph[k], s10, ec);
+}
+
+// one (pixel, scene), tied roughness: loss_pixel_scene with the target shading replaced by the photo's three values
+template <bool WITH_GRAD, int DEFER>
+__device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
+                                                  float s10, float eps, float inv_count, float &lsum, Grad &acc)
+{
+    const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
+    float bt[3];
+    photo_terms(ph, s10, ec, bt);
+    const Dots di = dots(K, g, mi);
+    Lobe li[1];
+    float Fi[3], fi[3], b[3], g_rad[3];
+    shade_loss<1, WITH_GRAD>(K, g, mi, di, li, Fi, fi, ec, b);
+    // K3's economy of transcendentals (loss_pixel_scene): the three 1/b from ONE v_rcp of their product, one log of the
+    // quotient per channel, equal operands select exactly 0 (sign(0) = 0)
+    float ib[3];
+    {
+        const float P = b[0] * b[1];
+        const float r = rcp_(P * b[2]);
+        const float t = r * b[2];
+        ib[0] = t * b[1]; ib[1] = t * b[0]; ib[2] = r * P;
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float lg = (b[k] != bt[k]) ? log2_(bt[k] * ib[k]) : 0.0f;
+        lsum += fabsf(lg);
+        g_rad[k] = loss_grad_of_b(K, lg, inv_count * ib[k]);
+    }
+    if (WITH_GRAD) shade_bwd<1, (DEFER & 1) != 0, (DEFER & 2) != 0, (DEFER & 4) != 0>(K, g, mi, di, li, Fi, fi, g_rad, acc);
+}
+
+// independent roughness channels: loss_pixel_scene_by_channel with the photo as the target side
+template <bool WITH_GRAD, int DEFER>
+__device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
+                                                             float s10, float eps, float inv_count, float &lsum, Grad &acc)
+{
+    const Dots di = dots(K, g, mi);
+    const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
+    const float omp = 1.0f - g.p;
+    float g_LNp = 0.0f, g_VN = 0.0f, g_LN = 0.0f, sN = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float bt = fma_(ph[k], s10, ec);
+        const Lobe li = lobe<WITH_GRAD, false>(K, mi.A[k], mi.oA[k], di);
+        const float Fi = fma_(mi.oms[k], g.p, mi.s[k]);
+        const float fi = fma_(Fi, li.GD - mi.dpi[k], mi.dpi[k]);
+        const float b = fma_(fi, g.E[k] * di.LNp, ec);
+        const float ib = rcp_(b);
+        const float lg = (b != bt) ? log2_(bt * ib) : 0.0f;
+        lsum += fabsf(lg);
+        if (WITH_GRAD) {
+            const float gE = loss_grad_of_b(K, lg, inv_count * ib) * g.E[k];
+            const float g_f = gE * di.LNp;
+            g_LNp = fma_(gE, fi, g_LNp);
+            const float g_F = g_f * (li.GD - mi.dpi[k]);
+            acc.s[k] = fma_(g_F, omp, acc.s[k]);
+            acc.d[k] = (DEFER & 1) ? fma_(g_f, 1.0f - Fi, acc.d[k]) : fma_(g_f * (1.0f - Fi), K.inv_pi, acc.d[k]);
+            const float gGD = g_f * Fi;
+            acc.r[k] = (DEFER & 2) ? fma_(gGD, li.KA, acc.r[k]) : fma_(gGD * li.KA, mi.r4m[k], acc.r[k]);
+            g_VN = fma_(gGD, li.KV, g_VN);
+            g_LN = fma_(gGD, li.KL, g_LN);
+            sN = fma_(gGD, li.KN, sN);
+        }
+    }
+    if (WITH_GRAD) {
+        float g_NH = (sN * 2.0f) * di.NH;
+        if (!(di.nh_raw >= K.tiny)) g_NH = 0.0f;
+        if (!(di.vn_raw >= K.tiny)) g_VN = 0.0f;
+        if (!(di.ln_raw >= K.tiny)) g_LN = 0.0f;
+        if (!(di.ln_raw >= 0.0f)) g_LNp = 0.0f;
+        const float gl = g_LN + g_LNp;
+        acc.n[0] = fma_(g_NH, g.hx, fma_(g_VN, g.wox, fma_(gl, g.wix, acc.n[0])));
+        acc.n[1] = fma_(g_NH, g.hy, fma_(g_VN, g.woy, fma_(gl, g.wiy, acc.n[1])));
+        acc.n[2] = fma_(g_NH, g.hz, fma_(g_VN, g.woz, fma_(gl, g.wiz, acc.n[2])));
+    }
+}
+
+template <int NL, bool WITH_GRAD, int DEFER>
+__device__ __forceinline__ void photo_pixel_scene_any(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
+                                                      float s10, float eps, float inv_count, float &lsum, Grad &acc)
+{
+    if (NL == 3)
+        photo_pixel_scene_by_channel<WITH_GRAD, DEFER & 3>(K, g, mi, ph, s10, eps, inv_count, lsum, acc);
+    else
+        photo_pixel_scene<WITH_GRAD, DEFER>(K, g, mi, ph, s10, eps, inv_count, lsum, acc);
+}
+
+// the three photo values of one (pixel, render): planes 3 s .. 3 s + 2 of the item's [S,3,H,W] photos.  One buffer resource
+// per render (base and size are wave-uniform: scalar arithmetic), so any S fits the 32-bit byte offsets.
+__device__ __forceinline__ void load_photo(const float *__restrict__ render_base, size_t plane, size_t pix, float ph[3])
+{
+    const PlaneBuf pb = plane_buf(render_base, 3, plane, pix);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ph[k] = plane_load(pb, k);
+}
+
+// Scene loop, software-pipelined like K3's (loss_scene_loop): the geometry of render s+1 is computed beside the shading /
+// loss / adjoint of render s, and the three photo values of render s+1 -- the only loads inside the loop -- are issued at
+// the top of the pass that shades render s: they have a whole pass (~200 VALU instructions) to arrive, and because they
+// are issued behind the loads of render s the compiler's wait in front of the first use of render s's values is a counted
+// vmcnt that leaves them in flight (tests/test_photo_loss_cpu.py checks that in the assembly).  The loop body holds two
+// passes with the roles of the geometry and photo register sets swapped: nothing is copied from "next" to "current".
+// Left alone, the compiler SINKS the prefetch out of the pass that issues it, across the loop's exit test, to just in front
+// of its first use in the next pass (seen in the assembly: ~140 instructions ahead of the use instead of a whole pass).  An
+// empty asm that reads the three registers at the end of the issuing pass keeps the loads in that pass -- in front of its
+// scheduling barrier -- and puts their wait at its end (behind a second scheduling barrier: the empty asm may otherwise be
+// moved up), a whole pass of arithmetic behind the issue.
+#define SVBRDF_PHOTO_PIN(P) __builtin_amdgcn_sched_barrier(0); asm volatile("" ::"v"(P[0]), "v"(P[1]), "v"(P[2]));
+template <int NL, bool WITH_GRAD, int DEFER>
+__device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float y, const float *__restrict__ scp,
+                                                  const float *sc_lds, const float *__restrict__ pp, size_t plane,
+                                                  size_t pix, int S, float eps, float inv_count, Grad &acc)
+{
+    constexpr int ST = 9;
+    float lsum = 0.0f;
+    const VConst K = make_vconst();
+    const float s10 = vreg(0.0009765625f);      // 2^-10 (kLossScaleExp) as a VGPR operand of photo_terms' FMA
+    eps = vreg(eps);
+    inv_count = vreg(inv_count);
+    const size_t render = 3 * plane;            // floats per photo
+    float sc[9];
+    float pa[3], pb[3];
+    load_photo(pp, plane, pix, pa);             // render 0
+    if (WITH_GRAD) {
+        load_scene(scp, sc);
+        Geom ga = geometry<true>(K, sc, x, y), gb;
+        load_scene(scp + (S > 1 ? ST : 0), sc);
+#define SVBRDF_PHOTO_PASS(G_CUR, G_NEXT, P_CUR, P_NEXT, SI)                                                           \
+        {                                                                                                          \
+            asm volatile("" ::"s"(sc[0]), "s"(sc[8]));                                                             \
+            float cur[9];                                                                                          \
+            _Pragma("unroll") for (int i = 0; i < 9; ++i) cur[i] = sc[i];                                          \
+            load_scene(scp + ((SI) + 2 < S ? 2 * ST : ((SI) + 1 < S ? ST : 0)), sc);                               \
+            scp += ((SI) + 1 < S) ? ST : 0;                                                                        \
+            pp += ((SI) + 1 < S) ? render : 0;          /* photo of render s+1 (a harmless repeat on the last pass) */ \
+            load_photo(pp, plane, pix, P_NEXT);                                                                    \
+            __builtin_amdgcn_sched_barrier(0);                                                                     \
+            G_NEXT = geometry<true>(K, cur, x, y);                                                                 \
+            photo_pixel_scene_any<NL, WITH_GRAD, DEFER>(K, G_CUR, mi, P_CUR, s10, eps, inv_count, lsum, acc);      \
+            SVBRDF_PHOTO_PIN(P_NEXT)                                                                               \
+        }
+        for (int s = 0;;) {
+            SVBRDF_PHOTO_PASS(ga, gb, pa, pb, s)
+            if (++s >= S) break;
+            SVBRDF_PHOTO_PASS(gb, ga, pb, pa, s)
+            if (++s >= S) break;
+        }
+#undef SVBRDF_PHOTO_PASS
+    } else {
+        // forward only: scene table of the item staged in LDS (K3's measured choice for its forward-only kernels)
+        load_scene(sc_lds, sc);
+        Geom g_next = geometry<true>(K, sc, x, y);
+        for (int s = 0; s < S; ++s) {
+            const Geom g = g_next;
+            pp += (s + 1 < S) ? render : 0;
+            load_photo(pp, plane, pix, pb);
+            __builtin_amdgcn_sched_barrier(0);      // (the scheduler otherwise sinks the three loads to their first use)
+            load_scene(sc_lds + (s + 1 < S ? s + 1 : s) * 9, sc);
+            g_next = geometry<true>(K, sc, x, y);
+            photo_pixel_scene_any<NL, WITH_GRAD, DEFER>(K, g, mi, pa, s10, eps, inv_count, lsum, acc);
+            SVBRDF_PHOTO_PIN(pb)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) pa[k] = pb[k];
+        }
+    }
+#undef SVBRDF_PHOTO_PIN
+    lsum *= 0.693147180559945309417f;       // the loop sums |log2|
+    if (WITH_GRAD && DEFER) {               // the per-pixel constants the adjoint left out (shade_bwd's DEFER_*)
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (DEFER & 4) acc.d[k] *= mi.oms[k] * K.inv_pi;
+            else if (DEFER & 1) acc.d[k] *= K.inv_pi;
+            if (DEFER & 2) acc.r[k] *= mi.r4m[k];
+        }
+    }
+    return lsum;
+}
+
+// One thread = one pixel, all S renders of it; workgroup = 256 pixels of one batch item (as K3).
+template <bool WITH_GRAD, bool EARLY_COORDS>
+__device__ __forceinline__ void photo_loss_body(const float *__restrict__ input, const float *__restrict__ photos,
+                                                const float *__restrict__ scenes, const float *__restrict__ xrow,
+                                                float eps, float inv_count, double loss_scale, float fixed_scale,
+                                                float *__restrict__ grad_input, unsigned long long *__restrict__ ws,
+                                                float *__restrict__ loss_out, int S, int H, int W)
+{
+    extern __shared__ __attribute__((aligned(16))) float sc_lds[];      // [S][9], forward-only kernels
+    const size_t plane = (size_t)H * W;
+    const size_t pix = (size_t)blockIdx.x * kLossThreads + threadIdx.x;
+    const int b = blockIdx.y;
+    const bool active = pix < plane;
+    float lsum = 0.0f;
+    if (!WITH_GRAD) {
+        for (int i = threadIdx.x; i < S * 9; i += kLossThreads) sc_lds[i] = scenes[(size_t)b * S * 9 + i];
+        __syncthreads();
+    }
+    if (active) {
+        Maps in;
+        Grad acc;
+        // pixel coordinates issued in front of the plane loads (by-value-table kernels, power-of-two width): see
+        // rendering_loss_body
+        [[maybe_unused]] float x_early = 0.0f, y_early = 0.0f;
+        const bool pow2 = (W & (W - 1)) == 0;
+        const bool early_coords = EARLY_COORDS && WITH_GRAD && pow2;
+        if (early_coords) {
+            const unsigned p32 = (unsigned)pix, sh = (unsigned)__builtin_ctz((unsigned)W);
+            x_early = xrow[p32 & (unsigned)(W - 1)];
+            y_early = xrow[p32 >> sh];
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        load_maps_k3(input + (size_t)b * 12 * plane, plane, pix, in);
+        zero_grad(acc);
+        const bool tied = tied_roughness(in);
+        const MapK mi = prepare<WITH_GRAD>(in);
+        float x[1], y;
+        if (early_coords) {
+            x[0] = x_early;
+            y = -y_early;
+        } else if (pow2) {
+            const unsigned p32 = (unsigned)pix, sh = (unsigned)__builtin_ctz((unsigned)W);
+            x[0] = xrow[p32 & (unsigned)(W - 1)];
+            y = -xrow[p32 >> sh];
+        } else {
+            pixel_coords<1>(xrow, pix, W, x, y);
+        }
+        {
+            // a NaN or infinite normal / roughness value would vanish in the clamps (v_max returns the other operand):
+            // t - t is 0 for finite t and NaN otherwise, added to the pixel's x coordinate (rendering_loss_body).  Diffuse,
+            // specular and the photo values propagate through the arithmetic by themselves.
+            const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
+            x[0] += chk - chk;
+        }
+        const float *__restrict__ scp = scenes + (size_t)b * S * 9;
+        const float *__restrict__ pp = photos + (size_t)b * S * 3 * plane;
+        constexpr int kDefer = WITH_GRAD ? 7 : 0;
+        if (__all(tied))     // wave-uniform
+            lsum = photo_scene_loop<1, WITH_GRAD, kDefer>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc);
+        else
+            lsum = photo_scene_loop<3, WITH_GRAD, kDefer & 3>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc);
+        if (WITH_GRAD) store_grads_k3(grad_input + (size_t)b * 12 * plane, plane, pix, acc);
+    }
+    {
+        __shared__ float wave_part[kLossThreads / 64];
+        lsum = wave_sum(lsum);
+        if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = lsum;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float t = 0.0f;
+#pragma unroll
+            for (int w = 0; w < kLossThreads / 64; ++w) t += wave_part[w];
+            loss_arrive(t, fixed_scale, loss_scale, ws, loss_out);
+        }
+    }
+}
+
+#ifndef SVBRDF_PHOTO_LOSS_MIN_WAVES
+#define SVBRDF_PHOTO_LOSS_MIN_WAVES 4      // 128 VGPRs, as K3
+#endif
+#define SVBRDF_PHOTO_LOSS_ATTRS \
+    __launch_bounds__(kLossThreads) __attribute__((amdgpu_waves_per_eu(SVBRDF_PHOTO_LOSS_MIN_WAVES, 8)))
+
+// scene table in device memory (any B*S)
+template <bool WITH_GRAD>
+__global__ SVBRDF_PHOTO_LOSS_ATTRS void k_photo_loss(const float *__restrict__ input, const float *__restrict__ photos,
+                                                     const float *__restrict__ scenes, const float *__restrict__ xrow,
+                                                     float eps, float inv_count, double loss_scale, float fixed_scale,
+                                                     float *__restrict__ grad_input, unsigned long long *__restrict__ ws,
+                                                     float *__restrict__ loss_out, int S, int H, int W)
+{
+    photo_loss_body<WITH_GRAD, false>(input, photos, scenes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input,
+                                      ws, loss_out, S, H, W);
+}
+
+// scene table BY VALUE in the kernel-argument block, first argument, read through the segment pointer
+// (k_rendering_loss_inl has the reasons)
+template <bool WITH_GRAD>
+__global__ SVBRDF_PHOTO_LOSS_ATTRS void k_photo_loss_inl([[maybe_unused]] const SceneBlock table,
+                                                         const float *__restrict__ input, const float *__restrict__ photos,
+                                                         const float *__restrict__ xrow, float eps, float inv_count,
+                                                         double loss_scale, float fixed_scale,
+                                                         float *__restrict__ grad_input, unsigned long long *__restrict__ ws,
+                                                         float *__restrict__ loss_out, int S, int H, int W)
+{
+    const float *__restrict__ rows = (const float *)__builtin_amdgcn_kernarg_segment_ptr();
+    photo_loss_body<WITH_GRAD, true>(input, photos, rows, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
+                                     loss_out, S, H, W);
+}
+
+template <bool G>
+void launch_photo(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st, const float *input, const float *photos,
+                  const float *scenes, const float *xrow, float eps, float inv_count, double loss_scale, float fixed_scale,
+                  float *grad_input, unsigned long long *ws, float *loss_out, int B, int S, int H, int W)
+{
+    if (rows) {
+        SceneBlock block_arg;      // only the first B*S rows are ever read
+        std::memcpy(block_arg.v, rows, (size_t)B * S * 9 * sizeof(float));
+        hipLaunchKernelGGL((k_photo_loss_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos, xrow,
+                           eps, inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+    } else {
+        hipLaunchKernelGGL((k_photo_loss<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, scenes, xrow, eps,
+                           inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+    }
+}
+
+// argument checks, grid, fixed-point scale: those of svbrdf_rendering_loss_fwd_bwd (loss_impl in svbrdf_kernels.hip).  The
+// launch is counted by the main unit's counter through launch_status() (svbrdf_internal_launch_status).
+int photo_impl(const char *who, bool scenes_on_host, const float *input, const float *photos, const float *scenes,
+               const float *xrow, float eps, float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes,
+               int B, int S, int H, int W, void *stream)
+{
+    if (!input || !photos || !scenes || !xrow || !loss_out || !workspace) return fail(SVBRDF_ERR_NULL, who);
+    if (int e = check_dims(B, S, H, W)) return e;
+    if (!(eps >= 1e-9f) || !(eps <= 1e9f))
+        return fail(SVBRDF_ERR_DIMS, "photo_loss: eps must lie in [1e-9, 1e9] (the reference uses 0.1)");
+    if (scenes_on_host && (long long)B * S > SVBRDF_HOST_SCENES_MAX_ROWS)
+        return fail(SVBRDF_ERR_DIMS, "host_scenes: B*S exceeds SVBRDF_HOST_SCENES_MAX_ROWS (upload the table and use the device-pointer entry)");
+    if (!aligned(input, 4) || !aligned(photos, 4) || !aligned(scenes, 4) || !aligned(xrow, 4) || !aligned(loss_out, 4) ||
+        !aligned(workspace, 8) || (grad_input && !aligned(grad_input, 4)))
+        return fail(SVBRDF_ERR_ALIGN, "photo_loss: pointers must be 4-byte aligned (workspace 8-byte)");
+    if (workspace_bytes < svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
+        return fail(SVBRDF_ERR_WORKSPACE, "photo_loss: workspace too small");
+    const long long plane = (long long)H * W;
+    if (plane > (1LL << 25))
+        return fail(SVBRDF_ERR_DIMS, "photo_loss: H*W exceeds 2^25 (one item's 12 planes are addressed with 32-bit byte offsets)");
+    const dim3 grid((unsigned)((plane + kLossThreads - 1) / kLossThreads), (unsigned)B, 1);
+    const double count = (double)B * S * 3.0 * (double)plane;
+    const float inv_count = (float)(1.0 / count);
+    int k = 24;     // fixed-point scale 2^k of the per-workgroup partial sums (loss_impl)
+    const double worst_per_slot = count * 32.0 / (double)kLossSlots + 32.0 * kLossThreads * 3 * S;
+    while (k > 0 && worst_per_slot * std::ldexp(1.0, k) >= std::ldexp(1.0, kLossCountShift - 1)) --k;
+    const float fixed_scale = (float)std::ldexp(1.0, k);
+    const double loss_scale = std::ldexp(1.0, -k) / count;
+    if ((unsigned long long)grid.x * grid.y >= (1ULL << 16) * kLossSlots)
+        return fail(SVBRDF_ERR_DIMS, "photo_loss: too many workgroups for the arrival counters");
+    const size_t lds_bytes = grad_input ? 0 : (size_t)S * 9 * sizeof(float);
+    if (lds_bytes > 60 * 1024) return fail(SVBRDF_ERR_DIMS, "photo_loss: too many scenes per item for the LDS stage (max 1706)");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    unsigned long long *ws = static_cast<unsigned long long *>(workspace);
+    const float *rows = scenes_on_host ? scenes : nullptr;
+    if (grad_input)
+        launch_photo<true>(rows, grid, lds_bytes, st, input, photos, scenes, xrow, eps, inv_count, loss_scale, fixed_scale,
+                           grad_input, ws, loss_out, B, S, H, W);
+    else
+        launch_photo<false>(rows, grid, lds_bytes, st, input, photos, scenes, xrow, eps, inv_count, loss_scale, fixed_scale,
+                            grad_input, ws, loss_out, B, S, H, W);
+    return launch_status(who);
+}
+
+}  // namespace
+
+extern "C" {
+
+int svbrdf_photo_loss_fwd_bwd(const float *input, const float *photos, const float *scenes, const float *xrow, float eps,
+                              float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes, int B, int S,
+                              int H, int W, void *stream)
+{
+    return photo_impl("photo_loss", false, input, photos, scenes, xrow, eps, loss_out, grad_input, workspace,
+                      workspace_bytes, B, S, H, W, stream);
+}
+
+int svbrdf_photo_loss_fwd_bwd_host_scenes(const float *input, const float *photos, const float *scenes_host,
+                                          const float *xrow, float eps, float *loss_out, float *grad_input,
+                                          void *workspace, size_t workspace_bytes, int B, int S, int H, int W, void *stream)
+{
+    return photo_impl("photo_loss_host_scenes", true, input, photos, scenes_host, xrow, eps, loss_out, grad_input,
+                      workspace, workspace_bytes, B, S, H, W, stream);
+}
+
+}  // extern "C"

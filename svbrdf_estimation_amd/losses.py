@@ -262,6 +262,170 @@ class RenderingLoss(nn.Module):
         return nn.functional.l1_loss(a, t)
 
 
+class _FusedPhotoLoss(torch.autograd.Function):
+    """The fused photo-loss kernel behind autograd: it already produces d loss/d input for upstream gradient 1."""
+
+    @staticmethod
+    def forward(ctx, input, photos, scenes, eps):
+        need_in = ctx.needs_input_grad[0]
+        ctx.save_for_backward(input, photos)        # (for backward(create_graph=True) only: references, no copies)
+        ctx.second_order = (scenes if scenes.is_cuda else scenes.detach().clone(), float(eps))
+        loss, ctx.grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if torch.is_grad_enabled():
+            # backward(create_graph=True): the kernel's gradient is a constant to autograd; differentiate the composed
+            # definition instead (same scenes), in float64 like the other fused losses do
+            input, photos = ctx.saved_tensors
+            scenes, eps = ctx.second_order
+            with torch.enable_grad():
+                loss = composed_photo_loss(input.to(torch.float64), photos, scenes, eps)
+                g, = torch.autograd.grad(loss, [input], grad_loss.to(torch.float64).reshape(()), create_graph=True)
+            return g.to(input.dtype), None, None, None
+        if ctx.grad is None:
+            raise RuntimeError("Trying to backward through the fused photo loss a second time: its gradient buffer was "
+                               "handed to the first backward.  Specify retain_graph=True for the first one.")
+        # chain rule through the scalar loss on the device, no host sync (as _FusedRenderingLoss.backward)
+        keep = _current_backward_keeps_graph()
+        grad = ctx.grad
+        if not keep:
+            ctx.grad = None
+        if _is_unit_gradient(grad_loss):     # _PhotoLossTensor.backward's cached 1.0: nothing to scale, nothing to launch
+            return (grad.clone() if keep else grad), None, None, None
+        scale = grad_loss.detach().to(torch.float32).reshape(1)
+        return _native.scale_inplace_(grad.clone() if keep else grad, scale), None, None, None
+
+
+class _PhotoLossTensor(torch.Tensor):
+    """The 0-dim loss PhotoLoss returns when a gradient is wanted: an ordinary tensor whose PLAIN ``backward()`` (no
+    explicit gradient, no create_graph, nobody watching the loss's gradient) hands autograd a cached device-resident 1.0
+    as the upstream gradient; the loss's node recognises that tensor and skips its (no-op) scale launch, so a step is
+    ONE kernel launch.  Same values bit for bit: multiplying by 1.0 is what was skipped.  Every other use goes through
+    autograd unchanged (``_FusedLossTensor`` does the same for the native host path of the other losses)."""
+
+    __torch_function__ = torch._C._disabled_torch_function_impl
+
+    def backward(self, gradient=None, retain_graph=None, create_graph=False, inputs=None):
+        if gradient is None and not create_graph and self._backward_hooks is None and not self.retains_grad:
+            gradient = _unit_gradient(self.device)
+        return torch.Tensor.backward(self, gradient, retain_graph, create_graph, inputs)
+
+
+_unit_gradients = {}
+
+
+def _unit_gradient(device):
+    t = _unit_gradients.get(device)
+    if t is None:
+        t = _unit_gradients[device] = torch.ones((), dtype=torch.float32, device=device)
+    return t
+
+
+def _is_unit_gradient(grad):
+    t = _unit_gradients.get(grad.device)
+    return t is not None and grad.data_ptr() == t.data_ptr() and t._version == 0 and grad.dtype == torch.float32
+
+
+def composed_photo_loss(input, photos, scenes, eps):
+    """The photo loss from differentiable pieces -- S renders per item through K1 / K2 (``renderers._RenderFunction``:
+    float32 maps through the float32 kernels, float64 maps through the float64 ones), log / L1 mean by torch.  What float64
+    maps take and what ``backward(create_graph=True)`` of the fused loss differentiates.  ``scenes`` [B,S,9] float32."""
+    rendered = renderers._RenderFunction.apply(input, scenes)
+    return nn.functional.l1_loss(torch.log(rendered + eps), torch.log(photos.to(rendered.dtype) + eps))
+
+
+class PhotoLoss(nn.Module):
+    """The rendering loss against PHOTOGRAPHS instead of against the renderings of ground-truth maps:
+
+        mean over b,s,c,i,j of | log(render(scenes[b][s], input[b]) + eps) - log(photos[b,s] + eps) |
+
+    -- fitting maps to captured or synthesised photos, self-supervised training on the input photos themselves.
+    ``forward(input [B,12,H,W], photos [B,S,3,H,W] or [B,3,H,W] (S = 1), scenes)`` returns a 0-dim tensor, differentiable
+    w.r.t. ``input`` only.  ``scenes``: the light / view of every photo, a ``[B,S,9]`` float32 tensor (host or device;
+    camera xyz | light xyz | light rgb) or a nested list ``scenes[b][s]`` of ``environment.Scene``-like objects.
+
+    With this package's ``LocalRenderer`` and float32 maps on a ROCm device it is ONE fused HIP kernel (forward and the
+    analytic backward; csrc/svbrdf_photo_loss.hip).  Any other renderer object, float64 maps and
+    ``backward(create_graph=True)`` take the composed definition: ``renderer.render`` per scene, ``log``, L1 mean --
+    which is also the semantic specification of the fused path."""
+
+    def __init__(self, renderer, eps=0.1):
+        super().__init__()
+        self.renderer = renderer
+        self.eps = eps
+
+    def uses_fused_kernel(self):
+        return RenderingLoss(self.renderer).uses_fused_kernel()
+
+    @staticmethod
+    def _check(input, photos):
+        if not isinstance(input, torch.Tensor) or not isinstance(photos, torch.Tensor):
+            raise TypeError("input and photos must be tensors")
+        if input.dim() != 4 or input.shape[1] != 12:
+            raise ValueError("input must be [B,12,H,W]")
+        if photos.dim() == 4:
+            photos = photos.unsqueeze(1)                # [B,3,H,W]: one photo per item
+        if photos.dim() != 5 or photos.shape[0] != input.shape[0] or photos.shape[2] != 3 \
+                or photos.shape[3:] != input.shape[2:]:
+            raise ValueError("photos must be [B,S,3,H,W] (or [B,3,H,W]) with the input's B, H and W")
+        if photos.requires_grad:
+            raise RuntimeError("PhotoLoss has no gradient w.r.t. the photos: pass photos.detach()")
+        if photos.device != input.device:
+            raise ValueError("input and photos must be on the same device")
+        if not photos.dtype.is_floating_point or not input.dtype.is_floating_point:
+            raise TypeError("input and photos must be floating point (got %s, %s)" % (input.dtype, photos.dtype))
+        return photos
+
+    @staticmethod
+    def _scene_objects(scenes, B, S):
+        """-> scenes[b][s] as objects with .camera.pos / .light.pos / .light.color (what a plugin renderer takes)"""
+        if isinstance(scenes, torch.Tensor):
+            if tuple(scenes.shape) != (B, S, 9):
+                raise ValueError("scenes must be [B,S,9] = %s, got %s" % ((B, S, 9), tuple(scenes.shape)))
+            return [environment.scenes_from_table(t) for t in scenes.detach().to("cpu", torch.float32)]
+        rows = [list(r) for r in scenes]
+        if len(rows) != B or any(len(r) != S for r in rows):
+            raise ValueError("scenes must hold S = %d scenes for each of the B = %d items" % (S, B))
+        return rows
+
+    @staticmethod
+    def _scene_table(scenes, B, S):
+        """-> [B,S,9] float32 tensor (a tensor passes, host or device; Scene objects become a host table)"""
+        if isinstance(scenes, torch.Tensor):
+            if tuple(scenes.shape) != (B, S, 9):
+                raise ValueError("scenes must be [B,S,9] = %s, got %s" % ((B, S, 9), tuple(scenes.shape)))
+            if scenes.dtype != torch.float32:
+                raise TypeError("scenes must be float32 (got %s)" % scenes.dtype)
+            return scenes
+        rows = PhotoLoss._scene_objects(scenes, B, S)
+        return torch.stack([torch.stack([environment.scene_to_row(sc) for sc in r]) for r in rows])
+
+    def forward(self, input, photos, scenes):
+        photos = self._check(input, photos)
+        B, S = photos.shape[0], photos.shape[1]
+        if not self.uses_fused_kernel():
+            return self._forward_plugin(input, photos, self._scene_objects(scenes, B, S))
+        table = self._scene_table(scenes, B, S)
+        if not input.is_cuda:
+            raise _native.NativeLibraryError("PhotoLoss with the MI355X LocalRenderer needs tensors on a ROCm device "
+                                             "(got %s); there is no CPU fallback" % input.device)
+        if input.dtype == torch.float64 or photos.dtype == torch.float64:
+            # double on either side: the reference's torch ops would promote, so does this (float64 K1 / K2)
+            return composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps)
+        if input.dtype != torch.float32 or photos.dtype != torch.float32:
+            raise TypeError("input and photos must be float32 or float64 (got %s, %s)" % (input.dtype, photos.dtype))
+        loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps))
+        return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
+
+    def _forward_plugin(self, input, photos, scenes):
+        """the composed definition with a foreign renderer object: its own render() per scene, log, L1 mean"""
+        rendered = torch.stack([torch.cat([self.renderer.render(sc, input[b]) for sc in scenes[b]], dim=0)
+                                for b in range(input.shape[0])], dim=0)
+        return nn.functional.l1_loss(torch.log(rendered + self.eps), torch.log(photos + self.eps))
+
+
 class MixedLoss(nn.Module):
     """losses.py:54-63: l1_weight * SVBRDFL1Loss + RenderingLoss.
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds an experiment variant of libsvbrdf_hip.so into tools/_build/libsvbrdf_<tag>.so with extra flags for both
-# translation units (e.g. -DSVBRDF_X=1) and optional overrides SCHED_MAIN=... SCHED_ADJOINT=... in the environment.
+# translation units (e.g. -DSVBRDF_X=1) and optional overrides SCHED_MAIN=... SCHED_ADJOINT=... SCHED_PHOTO=... in the environment.
 #   bash tools/build_variant.sh <tag> [extra compiler flags...]
 # SRC_DIR=<dir holding svbrdf_kernels.hip and svbrdf_hip.h> builds another revision of the source (e.g. files taken
 # with `git show <rev>:...`) for a same-box A/B against it.
@@ -22,6 +22,10 @@ AUX=""
 if [ -f $src/svbrdf_aux_f64.hip ]; then      # round 5 on: the auxiliary float64 unit is a file of its own
   /opt/rocm/bin/hipcc $F -c -o $out/obj_$tag/aux.o $src/svbrdf_aux_f64.hip &
   AUX=$out/obj_$tag/aux.o
+fi
+if [ -f $src/svbrdf_photo_loss.hip ]; then   # round 9 on: the fused photo loss, a unit with its own option set (SCHED_PHOTO)
+  /opt/rocm/bin/hipcc $F ${SCHED_PHOTO:-$SA} -c -o $out/obj_$tag/photo.o $src/svbrdf_photo_loss.hip &
+  AUX="$AUX $out/obj_$tag/photo.o"
 fi
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -fPIC -shared -o $out/libsvbrdf_$tag.so $out/obj_$tag/main.o $out/obj_$tag/adj.o $out/obj_$tag/adjx.o $AUX

@@ -1,0 +1,77 @@
+"""Fit SVBRDF maps to photographs with the fused photo loss (losses.PhotoLoss): the inverse-rendering use of the engine.
+
+    python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
+
+Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
+each from ``synthesis.render_inputs`` (the scene table is what that call draws from torch's global generator: the same seed
+gives it again).  A perturbed copy of the maps is then a leaf tensor that Adam fits to the photographs through
+``PhotoLoss`` -- one kernel launch per step for loss and gradient.  Prints the loss per step and the time per step.
+"""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import synth  # noqa: E402
+from svbrdf_estimation_amd import losses, renderers, synthesis  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--photos", type=int, default=9, help="photographs per material")
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--noise", action="store_true", help="sensor noise on the photographs (dataset.py:215-217)")
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--print-every", type=int, default=10)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs a ROCm device"
+    dev = torch.device("cuda:0")
+    B, H, S = args.batch, args.size, args.photos
+    truth = torch.from_numpy(synth.make_maps(args.seed, B, H)).to(dev)
+    torch.manual_seed(args.seed)
+    torch.cuda.manual_seed(args.seed)
+    photos = synthesis.render_inputs(truth, S, use_augmentation=True, noise="device" if args.noise else None)
+    torch.manual_seed(args.seed)
+    table = torch.stack([synthesis.input_scene_table(S, True) for _ in range(B)], dim=0).to(dev)
+    start = truth.clone()
+    jitter = torch.from_numpy(synth.uniform01(args.seed + 1000, (B, 9, H, H))).to(dev) - 0.5
+    start[:, 3:] = (start[:, 3:] + 0.3 * jitter).clamp_(0.02, 0.98)        # diffuse, roughness, specular off by up to 0.15
+    x = start.clone().requires_grad_(True)
+    fn = losses.PhotoLoss(renderers.LocalRenderer())
+    opt = torch.optim.Adam([x], lr=args.lr)
+    print("fitting %d x [12,%d,%d] maps to %d photographs each (%s), Adam lr %g" % (
+        B, H, H, S, "sensor noise" if args.noise else "noise-free", args.lr))
+    t_last, step_ms = None, []
+    for step in range(args.steps):
+        if step % args.print_every == 0:
+            torch.cuda.synchronize()
+            now = time.perf_counter()
+            if t_last is not None:
+                step_ms.append(1e3 * (now - t_last) / args.print_every)
+            t_last = now
+        opt.zero_grad(set_to_none=True)
+        loss = fn(x, photos, table)
+        loss.backward()
+        opt.step()
+        with torch.no_grad():
+            x[:, 3:].clamp_(0.0, 1.0)
+        if step % args.print_every == 0 or step == args.steps - 1:
+            err = (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
+            print("step %4d  loss %.6f  mean |d,r,s - truth| %.5f%s" % (
+                step, loss.item(), err, "  %.3f ms/step" % step_ms[-1] if step_ms else ""))
+    if step_ms:
+        print("median %.3f ms per step (loss + backward + Adam + clamp, host included)" % float(np.median(step_ms)))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,133 @@
+"""The fused photo loss against K3 and against the composed form, one process, one box (profiles/r09_photo_loss.txt).
+
+    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...]
+
+At the configuration-2 shape (B = 8, 256 x 256, S = 9, scene table by value, six batches rotating beyond the 256 MB
+Infinity Cache, as bench.py does) it prints the event-timed median per launch of
+  * the photo loss (svbrdf_photo_loss_fwd_bwd_host_scenes),
+  * K3, the rendering loss on the same maps (svbrdf_mixed_loss_fwd_bwd_host_scenes, l1_weight 0),
+  * the composed form: K1, log / L1 mean by torch, the backward of those ops, K2 (what PhotoLoss takes for float64 maps,
+    here on float32 maps),
+the fraction of 8 TB/s at the algorithmic bytes (12 + 3 S + 12) * 4 * H * W * B, and the VALU instructions per
+pixel-render of the scene loops from tools/isa_stats.py (where hipcc is present).  The method is that of
+tests/test_gpu_photo_loss.py::test_photo_loss_is_no_slower_than_k3, which it imports: launches enqueued behind a spinning
+wave so that the stream runs them back to back, an event between every two, medians of interleaved rounds.
+
+--variants: other builds of the library (tools/build_variant.sh, e.g. the photo-loss unit compiled with another of the
+Makefile's scheduler sets), each measured in a child process of its own on this box, interleaved with the shipped build.
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+
+def isa_lines():
+    hipcc, csrc = "/opt/rocm/bin/hipcc", os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
+    if not os.path.exists(hipcc):
+        return ["VALU per pixel-render: not counted here (no hipcc on this box); tests/test_photo_loss_cpu.py holds the budget"]
+    import tempfile
+    import isa_stats
+    var = lambda n: subprocess.check_output(["make", "-s", "-C", csrc, "print-" + n], text=True).split()
+    out = os.path.join(tempfile.mkdtemp(prefix="photo_isa_"), "photo.s")
+    cmd = var("HIPCC") + var("HIPFLAGS") + var("SCHED_PHOTO") + ["-S", "--cuda-device-only", "-o", out, "svbrdf_photo_loss.hip"]
+    subprocess.check_call(cmd, cwd=csrc, stderr=subprocess.DEVNULL)
+    text, lines = open(out).read(), []
+    for k in sorted(isa_stats.kernels(text)):
+        if "k_photo_loss" not in k:
+            continue
+        _, meta, _, loops, _, _ = isa_stats.analyse(text, k)
+        per = 2 if "ILb1E" in k else 1
+        for c in sorted((c for c in loops if c["trans"]), key=lambda c: c["valu"]):
+            lines.append("%-24s %s loop: %5.1f VALU, %4.1f transcendentals per pixel-render; %s VGPRs, scratch %s" % (
+                ("by-value" if "_inl" in k else "device") + (" fwd+bwd" if per == 2 else " fwd only"),
+                "tied  " if c["trans"] / per < 14 else "untied", c["valu"] / per, c["trans"] / per, meta.get("NumVgprs"),
+                meta.get("ScratchSize")))
+    return lines
+
+
+def measure_composed(dev, native, sets=6, n=30, rounds=3):
+    import numpy as np
+    import torch
+    from bench import synthetic_maps
+    from svbrdf_estimation_amd import environment, losses
+    import test_gpu_photo_loss as T
+    B, H = 8, 256
+    gen = torch.Generator().manual_seed(5)
+    torch.manual_seed(11)
+    table = environment.BatchSceneSampler(B, 3, 6).sample().contiguous()
+    ins = [synthetic_maps(gen, B, H, tied=True).to(dev).requires_grad_(True) for _ in range(sets)]
+    photos = [native.render_fwd(synthetic_maps(gen, B, H, tied=True).to(dev), table).clamp_(0.0, 1.0) for _ in range(sets)]
+    clk = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def step(i):
+        k = i % sets
+        ins[k].grad = None
+        losses.composed_photo_loss(ins[k], photos[k], table, 0.1).backward()
+
+    return float(np.median([T._event_timed_median(step, n, lambda: native.clock_probe(clk, ticks=800000), dev)
+                            for _ in range(rounds)]))
+
+
+def child():
+    import torch
+    from svbrdf_estimation_amd import _native
+    import test_gpu_photo_loss as T
+    dev = torch.device("cuda:0")
+    res = T.measure_photo_loss_against_k3(dev, _native)
+    res["composed_us"] = measure_composed(dev, _native)
+    res["library"] = _native.library_path()
+    print("RESULT " + json.dumps(res))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--out", default=None, help="also write the report to this file")
+    ap.add_argument("--variants", nargs="*", default=[], metavar="TAG=LIB")
+    ap.add_argument("--passes", type=int, default=1, help="how often the builds are measured in turn")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    args = ap.parse_args()
+    if args.child:
+        return child()
+    builds = [("shipped", None)] + [tuple(v.split("=", 1)) for v in args.variants]
+    rows = []
+    for p in range(args.passes):
+        for tag, lib in builds:
+            env = dict(os.environ)
+            if lib:
+                env["SVBRDF_HIP_LIB"] = os.path.abspath(lib)
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, text=True, timeout=300,
+                                 stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+            line = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")]
+            if out.returncode != 0 or not line:
+                print(out.stdout[-2000:])
+                raise SystemExit("measurement of build %r failed (exit status %s): nothing more is started" % (tag, out.returncode))
+            rows.append((tag, p, json.loads(line[0][7:])))
+    B, H, S = 8, 256, 9
+    lines = ["# tools/photo_loss_bench.py on %s; B = %d, %d x %d, S = %d, scene table by value, %d rotating batches" % (
+        rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
+        "# medians of event-timed launches (us per launch); algorithmic bytes of the photo loss (12 + 3 S + 12) * 4 * H * W * B = %.1f MB"
+        % ((12 + 3 * S + 12) * 4 * H * H * B / 1e6)]
+    for tag, p, r in rows:
+        lines.append("%-16s pass %d: photo loss %7.2f  K3 %7.2f  composed K1 + torch + K2 %8.2f   photo loss = %.3f of 8 TB/s, "
+                     "%.2fx K3, %.1fx composed   rounds %s" % (tag, p, r["photo_loss_us"], r["k3_us"], r["composed_us"],
+                                                             r["photo_loss_frac_of_8TBps"], r["k3_us"] / r["photo_loss_us"],
+                                                             r["composed_us"] / r["photo_loss_us"], r["rounds"]))
+    lines += ["# scene loops of the shipped source (hipcc -S with the Makefile's flags, tools/isa_stats.py); K3's tied loop: 301 VALU per pixel-render"]
+    lines += isa_lines()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
