@@ -276,11 +276,13 @@ static int FN(render_bwd)(const float *maps, const float *scenes, const float *x
  * losses.py:7-19 (SVBRDFL1Loss: L1 of normals and roughness, L1 of log(x+eps_l1) for
  * diffuse and specular, each a mean over B*3*H*W) combined as in losses.py:62-63
  * (MixedLoss = l1_weight * L1 + rendering).
+ * input_lo (optional, [B,12,H,W]): added to the input maps after their conversion to REAL -- the low parts of maps that
+ * are not float32 values (the double instantiation of the head-fused loss decodes the head in double).
  * tie_allow (optional, [B,12,H,W]): per gradient element, 2 * sum over the pixel's tied terms -- those the tie map
  * counts (not a structural zero) with |delta| < tie_level -- of |that term's sign-free contribution| (shade_bwd of
  * g_rad = invN / ai in its one channel).  Where sign(delta) is rounding noise an fp32 evaluation may pick either sign
  * (or 0), which moves the gradient by at most that much.  The L1 part never adds to it. */
-static int FN(rendering_loss)(const float *input, const float *target,
+static int FN(rendering_loss)(const float *input, const double *input_lo, const float *target,
                               const float *scenes, const float *xrow, float eps,
                               float l1_weight, float eps_l1,
                               double *loss_out, OUT_T *grad_input, OUT_T *min_abs_delta,
@@ -308,6 +310,15 @@ static int FN(rendering_loss)(const float *input, const float *target,
             REAL tie = (REAL)1e30;      /* smallest |log difference| of this pixel: sign() is noise below ~1e-6 */
             REAL al[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   /* tie allowance of the 12 gradient elements */
             FN(load_maps)(mi, plane, pix, n, d, r, s);
+            if (input_lo) {     /* the input maps are input + input_lo: maps decoded in double (head_loss, f64) */
+                const double *lo = input_lo + (size_t)b * 12 * plane + pix;
+                for (k = 0; k < 3; ++k) {
+                    n[k] += (REAL)lo[(size_t)(0 + k) * plane];
+                    d[k] += (REAL)lo[(size_t)(3 + k) * plane];
+                    r[k] += (REAL)lo[(size_t)(6 + k) * plane];
+                    s[k] += (REAL)lo[(size_t)(9 + k) * plane];
+                }
+            }
             FN(load_maps)(mt, plane, pix, tn, td, tr, ts);
             if (l1_weight != 0.0f) {
                 for (k = 0; k < 3; ++k) {

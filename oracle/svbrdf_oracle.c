@@ -121,7 +121,7 @@ EXPORT int svbrdf_oracle_rendering_loss(const float *input, const float *target,
                                         int B, int S, int H, int W)
 {
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f32(input, target, scenes, xrow, eps, 0.0f, 0.01f, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
+    return e ? e : rendering_loss_f32(input, NULL, target, scenes, xrow, eps, 0.0f, 0.01f, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
 }
 
 /* losses.py:54-63 MixedLoss = l1_weight * SVBRDFL1Loss + RenderingLoss */
@@ -132,7 +132,7 @@ EXPORT int svbrdf_oracle_mixed_loss(const float *input, const float *target,
                                     int B, int S, int H, int W)
 {
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f32(input, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
+    return e ? e : rendering_loss_f32(input, NULL, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
 }
 
 /* per pixel: the smallest |log(render(input)+eps) - log(render(target)+eps)| over scenes and channels,
@@ -145,7 +145,7 @@ EXPORT int svbrdf_oracle_loss_tie_map(const float *input, const float *target, c
 {
     double loss;
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, 0.0f, 0.01f, &loss, NULL, min_abs_delta, NULL, 0.0, B, S, H, W);
+    return e ? e : rendering_loss_f64(input, NULL, target, scenes, xrow, eps, 0.0f, 0.01f, &loss, NULL, min_abs_delta, NULL, 0.0, B, S, H, W);
 }
 
 /* per gradient element of the rendering loss: the largest amount by which the sign() of tied terms (those
@@ -157,7 +157,7 @@ EXPORT int svbrdf_oracle_loss_tie_allowance(const float *input, const float *tar
 {
     double loss;
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, 0.0f, 0.01f, &loss, NULL, NULL, allowance,
+    return e ? e : rendering_loss_f64(input, NULL, target, scenes, xrow, eps, 0.0f, 0.01f, &loss, NULL, NULL, allowance,
                                       tie_level, B, S, H, W);
 }
 
@@ -205,20 +205,45 @@ EXPORT int svbrdf_oracle_head_decode(const float *enc, float *maps, int B, int H
     return 0;
 }
 
-/* chain rule of head_decode, in double: g12 [B,12,H,W] -> g9 [B,9,H,W] */
-static void head_chain(const float *maps, const float *len, const double *g12, double *g9, int B, int H, int W)
+/* head_decode in double on the same float32 encoded values: maps64 [B,12,H,W], len64 [B,H,W] */
+static void head_decode_f64(const float *enc, double *maps64, double *len64, int B, int H, int W)
 {
     const size_t plane = (size_t)H * W;
     long bp;
 #pragma omp parallel for schedule(static)
     for (bp = 0; bp < (long)B * (long)plane; ++bp) {
         size_t b = (size_t)bp / plane, p = (size_t)bp % plane;
-        const float *m = maps + b * 12 * plane;
+        const float *e = enc + b * 9 * plane + p;
+        double *m = maps64 + b * 12 * plane + p;
+        double vx = (double)e[0] * 3.0, vy = (double)e[plane] * 3.0;
+        double len = sqrt((vx * vx + vy * vy) + 1.0);
+        int k;
+        m[0] = vx / len;
+        m[plane] = vy / len;
+        m[2 * plane] = 1.0 / len;
+        for (k = 0; k < 3; ++k) {
+            m[(3 + k) * plane] = ((double)e[(2 + k) * plane] + 1.0) / 2.0;
+            m[(6 + k) * plane] = ((double)e[5 * plane] + 1.0) / 2.0;
+            m[(9 + k) * plane] = ((double)e[(6 + k) * plane] + 1.0) / 2.0;
+        }
+        len64[b * plane + p] = len;
+    }
+}
+
+/* chain rule of head_decode, in double: g12 [B,12,H,W] -> g9 [B,9,H,W]; maps [B,12,H,W] and len [B,H,W] as the loss saw them */
+static void head_chain(const double *maps, const double *len, const double *g12, double *g9, int B, int H, int W)
+{
+    const size_t plane = (size_t)H * W;
+    long bp;
+#pragma omp parallel for schedule(static)
+    for (bp = 0; bp < (long)B * (long)plane; ++bp) {
+        size_t b = (size_t)bp / plane, p = (size_t)bp % plane;
+        const double *m = maps + b * 12 * plane;
         const double *g = g12 + b * 12 * plane;
         double *o = g9 + b * 9 * plane;
         double n0 = m[p], n1 = m[plane + p], n2 = m[2 * plane + p];
         double ng = n0 * g[p] + n1 * g[plane + p] + n2 * g[2 * plane + p];
-        double il = 1.0 / (double)len[b * plane + p];
+        double il = 1.0 / len[b * plane + p];
         int k;
         o[0 * plane + p] = 3.0 * (g[p] - n0 * ng) * il;
         o[1 * plane + p] = 3.0 * (g[plane + p] - n1 * ng) * il;
@@ -231,32 +256,60 @@ static void head_chain(const float *maps, const float *len, const double *g12, d
 }
 
 /* mixed loss of the decoded head output and its gradient w.r.t. the 9 encoded channels.
- * f64 != 0: the loss/gradient w.r.t. the decoded maps are evaluated in double. */
+ * f64 == 0: the reference's float32 arithmetic -- float32 decode, float32 loss and 12-channel gradient; only the chain rule
+ *           through the decode is carried out in double, on the float32 normal and length.
+ * f64 != 0: the same formulas in double on the same float32 encoded values, the DECODE INCLUDED: neither the normal
+ *           normalize(3 ex, 3 ey, 1) nor (e + 1) / 2 is rounded to float32 on its way into the loss (they reach
+ *           rendering_loss_f64 as float32 value + low part).  This is the double-precision evaluation that an independent
+ *           float64 autograd of decode + loss reproduces to rounding (tests/test_head_loss_cpu.py); with a float32 decode
+ *           in front of a double loss the two differed by up to 7e-6 of max|gradient|. */
 EXPORT int svbrdf_oracle_head_loss(const float *enc, const float *target, const float *scenes,
                                    const float *xrow, float eps, float l1_weight, float eps_l1,
                                    double *loss_out, double *grad9, int f64, int B, int S, int H, int W)
 {
-    const size_t n12 = (size_t)B * 12 * H * W;
+    const size_t plane = (size_t)H * W, n12 = (size_t)B * 12 * plane;
     float *maps, *len, *g32 = NULL;
-    double *g64 = NULL;
+    double *g64 = NULL, *maps64 = NULL, *len64 = NULL;
+    const int need64 = f64 || grad9 != NULL;      /* the double maps: the low parts of the f64 loss, and the chain rule */
     int rc = check_dims(B, S, H, W);
     size_t i;
     if (rc) return rc;
     maps = (float *)malloc(n12 * sizeof(float));
-    len = (float *)malloc((size_t)B * H * W * sizeof(float));
+    len = (float *)malloc((size_t)B * plane * sizeof(float));
+    if (need64) {
+        maps64 = (double *)malloc(n12 * sizeof(double));
+        len64 = (double *)malloc((size_t)B * plane * sizeof(double));
+    }
     g64 = grad9 ? (double *)malloc(n12 * sizeof(double)) : NULL;
-    if (!maps || !len || (grad9 && !g64)) { free(maps); free(len); free(g64); return -5; }
+    if (!maps || !len || (need64 && (!maps64 || !len64)) || (grad9 && !g64)) {
+        free(maps); free(len); free(maps64); free(len64); free(g64);
+        return -5;
+    }
     head_decode(enc, maps, len, B, H, W);
     if (f64) {
-        rc = rendering_loss_f64(maps, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, g64, NULL, NULL, 0.0, B, S, H, W);
+        double *lo = (double *)malloc(n12 * sizeof(double));
+        if (!lo) rc = -5;
+        if (!rc) {
+            head_decode_f64(enc, maps64, len64, B, H, W);
+            /* low parts: the two decodes agree to a float32 rounding, so the difference is exact and float32 + low = double */
+            for (i = 0; i < n12; ++i) lo[i] = maps64[i] - (double)maps[i];
+            rc = rendering_loss_f64(maps, lo, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, g64, NULL, NULL, 0.0, B, S, H, W);
+        }
+        free(lo);
     } else {
+        if (grad9) {
+            for (i = 0; i < n12; ++i) maps64[i] = (double)maps[i];
+            for (i = 0; i < (size_t)B * plane; ++i) len64[i] = (double)len[i];
+        }
         if (grad9) g32 = (float *)malloc(n12 * sizeof(float));
-        rc = rendering_loss_f32(maps, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, g32, NULL, NULL, 0.0, B, S, H, W);
-        if (grad9) for (i = 0; i < n12; ++i) g64[i] = (double)g32[i];
+        if (grad9 && !g32) rc = -5;
+        if (!rc)
+            rc = rendering_loss_f32(maps, NULL, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, g32, NULL, NULL, 0.0, B, S, H, W);
+        if (!rc && grad9) for (i = 0; i < n12; ++i) g64[i] = (double)g32[i];
         free(g32);
     }
-    if (!rc && grad9) head_chain(maps, len, g64, grad9, B, H, W);
-    free(maps); free(len); free(g64);
+    if (!rc && grad9) head_chain(maps64, len64, g64, grad9, B, H, W);
+    free(maps); free(len); free(maps64); free(len64); free(g64);
     return rc;
 }
 
@@ -281,7 +334,7 @@ EXPORT int svbrdf_oracle_rendering_loss_f64(const float *input, const float *tar
                                             int B, int S, int H, int W)
 {
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, 0.0f, 0.01f, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
+    return e ? e : rendering_loss_f64(input, NULL, target, scenes, xrow, eps, 0.0f, 0.01f, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
 }
 
 EXPORT int svbrdf_oracle_mixed_loss_f64(const float *input, const float *target,
@@ -291,5 +344,5 @@ EXPORT int svbrdf_oracle_mixed_loss_f64(const float *input, const float *target,
                                         int B, int S, int H, int W)
 {
     int e = check_dims(B, S, H, W);
-    return e ? e : rendering_loss_f64(input, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
+    return e ? e : rendering_loss_f64(input, NULL, target, scenes, xrow, eps, l1_weight, eps_l1, loss_out, grad_input, NULL, NULL, 0.0, B, S, H, W);
 }

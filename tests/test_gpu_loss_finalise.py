@@ -9,7 +9,8 @@ tail word.  Nothing is read back, so every grid shape has to come out right from
   * the scratch is all zero after every call, a call with a NaN map included;
   * two identical calls give bitwise equal loss and gradient (integer addition: the arrival order cannot matter);
   * the clean call after a non-finite one equals the clean reference bitwise (the sticky flag left with the tail word);
-  * the same for the forward-only kernels (want_grad=False: another translation unit, same epilogue) and for MixedLoss;
+  * the same for the forward-only kernels (want_grad=False: another translation unit, same epilogue), for MixedLoss and
+    for the head-fused MixedLoss;
   * the loss of the small grids against the C oracle: a finisher that dropped a slot or fired early would be off by 1/64 or more.
 """
 import numpy as np
@@ -136,20 +137,31 @@ def test_forward_only_call(dev, native, name):
     _scratch_is_zero(native)
 
 
-@pytest.mark.parametrize("name", ["65_workgroups", "config_2"])
-def test_mixed_loss_call(dev, native, name):
+@pytest.mark.parametrize("name,head", [pytest.param("65_workgroups", False, id="65_workgroups"),
+                                       pytest.param("config_2", False, id="config_2"),
+                                       pytest.param("65_workgroups", True, id="65_workgroups-head"),
+                                       pytest.param("config_2", True, id="config_2-head")])
+def test_mixed_loss_call(dev, native, oracle, name, head):
+    """head=True: the same grids through the head-fused kernels ([B,9,H,W] encoded input, tests/head_checks.py `interior`)"""
     inp, tgt, table = _case(name, dev)
+    if head:
+        import head_checks
+        inp = head_checks.interior(8150 + sorted(GRIDS).index(name), inp.shape[0], inp.shape[2])
     d_in, d_tg = _t(inp, dev), _t(tgt, dev)
-    l0, g0 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1)
+    l0, g0 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1, head=head)
     _scratch_is_zero(native)
     l0, g0 = l0.item(), _np(g0)
-    assert np.isfinite(l0) and np.isfinite(g0).all()
-    assert l0 > native.rendering_loss(d_in, d_tg, table)[0].item()       # the L1 part is in the sum
-    l1, g1 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1)
+    assert np.isfinite(l0) and np.isfinite(g0).all() and g0.shape == inp.shape
+    assert l0 > native.rendering_loss(d_in, d_tg, table, head=head)[0].item()       # the L1 part is in the sum
+    if head and GRIDS[name][5] <= 65:
+        ref_l, _ = oracle.head_loss(inp, tgt, _np(table), 0.1, want_grad=False)
+        print("[loss-finalise] %s head: loss %.9g, oracle %.9g" % (name, l0, ref_l))
+        assert_loss_close(l0, ref_l, name + " head")
+    l1, g1 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1, head=head)
     assert l1.item() == l0 and np.array_equal(_np(g1), g0)
-    ln, _ = native.rendering_loss(d_in, _t(_with_nan(tgt), dev), table, l1_weight=0.1)
+    ln, _ = native.rendering_loss(d_in, _t(_with_nan(tgt), dev), table, l1_weight=0.1, head=head)
     assert np.isnan(ln.item())
     _scratch_is_zero(native)
-    l2, g2 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1)
+    l2, g2 = native.rendering_loss(d_in, d_tg, table, l1_weight=0.1, head=head)
     _scratch_is_zero(native)
     assert l2.item() == l0 and np.array_equal(_np(g2), g0)
