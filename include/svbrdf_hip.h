@@ -202,6 +202,28 @@ SVBRDF_API int svbrdf_photo_loss_fwd_bwd_host_scenes(const float *input, const f
                                                      void *workspace, size_t workspace_bytes, int B, int S, int H,
                                                      int W, void *stream);
 
+/* The fused photo loss with the network head folded in: svbrdf_photo_loss_fwd_bwd(decode(encoded9), ...) in ONE launch,
+ *   loss_out[0]   = mean_{b,s,c,i,j} | log(render(scene[b,s], decode(encoded9[b])) + eps) - log(photos[b,s] + eps) |
+ *   grad_encoded9 = d loss / d encoded9 ([B,9,H,W], upstream gradient 1.0), or NULL for forward-only (same loss bitwise).
+ * `encoded9` [B,9,H,W] is the generator's output after tanh, channel layout and decode exactly those of
+ * svbrdf_head_loss_fwd_bwd (models.py:338-346); defined for any finite value, no clamp of its own.  What training or
+ * fine-tuning the network against photographs needs: (9 + 3 S + 9) * 4 bytes per pixel, no 12-channel map tensor, no
+ * elementwise launches of the head.  Decoded roughness is one channel repeated: the tied scene loop only.  Everything else
+ * is svbrdf_photo_loss_fwd_bwd's: a NaN or infinity in any of the 9 channels or in `photos`, or a photo value at or below
+ * -eps, gives NaN with the scratch left zeroed; equal operands give term 0 and gradient 0; bitwise reproducible; the
+ * same error codes before any launch, alignment rule, eps range, workspace and `_host_scenes` limit.
+ * ADDED TO ABI VERSION 8 WITHOUT A BUMP (a backward-compatible addition: nothing existing changed).  A caller that may meet
+ * an older build of version 8 detects the two entry points by symbol presence (dlsym / hasattr). */
+SVBRDF_API int svbrdf_head_photo_loss_fwd_bwd(const float *encoded9, const float *photos, const float *scenes,
+                                              const float *xrow, float eps, float *loss_out, float *grad_encoded9,
+                                              void *workspace, size_t workspace_bytes, int B, int S, int H, int W,
+                                              void *stream);
+SVBRDF_API int svbrdf_head_photo_loss_fwd_bwd_host_scenes(const float *encoded9, const float *photos,
+                                                          const float *scenes_host, const float *xrow, float eps,
+                                                          float *loss_out, float *grad_encoded9, void *workspace,
+                                                          size_t workspace_bytes, int B, int S, int H, int W,
+                                                          void *stream);
+
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd
  * wrapper to apply the upstream gradient of the loss (the chain rule through

@@ -79,7 +79,11 @@ def _load():
             getattr(lib, name).argtypes = lib.svbrdf_mixed_loss_fwd_bwd.argtypes
             getattr(lib, name).restype = ctypes.c_int
         lib.svbrdf_host_scenes_max_rows.restype = ctypes.c_int
-        for name in ("svbrdf_photo_loss_fwd_bwd", "svbrdf_photo_loss_fwd_bwd_host_scenes"):
+        for name in ("svbrdf_photo_loss_fwd_bwd", "svbrdf_photo_loss_fwd_bwd_host_scenes",
+                     "svbrdf_head_photo_loss_fwd_bwd", "svbrdf_head_photo_loss_fwd_bwd_host_scenes"):
+            if not hasattr(lib, name):      # the head entries joined ABI version 8 without a bump: an older build lacks them
+                raise NativeLibraryError("%s lacks %s (a build of ABI version 8 older than this binding) -- rebuild"
+                                         % (_SO, name))
             getattr(lib, name).argtypes = lib.svbrdf_rendering_loss_fwd_bwd.argtypes
             getattr(lib, name).restype = ctypes.c_int
         lib.svbrdf_scale_inplace.argtypes = [_fp, _fp, ctypes.c_size_t, _fp]
@@ -176,12 +180,12 @@ class _on_device:
             self.ctx.__exit__(*a)
 
 
-def _dims(maps, scenes):
+def _dims(maps, scenes, channels=12):
     """-> (B, S, H, W, shared): `scenes` is [B,S,9], or [S,9] = the same S scenes for every map (host tables only)"""
     if not isinstance(scenes, torch.Tensor):
         raise TypeError("scenes must be a torch.Tensor")
-    if maps.dim() != 4 or maps.shape[1] != 12:
-        raise ValueError("maps must be [B,12,H,W], got %s" % (tuple(maps.shape),))
+    if maps.dim() != 4 or maps.shape[1] != channels:
+        raise ValueError("maps must be [B,%d,H,W], got %s" % (channels, tuple(maps.shape)))
     B, _, H, W = maps.shape
     if H != W:
         raise ValueError("H must equal W (got %dx%d): the reference transposes the x grid, renderers.py:75" % (H, W))
@@ -528,11 +532,13 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
     return loss, grad
 
 
-def photo_loss(input, photos, scenes, eps=0.1, want_grad=True):
+def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False):
     """Fused photo loss (svbrdf_photo_loss_fwd_bwd*): mean |log(render(scenes[b,s], input[b]) + eps) - log(photos[b,s] + eps)|
     and d loss/d input in ONE launch.  input [B,12,H,W] and photos [B,S,3,H,W] device fp32; scenes [B,S,9] fp32 on the
     maps' device, or on the HOST (at most host_scenes_max_rows() rows ride in the launch's argument block, a larger table
-    is uploaded).  Returns (loss [1] device tensor, grad or None)."""
+    is uploaded).  With head=True `input` is the generator's [B,9,H,W] post-tanh output, the network head is decoded in
+    the kernel (svbrdf_head_photo_loss_fwd_bwd*) and the gradient has its 9 channels.  Returns (loss [1] device tensor,
+    grad or None)."""
     _require_device_f32(input, "input")
     _require_device_f32(photos, "photos")
     host_scenes = isinstance(scenes, torch.Tensor) and not scenes.is_cuda
@@ -546,7 +552,7 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True):
     if photos.device != input.device or (not host_scenes and scenes.device != input.device):
         raise ValueError("input, photos and scenes must be on the same device")
     input, photos, scenes = input.contiguous(), photos.contiguous(), scenes.contiguous()
-    B, S, H, W, shared = _dims(input, scenes)
+    B, S, H, W, shared = _dims(input, scenes, channels=9 if head else 12)
     if shared:
         raise ValueError("the loss needs one scene row per photo: scenes must be [B,S,9]")
     if tuple(photos.shape) != (B, S, 3, H, W):
@@ -556,7 +562,7 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True):
     ws = _workspace(input.device, lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
     loss = torch.empty(1, dtype=torch.float32, device=input.device)
     grad = torch.empty_like(input) if want_grad else None
-    entry = "svbrdf_photo_loss_fwd_bwd_host_scenes" if host_scenes else "svbrdf_photo_loss_fwd_bwd"
+    entry = ("svbrdf_head_photo_loss_fwd_bwd" if head else "svbrdf_photo_loss_fwd_bwd") + ("_host_scenes" if host_scenes else "")
     hook = _launch_hook
     with _on_device(input.device):
         if hook is not None:

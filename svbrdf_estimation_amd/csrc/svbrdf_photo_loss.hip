@@ -208,7 +208,10 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
 }
 
 // One thread = one pixel, all S renders of it; workgroup = 256 pixels of one batch item (as K3).
-template <bool WITH_GRAD, bool EARLY_COORDS>
+// HEAD: `input` is the generator's [B,9,H,W] post-tanh output and `grad_input` its gradient: the network head
+// (decode_head / head_bwd, K3's own: svbrdf_head_loss_fwd_bwd) is folded in, 9 planes in and 9 out instead of 12 and 12.
+// Decoded roughness is one channel repeated, so only the tied scene loop is instantiated for it.
+template <bool WITH_GRAD, bool EARLY_COORDS, bool HEAD = false>
 __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input, const float *__restrict__ photos,
                                                 const float *__restrict__ scenes, const float *__restrict__ xrow,
                                                 float eps, float inv_count, double loss_scale, float fixed_scale,
@@ -228,6 +231,8 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
     if (active) {
         Maps in;
         Grad acc;
+        [[maybe_unused]] Head head;
+        [[maybe_unused]] float head_chk = 0.0f;
         // pixel coordinates issued in front of the plane loads (by-value-table kernels, power-of-two width): see
         // rendering_loss_body
         [[maybe_unused]] float x_early = 0.0f, y_early = 0.0f;
@@ -239,9 +244,20 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
             y_early = xrow[p32 >> sh];
             __builtin_amdgcn_sched_barrier(0);
         }
-        load_maps_k3(input + (size_t)b * 12 * plane, plane, pix, in);
+        if (HEAD) {
+            float e[9];
+            const PlaneBuf pb = plane_buf(input + (size_t)b * 9 * plane, 9, plane, pix);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) e[k] = plane_load(pb, k);
+            head = decode_head(e, in);
+            // the guard below, from the encoded values that feed the normal and the roughness (each on its own: a sum
+            // of large finite values must not overflow into a NaN report)
+            head_chk = ((e[0] - e[0]) + (e[1] - e[1])) + (e[5] - e[5]);
+        } else {
+            load_maps_k3(input + (size_t)b * 12 * plane, plane, pix, in);
+        }
         zero_grad(acc);
-        const bool tied = tied_roughness(in);
+        const bool tied = HEAD || tied_roughness(in);
         const MapK mi = prepare<WITH_GRAD>(in);
         float x[1], y;
         if (early_coords) {
@@ -258,17 +274,24 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
             // a NaN or infinite normal / roughness value would vanish in the clamps (v_max returns the other operand):
             // t - t is 0 for finite t and NaN otherwise, added to the pixel's x coordinate (rendering_loss_body).  Diffuse,
             // specular and the photo values propagate through the arithmetic by themselves.
-            const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
-            x[0] += chk - chk;
+            if (HEAD) {
+                x[0] += head_chk;
+            } else {
+                const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
+                x[0] += chk - chk;
+            }
         }
         const float *__restrict__ scp = scenes + (size_t)b * S * 9;
         const float *__restrict__ pp = photos + (size_t)b * S * 3 * plane;
         constexpr int kDefer = WITH_GRAD ? 7 : 0;
-        if (__all(tied))     // wave-uniform
+        if (HEAD || __all(tied))     // wave-uniform
             lsum = photo_scene_loop<1, WITH_GRAD, kDefer>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc);
         else
             lsum = photo_scene_loop<3, WITH_GRAD, kDefer & 3>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc);
-        if (WITH_GRAD) store_grads_k3(grad_input + (size_t)b * 12 * plane, plane, pix, acc);
+        if (WITH_GRAD) {
+            if (HEAD) store_pixel_grad<true>(head, acc, grad_input, b, plane, pix);
+            else store_grads_k3(grad_input + (size_t)b * 12 * plane, plane, pix, acc);
+        }
     }
     {
         __shared__ float wave_part[kLossThreads / 64];
@@ -317,7 +340,32 @@ __global__ SVBRDF_PHOTO_LOSS_ATTRS void k_photo_loss_inl([[maybe_unused]] const 
                                      loss_out, S, H, W);
 }
 
-template <bool G>
+// the head variants (svbrdf_head_photo_loss_fwd_bwd*): `encoded9` [B,9,H,W] in, its gradient out
+template <bool WITH_GRAD>
+__global__ SVBRDF_PHOTO_LOSS_ATTRS void k_head_photo(const float *__restrict__ encoded9, const float *__restrict__ photos,
+                                                     const float *__restrict__ scenes, const float *__restrict__ xrow,
+                                                     float eps, float inv_count, double loss_scale, float fixed_scale,
+                                                     float *__restrict__ grad_encoded9, unsigned long long *__restrict__ ws,
+                                                     float *__restrict__ loss_out, int S, int H, int W)
+{
+    photo_loss_body<WITH_GRAD, false, true>(encoded9, photos, scenes, xrow, eps, inv_count, loss_scale, fixed_scale,
+                                            grad_encoded9, ws, loss_out, S, H, W);
+}
+
+template <bool WITH_GRAD>
+__global__ SVBRDF_PHOTO_LOSS_ATTRS void k_head_photo_inl([[maybe_unused]] const SceneBlock table,
+                                                         const float *__restrict__ encoded9, const float *__restrict__ photos,
+                                                         const float *__restrict__ xrow, float eps, float inv_count,
+                                                         double loss_scale, float fixed_scale,
+                                                         float *__restrict__ grad_encoded9, unsigned long long *__restrict__ ws,
+                                                         float *__restrict__ loss_out, int S, int H, int W)
+{
+    const float *__restrict__ rows = (const float *)__builtin_amdgcn_kernarg_segment_ptr();
+    photo_loss_body<WITH_GRAD, true, true>(encoded9, photos, rows, xrow, eps, inv_count, loss_scale, fixed_scale,
+                                           grad_encoded9, ws, loss_out, S, H, W);
+}
+
+template <bool G, bool HEAD>
 void launch_photo(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st, const float *input, const float *photos,
                   const float *scenes, const float *xrow, float eps, float inv_count, double loss_scale, float fixed_scale,
                   float *grad_input, unsigned long long *ws, float *loss_out, int B, int S, int H, int W)
@@ -325,17 +373,26 @@ void launch_photo(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st
     if (rows) {
         SceneBlock block_arg;      // only the first B*S rows are ever read
         std::memcpy(block_arg.v, rows, (size_t)B * S * 9 * sizeof(float));
-        hipLaunchKernelGGL((k_photo_loss_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos, xrow,
-                           eps, inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+        if (HEAD)
+            hipLaunchKernelGGL((k_head_photo_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos,
+                               xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+        else
+            hipLaunchKernelGGL((k_photo_loss_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos,
+                               xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
     } else {
-        hipLaunchKernelGGL((k_photo_loss<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, scenes, xrow, eps,
-                           inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+        if (HEAD)
+            hipLaunchKernelGGL((k_head_photo<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, scenes, xrow, eps,
+                               inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+        else
+            hipLaunchKernelGGL((k_photo_loss<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, scenes, xrow, eps,
+                               inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
     }
 }
 
 // argument checks, grid, fixed-point scale: those of svbrdf_rendering_loss_fwd_bwd (loss_impl in svbrdf_kernels.hip).  The
 // launch is counted by the main unit's counter through launch_status() (svbrdf_internal_launch_status).
-int photo_impl(const char *who, bool scenes_on_host, const float *input, const float *photos, const float *scenes,
+// `head`: input and grad_input are the 9 encoded planes (svbrdf_head_photo_loss_fwd_bwd*), same checks
+int photo_impl(const char *who, bool scenes_on_host, bool head, const float *input, const float *photos, const float *scenes,
                const float *xrow, float eps, float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes,
                int B, int S, int H, int W, void *stream)
 {
@@ -368,12 +425,17 @@ int photo_impl(const char *who, bool scenes_on_host, const float *input, const f
     hipStream_t st = static_cast<hipStream_t>(stream);
     unsigned long long *ws = static_cast<unsigned long long *>(workspace);
     const float *rows = scenes_on_host ? scenes : nullptr;
-    if (grad_input)
-        launch_photo<true>(rows, grid, lds_bytes, st, input, photos, scenes, xrow, eps, inv_count, loss_scale, fixed_scale,
-                           grad_input, ws, loss_out, B, S, H, W);
-    else
-        launch_photo<false>(rows, grid, lds_bytes, st, input, photos, scenes, xrow, eps, inv_count, loss_scale, fixed_scale,
-                            grad_input, ws, loss_out, B, S, H, W);
+#define SVBRDF_LAUNCH_PHOTO(G, HD)                                                                                      \
+    launch_photo<G, HD>(rows, grid, lds_bytes, st, input, photos, scenes, xrow, eps, inv_count, loss_scale, fixed_scale, \
+                        grad_input, ws, loss_out, B, S, H, W)
+    if (head) {
+        if (grad_input) SVBRDF_LAUNCH_PHOTO(true, true);
+        else SVBRDF_LAUNCH_PHOTO(false, true);
+    } else {
+        if (grad_input) SVBRDF_LAUNCH_PHOTO(true, false);
+        else SVBRDF_LAUNCH_PHOTO(false, false);
+    }
+#undef SVBRDF_LAUNCH_PHOTO
     return launch_status(who);
 }
 
@@ -385,7 +447,7 @@ int svbrdf_photo_loss_fwd_bwd(const float *input, const float *photos, const flo
                               float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes, int B, int S,
                               int H, int W, void *stream)
 {
-    return photo_impl("photo_loss", false, input, photos, scenes, xrow, eps, loss_out, grad_input, workspace,
+    return photo_impl("photo_loss", false, false, input, photos, scenes, xrow, eps, loss_out, grad_input, workspace,
                       workspace_bytes, B, S, H, W, stream);
 }
 
@@ -393,8 +455,26 @@ int svbrdf_photo_loss_fwd_bwd_host_scenes(const float *input, const float *photo
                                           const float *xrow, float eps, float *loss_out, float *grad_input,
                                           void *workspace, size_t workspace_bytes, int B, int S, int H, int W, void *stream)
 {
-    return photo_impl("photo_loss_host_scenes", true, input, photos, scenes_host, xrow, eps, loss_out, grad_input,
+    return photo_impl("photo_loss_host_scenes", true, false, input, photos, scenes_host, xrow, eps, loss_out, grad_input,
                       workspace, workspace_bytes, B, S, H, W, stream);
+}
+
+// The network head folded in (added to ABI version 8 without a bump: see include/svbrdf_hip.h)
+int svbrdf_head_photo_loss_fwd_bwd(const float *encoded9, const float *photos, const float *scenes, const float *xrow,
+                                   float eps, float *loss_out, float *grad_encoded9, void *workspace,
+                                   size_t workspace_bytes, int B, int S, int H, int W, void *stream)
+{
+    return photo_impl("head_photo_loss", false, true, encoded9, photos, scenes, xrow, eps, loss_out, grad_encoded9,
+                      workspace, workspace_bytes, B, S, H, W, stream);
+}
+
+int svbrdf_head_photo_loss_fwd_bwd_host_scenes(const float *encoded9, const float *photos, const float *scenes_host,
+                                               const float *xrow, float eps, float *loss_out, float *grad_encoded9,
+                                               void *workspace, size_t workspace_bytes, int B, int S, int H, int W,
+                                               void *stream)
+{
+    return photo_impl("head_photo_loss_host_scenes", true, true, encoded9, photos, scenes_host, xrow, eps, loss_out,
+                      grad_encoded9, workspace, workspace_bytes, B, S, H, W, stream);
 }
 
 }  // extern "C"

@@ -263,14 +263,15 @@ class RenderingLoss(nn.Module):
 
 
 class _FusedPhotoLoss(torch.autograd.Function):
-    """The fused photo-loss kernel behind autograd: it already produces d loss/d input for upstream gradient 1."""
+    """The fused photo-loss kernel behind autograd: it already produces d loss/d input for upstream gradient 1.
+    ``head``: ``input`` is the generator's [B,9,H,W] post-tanh output, decoded in the kernel (HeadPhotoLoss)."""
 
     @staticmethod
-    def forward(ctx, input, photos, scenes, eps):
+    def forward(ctx, input, photos, scenes, eps, head):
         need_in = ctx.needs_input_grad[0]
         ctx.save_for_backward(input, photos)        # (for backward(create_graph=True) only: references, no copies)
-        ctx.second_order = (scenes if scenes.is_cuda else scenes.detach().clone(), float(eps))
-        loss, ctx.grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in)
+        ctx.second_order = (scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head))
+        loss, ctx.grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head)
         return loss.view(())
 
     @staticmethod
@@ -279,11 +280,12 @@ class _FusedPhotoLoss(torch.autograd.Function):
             # backward(create_graph=True): the kernel's gradient is a constant to autograd; differentiate the composed
             # definition instead (same scenes), in float64 like the other fused losses do
             input, photos = ctx.saved_tensors
-            scenes, eps = ctx.second_order
+            scenes, eps, head = ctx.second_order
             with torch.enable_grad():
-                loss = composed_photo_loss(input.to(torch.float64), photos, scenes, eps)
+                x = input.to(torch.float64)
+                loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes, eps)
                 g, = torch.autograd.grad(loss, [input], grad_loss.to(torch.float64).reshape(()), create_graph=True)
-            return g.to(input.dtype), None, None, None
+            return g.to(input.dtype), None, None, None, None
         if ctx.grad is None:
             raise RuntimeError("Trying to backward through the fused photo loss a second time: its gradient buffer was "
                                "handed to the first backward.  Specify retain_graph=True for the first one.")
@@ -293,9 +295,9 @@ class _FusedPhotoLoss(torch.autograd.Function):
         if not keep:
             ctx.grad = None
         if _is_unit_gradient(grad_loss):     # _PhotoLossTensor.backward's cached 1.0: nothing to scale, nothing to launch
-            return (grad.clone() if keep else grad), None, None, None
+            return (grad.clone() if keep else grad), None, None, None, None
         scale = grad_loss.detach().to(torch.float32).reshape(1)
-        return _native.scale_inplace_(grad.clone() if keep else grad, scale), None, None, None
+        return _native.scale_inplace_(grad.clone() if keep else grad, scale), None, None, None, None
 
 
 class _PhotoLossTensor(torch.Tensor):
@@ -360,11 +362,11 @@ class PhotoLoss(nn.Module):
         return RenderingLoss(self.renderer).uses_fused_kernel()
 
     @staticmethod
-    def _check(input, photos):
+    def _check(input, photos, channels=12):
         if not isinstance(input, torch.Tensor) or not isinstance(photos, torch.Tensor):
             raise TypeError("input and photos must be tensors")
-        if input.dim() != 4 or input.shape[1] != 12:
-            raise ValueError("input must be [B,12,H,W]")
+        if input.dim() != 4 or input.shape[1] != channels:
+            raise ValueError("input must be [B,%d,H,W]" % channels)
         if photos.dim() == 4:
             photos = photos.unsqueeze(1)                # [B,3,H,W]: one photo per item
         if photos.dim() != 5 or photos.shape[0] != input.shape[0] or photos.shape[2] != 3 \
@@ -416,7 +418,7 @@ class PhotoLoss(nn.Module):
             return composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps)
         if input.dtype != torch.float32 or photos.dtype != torch.float32:
             raise TypeError("input and photos must be float32 or float64 (got %s, %s)" % (input.dtype, photos.dtype))
-        loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps))
+        loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps), False)
         return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
 
     def _forward_plugin(self, input, photos, scenes):
@@ -474,3 +476,41 @@ class FusedHeadLoss(nn.Module):
                                                       eps_l1=self.l1_loss.epsilon_l1, head=True)
         maps = decode_head(encoded9)
         return self.l1_weight * self.l1_loss(maps, target) + self.rendering_loss(maps, target)
+
+
+class HeadPhotoLoss(nn.Module):
+    """``PhotoLoss(renderer, eps)(decode_head(encoded9), photos, scenes)`` in one kernel: what training or fine-tuning the
+    network against photographs needs.  ``forward(encoded9 [B,9,H,W], photos [B,S,3,H,W] or [B,3,H,W] (S = 1), scenes)``
+    with ``encoded9`` the generator's output after tanh (any finite value: no clamp of its own) and photos / scenes as
+    ``PhotoLoss.forward`` takes them; a 0-dim tensor, differentiable w.r.t. ``encoded9`` only.
+
+    With this package's ``LocalRenderer`` and float32 tensors on a ROCm device the head decode, the renderings, the loss
+    and the gradient w.r.t. the NINE encoded channels are ONE fused HIP kernel (csrc/svbrdf_photo_loss.hip: 9 planes in,
+    9 out, no 12-channel map tensor, none of the head's elementwise launches).  Any other renderer object, float64 on
+    either side and ``backward(create_graph=True)`` take the composed definition above, which is also the specification
+    of the fused path."""
+
+    def __init__(self, renderer, eps=0.1):
+        super().__init__()
+        self.renderer = renderer
+        self.eps = eps
+
+    def uses_fused_kernel(self):
+        return RenderingLoss(self.renderer).uses_fused_kernel()
+
+    def forward(self, encoded9, photos, scenes):
+        photos = PhotoLoss._check(encoded9, photos, channels=9)
+        composed = PhotoLoss(self.renderer, self.eps)
+        if not self.uses_fused_kernel():
+            return composed(decode_head(encoded9), photos, scenes)
+        table = PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
+        if not encoded9.is_cuda:
+            raise _native.NativeLibraryError("HeadPhotoLoss with the MI355X LocalRenderer needs tensors on a ROCm device "
+                                             "(got %s); there is no CPU fallback" % encoded9.device)
+        if encoded9.dtype == torch.float64 or photos.dtype == torch.float64:
+            # double on either side: promoted in front of the decode, as the reference's torch ops would
+            return composed(decode_head(encoded9.to(torch.float64)), photos, table)
+        if encoded9.dtype != torch.float32 or photos.dtype != torch.float32:
+            raise TypeError("encoded9 and photos must be float32 or float64 (got %s, %s)" % (encoded9.dtype, photos.dtype))
+        loss = _FusedPhotoLoss.apply(encoded9, photos, table, float(self.eps), True)
+        return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss

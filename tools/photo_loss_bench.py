@@ -1,6 +1,6 @@
 """The fused photo loss against K3 and against the composed form, one process, one box (profiles/r09_photo_loss.txt).
 
-    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...]
+    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...] [--head]
 
 At the configuration-2 shape (B = 8, 256 x 256, S = 9, scene table by value, six batches rotating beyond the 256 MB
 Infinity Cache, as bench.py does) it prints the event-timed median per launch of
@@ -12,6 +12,11 @@ the fraction of 8 TB/s at the algorithmic bytes (12 + 3 S + 12) * 4 * H * W * B,
 pixel-render of the scene loops from tools/isa_stats.py (where hipcc is present).  The method is that of
 tests/test_gpu_photo_loss.py::test_photo_loss_is_no_slower_than_k3, which it imports: launches enqueued behind a spinning
 wave so that the stream runs them back to back, an event between every two, medians of interleaved rounds.
+
+--head: the head leg instead -- the head-fused photo loss (svbrdf_head_photo_loss_fwd_bwd_host_scenes: the generator's
+[B,9,H,W] output in, its gradient out), the 12-channel photo kernel on the decoded maps and the unfused composition
+PhotoLoss(decode_head(x)) forward + backward through autograd, same shape, one process
+(tests/head_photo_checks.py::measure_head_photo_loss, the method of tests/test_gpu_head_photo_loss.py's speed test).
 
 --variants: other builds of the library (tools/build_variant.sh, e.g. the photo-loss unit compiled with another of the
 Makefile's scheduler sets), each measured in a child process of its own on this box, interleaved with the shipped build.
@@ -40,13 +45,13 @@ def isa_lines():
     subprocess.check_call(cmd, cwd=csrc, stderr=subprocess.DEVNULL)
     text, lines = open(out).read(), []
     for k in sorted(isa_stats.kernels(text)):
-        if "k_photo_loss" not in k:
+        if "k_photo_loss" not in k and "k_head_photo" not in k:
             continue
         _, meta, _, loops, _, _ = isa_stats.analyse(text, k)
         per = 2 if "ILb1E" in k else 1
         for c in sorted((c for c in loops if c["trans"]), key=lambda c: c["valu"]):
             lines.append("%-24s %s loop: %5.1f VALU, %4.1f transcendentals per pixel-render; %s VGPRs, scratch %s" % (
-                ("by-value" if "_inl" in k else "device") + (" fwd+bwd" if per == 2 else " fwd only"),
+                ("head " if "k_head_photo" in k else "") + ("by-value" if "_inl" in k else "device") + (" fwd+bwd" if per == 2 else " fwd only"),
                 "tied  " if c["trans"] / per < 14 else "untied", c["valu"] / per, c["trans"] / per, meta.get("NumVgprs"),
                 meta.get("ScratchSize")))
     return lines
@@ -75,13 +80,17 @@ def measure_composed(dev, native, sets=6, n=30, rounds=3):
                             for _ in range(rounds)]))
 
 
-def child():
+def child(head=False):
     import torch
     from svbrdf_estimation_amd import _native
     import test_gpu_photo_loss as T
     dev = torch.device("cuda:0")
-    res = T.measure_photo_loss_against_k3(dev, _native)
-    res["composed_us"] = measure_composed(dev, _native)
+    if head:
+        import head_photo_checks
+        res = head_photo_checks.measure_head_photo_loss(dev, _native)
+    else:
+        res = T.measure_photo_loss_against_k3(dev, _native)
+        res["composed_us"] = measure_composed(dev, _native)
     res["library"] = _native.library_path()
     print("RESULT " + json.dumps(res))
 
@@ -91,10 +100,11 @@ def main():
     ap.add_argument("--out", default=None, help="also write the report to this file")
     ap.add_argument("--variants", nargs="*", default=[], metavar="TAG=LIB")
     ap.add_argument("--passes", type=int, default=1, help="how often the builds are measured in turn")
+    ap.add_argument("--head", action="store_true", help="the head leg: fused head photo loss, 12-channel kernel, unfused composition")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.child:
-        return child()
+        return child(args.head)
     builds = [("shipped", None)] + [tuple(v.split("=", 1)) for v in args.variants]
     rows = []
     for p in range(args.passes):
@@ -102,7 +112,7 @@ def main():
             env = dict(os.environ)
             if lib:
                 env["SVBRDF_HIP_LIB"] = os.path.abspath(lib)
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], env=env, text=True, timeout=300,
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + (["--head"] if args.head else []), env=env, text=True, timeout=300,
                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
             line = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")]
             if out.returncode != 0 or not line:
@@ -110,15 +120,26 @@ def main():
                 raise SystemExit("measurement of build %r failed (exit status %s): nothing more is started" % (tag, out.returncode))
             rows.append((tag, p, json.loads(line[0][7:])))
     B, H, S = 8, 256, 9
-    lines = ["# tools/photo_loss_bench.py on %s; B = %d, %d x %d, S = %d, scene table by value, %d rotating batches" % (
-        rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
-        "# medians of event-timed launches (us per launch); algorithmic bytes of the photo loss (12 + 3 S + 12) * 4 * H * W * B = %.1f MB"
-        % ((12 + 3 * S + 12) * 4 * H * H * B / 1e6)]
-    for tag, p, r in rows:
-        lines.append("%-16s pass %d: photo loss %7.2f  K3 %7.2f  composed K1 + torch + K2 %8.2f   photo loss = %.3f of 8 TB/s, "
-                     "%.2fx K3, %.1fx composed   rounds %s" % (tag, p, r["photo_loss_us"], r["k3_us"], r["composed_us"],
-                                                             r["photo_loss_frac_of_8TBps"], r["k3_us"] / r["photo_loss_us"],
-                                                             r["composed_us"] / r["photo_loss_us"], r["rounds"]))
+    if args.head:
+        lines = ["# tools/photo_loss_bench.py --head on %s; B = %d, %d x %d, S = %d, scene table by value, %d rotating batches" % (
+            rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
+            "# medians of event-timed steps (us per step); algorithmic bytes of the head photo loss (9 + 3 S + 9) * 4 * H * W * B = %.1f MB"
+            % ((9 + 3 * S + 9) * 4 * H * H * B / 1e6)]
+        for tag, p, r in rows:
+            lines.append("%-16s pass %d: head photo loss %7.2f  12-channel photo loss %7.2f  unfused PhotoLoss(decode_head(x)) fwd + bwd "
+                         "%8.2f   head photo loss = %.3f of 8 TB/s, %.1fx the composition   rounds %s" % (
+                             tag, p, r["head_photo_us"], r["photo12_us"], r["composition_us"], r["head_photo_frac_of_8TBps"],
+                             r["composition_us"] / r["head_photo_us"], r["rounds"]))
+    else:
+        lines = ["# tools/photo_loss_bench.py on %s; B = %d, %d x %d, S = %d, scene table by value, %d rotating batches" % (
+            rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
+            "# medians of event-timed launches (us per launch); algorithmic bytes of the photo loss (12 + 3 S + 12) * 4 * H * W * B = %.1f MB"
+            % ((12 + 3 * S + 12) * 4 * H * H * B / 1e6)]
+        for tag, p, r in rows:
+            lines.append("%-16s pass %d: photo loss %7.2f  K3 %7.2f  composed K1 + torch + K2 %8.2f   photo loss = %.3f of 8 TB/s, "
+                         "%.2fx K3, %.1fx composed   rounds %s" % (tag, p, r["photo_loss_us"], r["k3_us"], r["composed_us"],
+                                                                 r["photo_loss_frac_of_8TBps"], r["k3_us"] / r["photo_loss_us"],
+                                                                 r["composed_us"] / r["photo_loss_us"], r["rounds"]))
     lines += ["# scene loops of the shipped source (hipcc -S with the Makefile's flags, tools/isa_stats.py); K3's tied loop: 301 VALU per pixel-render"]
     lines += isa_lines()
     text = "\n".join(lines) + "\n"
