@@ -39,7 +39,46 @@ def library_path():
     return _SO
 
 
-_fp = ctypes.c_void_p
+_fp, _int, _float, _size, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_ulonglong
+_DIMS = [_int] * 4 + [_fp]                                            # B, S (or R), H, W, stream
+_LOSS = [_fp] * 4 + [_float] + [_fp] * 3 + [_size] + _DIMS            # input, other, scenes, xrow, eps, loss, grad, ws, bytes
+_LOSS_L1 = [_fp] * 4 + [_float] * 3 + [_fp] * 3 + [_size] + _DIMS     # ... eps, l1_weight, eps_l1 ...
+_INPUTS = [_fp] * 3 + [_u64] * 2 + [_fp] * 2 + _DIMS
+# name -> (restype, argtypes) of every SVBRDF_API function of include/svbrdf_hip.h, applied once in _load();
+# tests/test_host_logic.py holds the lengths against the header
+SIGNATURES = {
+    "svbrdf_abi_version": (_int, []),
+    "svbrdf_last_error": (ctypes.c_char_p, []),
+    "svbrdf_make_xrow": (_int, [_fp, _int]),
+    "svbrdf_render_fwd": (_int, [_fp] * 4 + _DIMS),
+    "svbrdf_render_bwd": (_int, [_fp] * 5 + _DIMS),
+    "svbrdf_render_fwd_host_scenes": (_int, [_fp, _fp, _int, _fp, _fp] + _DIMS),
+    "svbrdf_render_bwd_host_scenes": (_int, [_fp, _fp, _int, _fp, _fp, _fp] + _DIMS),
+    "svbrdf_render_fwd_ragged": (_int, [_fp] * 5 + _DIMS),
+    "svbrdf_render_bwd_ragged": (_int, [_fp] * 6 + _DIMS),
+    "svbrdf_rendering_loss_workspace_bytes": (_size, [_int] * 4),
+    "svbrdf_rendering_loss_fwd_bwd": (_int, _LOSS),
+    "svbrdf_mixed_loss_fwd_bwd": (_int, _LOSS_L1),
+    "svbrdf_head_loss_fwd_bwd": (_int, _LOSS_L1),
+    "svbrdf_host_scenes_max_rows": (_int, []),
+    "svbrdf_mixed_loss_fwd_bwd_host_scenes": (_int, _LOSS_L1),
+    "svbrdf_head_loss_fwd_bwd_host_scenes": (_int, _LOSS_L1),
+    "svbrdf_photo_loss_fwd_bwd": (_int, _LOSS),
+    "svbrdf_photo_loss_fwd_bwd_host_scenes": (_int, _LOSS),
+    "svbrdf_head_photo_loss_fwd_bwd": (_int, _LOSS),
+    "svbrdf_head_photo_loss_fwd_bwd_host_scenes": (_int, _LOSS),
+    "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
+    "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
+    "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
+    "svbrdf_render_inputs": (_int, _INPUTS),
+    "svbrdf_render_inputs_host_scenes": (_int, _INPUTS),
+    "svbrdf_debug_copy": (_int, [_fp, _fp, _size, _fp]),
+    "svbrdf_debug_launch_count": (_u64, []),
+    "svbrdf_debug_clock_probe": (_int, [_fp, _u64, _fp]),
+    "svbrdf_render_fwd_f64": (_int, [_fp] * 4 + _DIMS),
+    "svbrdf_render_bwd_f64": (_int, [_fp] * 5 + _DIMS),
+    "svbrdf_render_bwd_jvp_f64": (_int, [_fp] * 7 + _DIMS),
+}
 
 
 def _load():
@@ -60,51 +99,14 @@ def _load():
             lib = ctypes.CDLL(_SO)
         except OSError as e:  # pragma: no cover
             raise NativeLibraryError("cannot load %s: %s" % (_SO, e))
-        lib.svbrdf_abi_version.restype = ctypes.c_int
-        lib.svbrdf_last_error.restype = ctypes.c_char_p
-        lib.svbrdf_make_xrow.argtypes = [_fp, ctypes.c_int]
-        lib.svbrdf_render_fwd.argtypes = [_fp, _fp, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-        lib.svbrdf_render_bwd.argtypes = [_fp, _fp, _fp, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-        lib.svbrdf_rendering_loss_workspace_bytes.argtypes = [ctypes.c_int] * 4
-        lib.svbrdf_rendering_loss_workspace_bytes.restype = ctypes.c_size_t
-        lib.svbrdf_rendering_loss_fwd_bwd.argtypes = (
-            [_fp, _fp, _fp, _fp, ctypes.c_float, _fp, _fp, _fp, ctypes.c_size_t] + [ctypes.c_int] * 4 + [_fp])
-        lib.svbrdf_mixed_loss_fwd_bwd.argtypes = (
-            [_fp, _fp, _fp, _fp, ctypes.c_float, ctypes.c_float, ctypes.c_float, _fp, _fp, _fp, ctypes.c_size_t]
-            + [ctypes.c_int] * 4 + [_fp])
-        lib.svbrdf_mixed_loss_fwd_bwd.restype = ctypes.c_int
-        lib.svbrdf_head_loss_fwd_bwd.argtypes = lib.svbrdf_mixed_loss_fwd_bwd.argtypes
-        lib.svbrdf_head_loss_fwd_bwd.restype = ctypes.c_int
-        for name in ("svbrdf_mixed_loss_fwd_bwd_host_scenes", "svbrdf_head_loss_fwd_bwd_host_scenes"):
-            getattr(lib, name).argtypes = lib.svbrdf_mixed_loss_fwd_bwd.argtypes
-            getattr(lib, name).restype = ctypes.c_int
-        lib.svbrdf_host_scenes_max_rows.restype = ctypes.c_int
-        for name in ("svbrdf_photo_loss_fwd_bwd", "svbrdf_photo_loss_fwd_bwd_host_scenes",
-                     "svbrdf_head_photo_loss_fwd_bwd", "svbrdf_head_photo_loss_fwd_bwd_host_scenes"):
-            if not hasattr(lib, name):      # the head entries joined ABI version 8 without a bump: an older build lacks them
-                raise NativeLibraryError("%s lacks %s (a build of ABI version 8 older than this binding) -- rebuild"
-                                         % (_SO, name))
-            getattr(lib, name).argtypes = lib.svbrdf_rendering_loss_fwd_bwd.argtypes
-            getattr(lib, name).restype = ctypes.c_int
-        lib.svbrdf_scale_inplace.argtypes = [_fp, _fp, ctypes.c_size_t, _fp]
-        lib.svbrdf_scale_inplace.restype = ctypes.c_int
-        lib.svbrdf_render_fwd_host_scenes.argtypes = [_fp, _fp, ctypes.c_int, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-        lib.svbrdf_render_bwd_host_scenes.argtypes = [_fp, _fp, ctypes.c_int, _fp, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-        for name in ("svbrdf_make_xrow", "svbrdf_render_fwd", "svbrdf_render_bwd", "svbrdf_rendering_loss_fwd_bwd",
-                     "svbrdf_render_fwd_host_scenes", "svbrdf_render_bwd_host_scenes"):
-            getattr(lib, name).restype = ctypes.c_int
-        lib.svbrdf_render_fwd_f64.argtypes = [_fp, _fp, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-        lib.svbrdf_render_bwd_f64.argtypes = [_fp, _fp, _fp, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-        lib.svbrdf_render_fwd_f64.restype = lib.svbrdf_render_bwd_f64.restype = ctypes.c_int
-        lib.svbrdf_render_bwd_jvp_f64.argtypes = [_fp] * 7 + [ctypes.c_int] * 4 + [_fp]
-        lib.svbrdf_render_bwd_jvp_f64.restype = ctypes.c_int
-        lib.svbrdf_render_inputs.argtypes = [_fp, _fp, _fp, ctypes.c_ulonglong, ctypes.c_ulonglong, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-        lib.svbrdf_render_inputs_host_scenes.argtypes = lib.svbrdf_render_inputs.argtypes
-        lib.svbrdf_render_inputs.restype = lib.svbrdf_render_inputs_host_scenes.restype = ctypes.c_int
-        lib.svbrdf_debug_copy.argtypes = [_fp, _fp, ctypes.c_size_t, _fp]
-        lib.svbrdf_debug_copy.restype = ctypes.c_int
-        lib.svbrdf_debug_launch_count.argtypes = []
-        lib.svbrdf_debug_launch_count.restype = ctypes.c_ulonglong
+        for name, (restype, argtypes) in SIGNATURES.items():
+            if not hasattr(lib, name):
+                if "photo_loss" in name:    # the photo entries joined ABI version 8 without a bump: an older build lacks them
+                    raise NativeLibraryError("%s lacks %s (a build of ABI version 8 older than this binding) -- rebuild"
+                                             % (_SO, name))
+                raise NativeLibraryError("%s does not export %s -- rebuild" % (_SO, name))
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         v = lib.svbrdf_abi_version()
         if v != ABI_VERSION:
             raise NativeLibraryError("ABI mismatch: library %d, binding %d -- rebuild" % (v, ABI_VERSION))
@@ -413,14 +415,6 @@ def _ragged_offsets(counts, B, R, device):
     return torch.tensor(off, dtype=torch.int32).to(device)
 
 
-def _ragged_binding():
-    lib = _load()
-    lib.svbrdf_render_fwd_ragged.argtypes = [_fp, _fp, _fp, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-    lib.svbrdf_render_bwd_ragged.argtypes = [_fp, _fp, _fp, _fp, _fp, _fp] + [ctypes.c_int] * 4 + [_fp]
-    lib.svbrdf_render_fwd_ragged.restype = lib.svbrdf_render_bwd_ragged.restype = ctypes.c_int
-    return lib
-
-
 def render_fwd_ragged(maps, scenes, counts):
     """K1, ragged: maps [B,12,H,W], scenes [R,9] grouped by map, counts[b] renders for map b -> [R,3,H,W]."""
     _require_device_f32(maps, "maps")
@@ -433,9 +427,9 @@ def render_fwd_ragged(maps, scenes, counts):
     off = _ragged_offsets(counts, B, R, maps.device)
     out = torch.empty((R, 3, H, W), dtype=torch.float32, device=maps.device)
     with _on_device(maps.device):
-        _check(_ragged_binding().svbrdf_render_fwd_ragged(maps.data_ptr(), scenes.data_ptr(), off.data_ptr(),
-                                                          xrow(maps.device, W).data_ptr(), out.data_ptr(), B, R, H, W,
-                                                          _stream(maps.device)), "svbrdf_render_fwd_ragged")
+        _check(_load().svbrdf_render_fwd_ragged(maps.data_ptr(), scenes.data_ptr(), off.data_ptr(),
+                                                xrow(maps.device, W).data_ptr(), out.data_ptr(), B, R, H, W,
+                                                _stream(maps.device)), "svbrdf_render_fwd_ragged")
     return out
 
 
@@ -451,43 +445,36 @@ def render_bwd_ragged(maps, scenes, counts, grad_out):
     off = _ragged_offsets(counts, B, R, maps.device)
     grad = torch.empty_like(maps)
     with _on_device(maps.device):
-        _check(_ragged_binding().svbrdf_render_bwd_ragged(maps.data_ptr(), scenes.data_ptr(), off.data_ptr(),
-                                                          xrow(maps.device, W).data_ptr(), grad_out.data_ptr(),
-                                                          grad.data_ptr(), B, R, H, W, _stream(maps.device)),
+        _check(_load().svbrdf_render_bwd_ragged(maps.data_ptr(), scenes.data_ptr(), off.data_ptr(),
+                                                xrow(maps.device, W).data_ptr(), grad_out.data_ptr(),
+                                                grad.data_ptr(), B, R, H, W, _stream(maps.device)),
                "svbrdf_render_bwd_ragged")
     return grad
 
 
-def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0, eps_l1=0.01, head=False):
-    """K3: fused rendering loss (+ d loss/d input); with l1_weight != 0 the SVBRDF L1 loss is folded
-    in (MixedLoss); with head=True `input` is the generator's [B,9,H,W] post-tanh output and the
-    network head is decoded in the kernel.  Returns (loss [1] device tensor, grad or None)."""
-    _require_device_f32(input, "input")
-    _require_device_f32(target, "target")
-    # a HOST table of at most host_scenes_max_rows() rows rides in the kernel-argument block (no upload)
-    host_scenes = isinstance(scenes, torch.Tensor) and not scenes.is_cuda
-    if host_scenes:
+def _loss_scene_table(scenes, device, what):
+    """The scene table of a fused-loss call -> (table, on_host).  A HOST fp32 [B,S,9] table of at most
+    host_scenes_max_rows() rows rides in the kernel-argument block (no upload); a larger one is uploaded; a device table
+    must live on `device` (`what`: the caller's message when it does not)."""
+    on_host = isinstance(scenes, torch.Tensor) and not scenes.is_cuda
+    if on_host:
         if scenes.dtype != torch.float32:
             raise TypeError("scenes must be float32 (got %s)" % scenes.dtype)
         if scenes.dim() == 3 and scenes.shape[0] * scenes.shape[1] > host_scenes_max_rows():
-            scenes, host_scenes = upload_scene_table(scenes, input.device), False
+            scenes, on_host = upload_scene_table(scenes, device), False
     else:
         _require_device_f32(scenes, "scenes")
-    if head:
-        if input.dim() != 4 or input.shape[1] != 9 or (input.shape[0],) + tuple(input.shape[2:]) != \
-                (target.shape[0],) + tuple(target.shape[2:]):
-            raise ValueError("head=True needs input [B,9,H,W] and target [B,12,H,W]")
-    elif input.shape != target.shape:
-        raise ValueError("input and target shapes differ: %s vs %s" % (tuple(input.shape), tuple(target.shape)))
-    if target.device != input.device or (not host_scenes and scenes.device != input.device):
-        raise ValueError("input, target and scenes must be on the same device")
-    input, target, scenes = input.contiguous(), target.contiguous(), scenes.contiguous()
-    B, S, H, W, shared = _dims(target, scenes)
-    if shared:
-        raise ValueError("the loss needs one scene table per batch item: scenes must be [B,S,9]")
+    if not on_host and scenes.device != device:
+        raise ValueError(what)
+    return scenes.contiguous(), on_host
+
+
+def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W):
+    """One launch of the fused-loss entry point `entry` (looked up on the loaded library): contiguous device tensors
+    `input` and `other` (target maps or photos), the scene table as _loss_scene_table returned it, `floats` = eps
+    (and l1_weight, eps_l1 for the entries that take them).  -> (loss [1] device tensor, grad like `input` or None)"""
     lib = _load()
-    nbytes = lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, W)
-    ws = _workspace(input.device, nbytes)
+    ws = _workspace(input.device, lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
     loss = torch.empty(1, dtype=torch.float32, device=input.device)
     grad = torch.empty_like(input) if want_grad else None
     xr = xrow(input.device, W)
@@ -495,33 +482,9 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
     with _on_device(input.device):
         if hook is not None:
             hook("begin")
-        if host_scenes:
-            entry = "svbrdf_head_loss_fwd_bwd_host_scenes" if head else "svbrdf_mixed_loss_fwd_bwd_host_scenes"
-            rc = getattr(lib, entry)(
-                input.data_ptr(), target.data_ptr(), scenes.data_ptr(), xr.data_ptr(),
-                ctypes.c_float(eps), ctypes.c_float(l1_weight), ctypes.c_float(eps_l1), loss.data_ptr(),
-                grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel() * 8, B, S, H, W,
-                _stream(input.device))
-        elif head:
-            entry = "svbrdf_head_loss_fwd_bwd"
-            rc = lib.svbrdf_head_loss_fwd_bwd(
-                input.data_ptr(), target.data_ptr(), scenes.data_ptr(), xr.data_ptr(),
-                ctypes.c_float(eps), ctypes.c_float(l1_weight), ctypes.c_float(eps_l1), loss.data_ptr(),
-                grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel() * 8, B, S, H, W,
-                _stream(input.device))
-        elif l1_weight != 0.0:
-            entry = "svbrdf_mixed_loss_fwd_bwd"
-            rc = lib.svbrdf_mixed_loss_fwd_bwd(
-                input.data_ptr(), target.data_ptr(), scenes.data_ptr(), xr.data_ptr(),
-                ctypes.c_float(eps), ctypes.c_float(l1_weight), ctypes.c_float(eps_l1), loss.data_ptr(),
-                grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel() * 8, B, S, H, W,
-                _stream(input.device))
-        else:
-            entry = "svbrdf_rendering_loss_fwd_bwd"
-            rc = lib.svbrdf_rendering_loss_fwd_bwd(
-                input.data_ptr(), target.data_ptr(), scenes.data_ptr(), xr.data_ptr(),
-                ctypes.c_float(eps), loss.data_ptr(), grad.data_ptr() if want_grad else None,
-                ws.data_ptr(), ws.numel() * 8, B, S, H, W, _stream(input.device))
+        rc = getattr(lib, entry)(input.data_ptr(), other.data_ptr(), scenes.data_ptr(), xr.data_ptr(), *floats,
+                                 loss.data_ptr(), grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel() * 8,
+                                 B, S, H, W, _stream(input.device))
         if hook is not None:
             hook("end")
     if rc != 0:
@@ -530,6 +493,38 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
         ws.zero_()
     _check(rc, entry)
     return loss, grad
+
+
+def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0, eps_l1=0.01, head=False):
+    """K3: fused rendering loss (+ d loss/d input); with l1_weight != 0 the SVBRDF L1 loss is folded
+    in (MixedLoss); with head=True `input` is the generator's [B,9,H,W] post-tanh output and the
+    network head is decoded in the kernel.  Returns (loss [1] device tensor, grad or None)."""
+    _require_device_f32(input, "input")
+    _require_device_f32(target, "target")
+    scenes, on_host = _loss_scene_table(scenes, input.device, "input, target and scenes must be on the same device")
+    if head:
+        if input.dim() != 4 or input.shape[1] != 9 or (input.shape[0],) + tuple(input.shape[2:]) != \
+                (target.shape[0],) + tuple(target.shape[2:]):
+            raise ValueError("head=True needs input [B,9,H,W] and target [B,12,H,W]")
+    elif input.shape != target.shape:
+        raise ValueError("input and target shapes differ: %s vs %s" % (tuple(input.shape), tuple(target.shape)))
+    if target.device != input.device:
+        raise ValueError("input, target and scenes must be on the same device")
+    B, S, H, W, shared = _dims(target, scenes)
+    if shared:
+        raise ValueError("the loss needs one scene table per batch item: scenes must be [B,S,9]")
+    if on_host:     # the by-value entries exist with the L1 arguments only
+        entry = "svbrdf_head_loss_fwd_bwd_host_scenes" if head else "svbrdf_mixed_loss_fwd_bwd_host_scenes"
+    elif head:
+        entry = "svbrdf_head_loss_fwd_bwd"
+    elif l1_weight != 0.0:
+        entry = "svbrdf_mixed_loss_fwd_bwd"
+    else:
+        entry = "svbrdf_rendering_loss_fwd_bwd"
+    floats = (ctypes.c_float(eps),)
+    if entry != "svbrdf_rendering_loss_fwd_bwd":
+        floats += (ctypes.c_float(l1_weight), ctypes.c_float(eps_l1))
+    return _fused_loss_call(entry, input.contiguous(), target.contiguous(), scenes, floats, want_grad, B, S, H, W)
 
 
 def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False):
@@ -541,41 +536,18 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False):
     grad or None)."""
     _require_device_f32(input, "input")
     _require_device_f32(photos, "photos")
-    host_scenes = isinstance(scenes, torch.Tensor) and not scenes.is_cuda
-    if host_scenes:
-        if scenes.dtype != torch.float32:
-            raise TypeError("scenes must be float32 (got %s)" % scenes.dtype)
-        if scenes.dim() == 3 and scenes.shape[0] * scenes.shape[1] > host_scenes_max_rows():
-            scenes, host_scenes = upload_scene_table(scenes, input.device), False
-    else:
-        _require_device_f32(scenes, "scenes")
-    if photos.device != input.device or (not host_scenes and scenes.device != input.device):
+    scenes, on_host = _loss_scene_table(scenes, input.device, "input, photos and scenes must be on the same device")
+    if photos.device != input.device:
         raise ValueError("input, photos and scenes must be on the same device")
-    input, photos, scenes = input.contiguous(), photos.contiguous(), scenes.contiguous()
     B, S, H, W, shared = _dims(input, scenes, channels=9 if head else 12)
     if shared:
         raise ValueError("the loss needs one scene row per photo: scenes must be [B,S,9]")
     if tuple(photos.shape) != (B, S, 3, H, W):
         raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
                          % ((B, S, 3, H, W), tuple(photos.shape)))
-    lib = _load()
-    ws = _workspace(input.device, lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
-    loss = torch.empty(1, dtype=torch.float32, device=input.device)
-    grad = torch.empty_like(input) if want_grad else None
-    entry = ("svbrdf_head_photo_loss_fwd_bwd" if head else "svbrdf_photo_loss_fwd_bwd") + ("_host_scenes" if host_scenes else "")
-    hook = _launch_hook
-    with _on_device(input.device):
-        if hook is not None:
-            hook("begin")
-        rc = getattr(lib, entry)(input.data_ptr(), photos.data_ptr(), scenes.data_ptr(), xrow(input.device, W).data_ptr(),
-                                 ctypes.c_float(eps), loss.data_ptr(), grad.data_ptr() if want_grad else None,
-                                 ws.data_ptr(), ws.numel() * 8, B, S, H, W, _stream(input.device))
-        if hook is not None:
-            hook("end")
-    if rc != 0:
-        ws.zero_()      # see rendering_loss
-    _check(rc, entry)
-    return loss, grad
+    entry = ("svbrdf_head_photo_loss_fwd_bwd" if head else "svbrdf_photo_loss_fwd_bwd") + ("_host_scenes" if on_host else "")
+    return _fused_loss_call(entry, input.contiguous(), photos.contiguous(), scenes, (ctypes.c_float(eps),), want_grad,
+                            B, S, H, W)
 
 
 def mix_materials(svbrdf0, svbrdf1, alpha):
@@ -592,12 +564,9 @@ def mix_materials(svbrdf0, svbrdf1, alpha):
         raise ValueError("svbrdf0, svbrdf1 and alpha must be on the same device")
     a, b, w = svbrdf0.contiguous(), svbrdf1.contiguous(), alpha.contiguous().view(-1)
     out = torch.empty_like(a)
-    lib = _load()
-    lib.svbrdf_mix_materials.argtypes = [_fp, _fp, _fp, _fp, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp]
-    lib.svbrdf_mix_materials.restype = ctypes.c_int
     with _on_device(a.device):
-        _check(lib.svbrdf_mix_materials(a.data_ptr(), b.data_ptr(), w.data_ptr(), out.data_ptr(), B, H, W,
-                                        _stream(a.device)), "svbrdf_mix_materials")
+        _check(_load().svbrdf_mix_materials(a.data_ptr(), b.data_ptr(), w.data_ptr(), out.data_ptr(), B, H, W,
+                                            _stream(a.device)), "svbrdf_mix_materials")
     return out
 
 
@@ -607,12 +576,9 @@ def clock_probe(out, ticks=300000, stream=None):
     (device int64[2]).  cycles / ticks * 0.1 = shader clock in GHz under whatever else is running."""
     if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.numel() >= 2):
         raise TypeError("out must be a device int64 tensor of at least 2 elements")
-    lib = _load()
-    lib.svbrdf_debug_clock_probe.argtypes = [_fp, ctypes.c_ulonglong, _fp]
-    lib.svbrdf_debug_clock_probe.restype = ctypes.c_int
     raw = stream.cuda_stream if stream is not None else _raw_stream(out.device)
     with _on_device(out.device):
-        _check(lib.svbrdf_debug_clock_probe(out.data_ptr(), int(ticks), ctypes.c_void_p(raw)), "svbrdf_debug_clock_probe")
+        _check(_load().svbrdf_debug_clock_probe(out.data_ptr(), int(ticks), ctypes.c_void_p(raw)), "svbrdf_debug_clock_probe")
     return out
 
 

@@ -280,6 +280,24 @@ struct State {
     std::atomic<const void *> unit_ptr{nullptr};
     std::atomic<uint32_t> unit_version{0};
 
+    // under `mu`: the x row of width W on `like`'s device (a switch of devices drops everything cached)
+    at::Tensor xrow_for(const at::Tensor &like, int W)
+    {
+        const int dev = like.device().index();
+        if (device != dev) {
+            workspace_by_stream.clear();
+            xrow_by_width.clear();
+            device = dev;
+        }
+        auto &xr = xrow_by_width[W];
+        if (!xr.defined()) {
+            auto host = at::empty({W}, at::TensorOptions().dtype(at::kFloat));
+            check(g_abi.make_xrow(host.data_ptr<float>(), W), "svbrdf_make_xrow");
+            xr = host.to(like.device());
+        }
+        return xr;
+    }
+
     // under `mu`
     void ensure_unit_grad(const at::TensorOptions &like)
     {
@@ -464,24 +482,12 @@ at::Tensor run_fused(const at::Tensor &input, const at::Tensor &target, const at
 void ensure_device_state(const at::Tensor &input, int S, int64_t stream)
 {
     const int B = (int)input.size(0), H = (int)input.size(2), W = (int)input.size(3);
-    const int dev = input.device().index();
-    if (g_state.device != dev) {          // first call, or the process switched devices: drop everything cached
-        g_state.workspace_by_stream.clear();
-        g_state.xrow_by_width.clear();
-        g_state.device = dev;
-    }
+    g_state.xrow = g_state.xrow_for(input, W);      // (first: a first call or a switch of devices drops the scratch too)
     const size_t need = g_abi.ws_bytes(B, S, H, W);
     auto &ws = g_state.workspace_by_stream[stream];
     if (!ws.defined() || (size_t)ws.numel() * 8 < need)
         ws = at::zeros({(int64_t)std::max<size_t>((need + 7) / 8, 8)}, at::TensorOptions().dtype(at::kLong).device(input.device()));
     g_state.workspace = ws;
-    auto &xr = g_state.xrow_by_width[W];
-    if (!xr.defined()) {
-        auto host = at::empty({W}, at::TensorOptions().dtype(at::kFloat));
-        check(g_abi.make_xrow(host.data_ptr<float>(), W), "svbrdf_make_xrow");
-        xr = host.to(input.device());
-    }
-    g_state.xrow = xr;
     g_state.ensure_unit_grad(input.options());
 }
 
@@ -606,19 +612,7 @@ at::Tensor render_shared_scenes(const at::Tensor &maps_in, const at::Tensor &row
     at::Tensor xrow;
     {
         std::lock_guard<std::mutex> lock(g_state.mu);
-        const int dev = maps_in.device().index();
-        if (g_state.device != dev) {
-            g_state.workspace_by_stream.clear();
-            g_state.xrow_by_width.clear();
-            g_state.device = dev;
-        }
-        auto &xr = g_state.xrow_by_width[W];
-        if (!xr.defined()) {
-            auto host = at::empty({W}, at::TensorOptions().dtype(at::kFloat));
-            check(g_abi.make_xrow(host.data_ptr<float>(), W), "svbrdf_make_xrow");
-            xr = host.to(maps_in.device());
-        }
-        xrow = xr;
+        xrow = g_state.xrow_for(maps_in, W);
     }
     void *st = reinterpret_cast<void *>(stream);
     at::Tensor out, maps;

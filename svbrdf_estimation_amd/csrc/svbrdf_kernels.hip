@@ -1224,7 +1224,7 @@ __device__ __forceinline__ void loss_arrive(float t, float fixed_scale, double l
     const unsigned nblocks = gridDim.x * gridDim.y, bid = blockIdx.y * gridDim.x + blockIdx.x;
     const unsigned slot = bid & (kLossSlots - 1);
     const unsigned slot_blocks = (nblocks - slot + kLossSlots - 1) / kLossSlots;
-    // The scale keeps every legitimate partial sum below 2^47 (loss_impl).  A partial sum that is NaN, infinite
+    // The scale keeps every legitimate partial sum below 2^47 (plan_loss).  A partial sum that is NaN, infinite
     // or beyond that (NaN/inf maps, or radiances no renderer input can produce) must neither be cast (undefined
     // for NaN/inf) nor reach the arrival count in the word's top bits: it contributes 0 and raises the sticky
     // non-finite flag in the tail word instead, and the finisher reports NaN -- as the reference's
@@ -1735,6 +1735,66 @@ namespace {
     return dim3((unsigned)((plane + per_block - 1) / per_block), (unsigned)B, 1);
 }
 
+// What every fused loss (K3 and the photo kernels of svbrdf_photo_loss.hip) needs to launch: one workgroup per 256 pixels
+// of one item, the fixed-point scale of the per-workgroup partial sums and the scratch words they are summed in.
+struct LossPlan {
+    dim3 grid;
+    float inv_count;          // 1 / (B S 3 H W)
+    double loss_scale;        // fixed-point sum -> mean
+    float fixed_scale;        // 2^k
+    size_t lds_bytes;         // forward-only kernels stage the scenes in LDS
+    unsigned long long *ws;
+};
+
+// The argument checks of every fused-loss entry point, in one order, and the plan.  `required`: the 4-byte-aligned
+// pointers that must not be null; `grad` may be null (forward only); `eps_name`: what the entry's header calls `eps`
+// (for the message).  `l1_weight` widens the worst case of a slot by the
+// L1 term's share (0: none).
+[[maybe_unused]] int plan_loss(const char *who, bool scenes_on_host, std::initializer_list<const void *> required,
+                               const float *grad, void *workspace, size_t workspace_bytes, const char *eps_name,
+                               float eps, float l1_weight, int B, int S, int H, int W, LossPlan *out)
+{
+    char text[200];
+    const auto bad = [&](int code, const char *what) {
+        std::snprintf(text, sizeof(text), "%s: %s", who, what);
+        return fail(code, text);
+    };
+    bool null = !workspace, misaligned = !aligned(workspace, 8) || !aligned(grad, 4);
+    for (const void *p : required) { null = null || !p; misaligned = misaligned || !aligned(p, 4); }
+    if (null) return fail(SVBRDF_ERR_NULL, who);
+    if (int e = check_dims(B, S, H, W)) return e;
+    if (!(eps >= 1e-9f) || !(eps <= 1e9f)) {
+        std::snprintf(text, sizeof(text), "%s: %s must lie in [1e-9, 1e9] (the reference uses 0.1)", who, eps_name);
+        return fail(SVBRDF_ERR_DIMS, text);
+    }
+    if (scenes_on_host && (long long)B * S > SVBRDF_HOST_SCENES_MAX_ROWS)
+        return bad(SVBRDF_ERR_DIMS, "B*S exceeds SVBRDF_HOST_SCENES_MAX_ROWS (upload the table and use the device-pointer entry)");
+    if (misaligned) return bad(SVBRDF_ERR_ALIGN, "pointers must be 4-byte aligned (workspace 8-byte)");
+    if (workspace_bytes < svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
+        return bad(SVBRDF_ERR_WORKSPACE, "workspace too small");
+    const long long plane = (long long)H * W;
+    if (plane > (1LL << 25))
+        return bad(SVBRDF_ERR_DIMS, "H*W exceeds 2^25 (one item's 12 planes are addressed with 32-bit byte offsets)");
+    out->grid = dim3((unsigned)((plane + kLossThreads - 1) / kLossThreads), (unsigned)B, 1);    // 256 pixels per workgroup
+    const double count = (double)B * S * 3.0 * (double)plane;
+    out->inv_count = (float)(1.0 / count);
+    out->ws = static_cast<unsigned long long *>(workspace);
+    // Fixed-point scale 2^k of the per-workgroup partial sums: as fine as 2^-24, coarser only if
+    // a slot could otherwise outgrow its 48 bits (|dlog| <= 32 per term is far beyond any
+    // radiance this renderer can produce: log(1e13/0.1)).
+    int k = 24;
+    const double l1_share = 1.0 + 4.0 * std::fabs((double)l1_weight);
+    const double worst_per_slot = (count * 32.0 / (double)kLossSlots + 32.0 * kLossThreads * 3 * S) * l1_share;
+    while (k > 0 && worst_per_slot * std::ldexp(1.0, k) >= std::ldexp(1.0, kLossCountShift - 1)) --k;
+    out->fixed_scale = (float)std::ldexp(1.0, k);
+    out->loss_scale = std::ldexp(1.0, -k) / count;
+    if ((unsigned long long)out->grid.x * out->grid.y >= (1ULL << 16) * kLossSlots)
+        return bad(SVBRDF_ERR_DIMS, "too many workgroups for the arrival counters");
+    out->lds_bytes = grad ? 0 : (size_t)S * 9 * sizeof(float);
+    if (out->lds_bytes > 60 * 1024) return bad(SVBRDF_ERR_DIMS, "too many scenes per item for the LDS stage (max 1706)");
+    return 0;
+}
+
 #endif  // SVBRDF_TU_MAIN || SVBRDF_TU_AUX (host helpers)
 
 
@@ -1992,47 +2052,21 @@ static int loss_impl(const char *who, bool head, bool scenes_on_host, const floa
                      float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes, int B, int S,
                      int H, int W, void *stream)
 {
-    if (!input || !target || !scenes || !xrow || !loss_out || !workspace) return fail(SVBRDF_ERR_NULL, who);
-    if (int e = check_dims(B, S, H, W)) return e;
-    if (!(eps >= 1e-9f) || !(eps <= 1e9f))
-        return fail(SVBRDF_ERR_DIMS, "loss: eps_render must lie in [1e-9, 1e9] (the reference uses 0.1)");
-    if (scenes_on_host && (long long)B * S > SVBRDF_HOST_SCENES_MAX_ROWS)
-        return fail(SVBRDF_ERR_DIMS, "host_scenes: B*S exceeds SVBRDF_HOST_SCENES_MAX_ROWS (upload the table and use the device-pointer entry)");
-    if (!aligned(input, 4) || !aligned(target, 4) || !aligned(scenes, 4) || !aligned(xrow, 4) ||
-        !aligned(loss_out, 4) || !aligned(workspace, 8) || (grad_input && !aligned(grad_input, 4)))
-        return fail(SVBRDF_ERR_ALIGN, "loss: pointers must be 4-byte aligned (workspace 8-byte)");
-    if (workspace_bytes < svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
-        return fail(SVBRDF_ERR_WORKSPACE, "loss: workspace too small");
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    LossPlan p;
+    if (int e = plan_loss(who, scenes_on_host, {input, target, scenes, xrow, loss_out}, grad_input, workspace,
+                          workspace_bytes, "eps_render", eps, l1_weight, B, S, H, W, &p)) return e;
     const long long plane = (long long)H * W;
-    if (plane > (1LL << 25))
-        return fail(SVBRDF_ERR_DIMS, "loss: H*W exceeds 2^25 (one item's 12 planes are addressed with 32-bit byte offsets)");
-    const dim3 grid((unsigned)((plane + kLossThreads - 1) / kLossThreads), (unsigned)B, 1);    // 256 pixels per workgroup
-    const double count = (double)B * S * 3.0 * (double)plane;
-    const float inv_count = (float)(1.0 / count);
-    unsigned long long *ws = static_cast<unsigned long long *>(workspace);
-    // Fixed-point scale 2^k of the per-workgroup partial sums: as fine as 2^-24, coarser only if
-    // a slot could otherwise outgrow its 48 bits (|dlog| <= 32 per term is far beyond any
-    // radiance this renderer can produce: log(1e13/0.1)).
-    int k = 24;
-    const double l1_share = 1.0 + 4.0 * std::fabs((double)l1_weight);
-    const double worst_per_slot = (count * 32.0 / (double)kLossSlots + 32.0 * kLossThreads * 3 * S) * l1_share;
-    while (k > 0 && worst_per_slot * std::ldexp(1.0, k) >= std::ldexp(1.0, kLossCountShift - 1)) --k;
-    const float fixed_scale = (float)std::ldexp(1.0, k);
-    const double loss_scale = std::ldexp(1.0, -k) / count;
-    if ((unsigned long long)grid.x * grid.y >= (1ULL << 16) * kLossSlots)
-        return fail(SVBRDF_ERR_DIMS, "loss: too many workgroups for the arrival counters");
-    const size_t lds_bytes = grad_input ? 0 : (size_t)S * 9 * sizeof(float);   // forward-only kernels stage scenes in LDS
-    if (lds_bytes > 60 * 1024) return fail(SVBRDF_ERR_DIMS, "loss: too many scenes per item for the LDS stage (max 1706)");
     const L1Params l1{l1_weight * (float)S, (float)((double)l1_weight / ((double)B * 3.0 * (double)plane)), eps_l1};
     const float *rows = scenes_on_host ? scenes : nullptr;
     if (grad_input)
         (l1_weight != 0.0f || head ? svbrdf_internal_launch_k3_adjoint_extra : svbrdf_internal_launch_k3_adjoint_plain)(
-            l1_weight != 0.0f, head, rows, grid.x, grid.y, lds_bytes, stream, input, target, scenes, xrow, eps,
-            inv_count, loss_scale, fixed_scale, l1.sum_scale, l1.grad_scale, l1.eps, grad_input, ws, loss_out, B, S, H, W);
+            l1_weight != 0.0f, head, rows, p.grid.x, p.grid.y, p.lds_bytes, stream, input, target, scenes, xrow, eps,
+            p.inv_count, p.loss_scale, p.fixed_scale, l1.sum_scale, l1.grad_scale, l1.eps, grad_input, p.ws, loss_out, B, S,
+            H, W);
     else
-        launch_k3<false, 2>(l1_weight != 0.0f, head, rows, grid, lds_bytes, st, input, target, scenes, xrow, eps,
-                            inv_count, loss_scale, fixed_scale, l1, grad_input, ws, loss_out, B, S, H, W);
+        launch_k3<false, 2>(l1_weight != 0.0f, head, rows, p.grid, p.lds_bytes, static_cast<hipStream_t>(stream), input,
+                            target, scenes, xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, l1, grad_input, p.ws,
+                            loss_out, B, S, H, W);
     return launch_status(who);
 }
 

@@ -389,45 +389,20 @@ void launch_photo(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st
     }
 }
 
-// argument checks, grid, fixed-point scale: those of svbrdf_rendering_loss_fwd_bwd (loss_impl in svbrdf_kernels.hip).  The
-// launch is counted by the main unit's counter through launch_status() (svbrdf_internal_launch_status).
+// Argument checks, grid and fixed-point scale: K3's own (plan_loss in svbrdf_kernels.hip; no L1 term here).  The launch
+// is counted by the main unit's counter through launch_status() (svbrdf_internal_launch_status).
 // `head`: input and grad_input are the 9 encoded planes (svbrdf_head_photo_loss_fwd_bwd*), same checks
 int photo_impl(const char *who, bool scenes_on_host, bool head, const float *input, const float *photos, const float *scenes,
                const float *xrow, float eps, float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes,
                int B, int S, int H, int W, void *stream)
 {
-    if (!input || !photos || !scenes || !xrow || !loss_out || !workspace) return fail(SVBRDF_ERR_NULL, who);
-    if (int e = check_dims(B, S, H, W)) return e;
-    if (!(eps >= 1e-9f) || !(eps <= 1e9f))
-        return fail(SVBRDF_ERR_DIMS, "photo_loss: eps must lie in [1e-9, 1e9] (the reference uses 0.1)");
-    if (scenes_on_host && (long long)B * S > SVBRDF_HOST_SCENES_MAX_ROWS)
-        return fail(SVBRDF_ERR_DIMS, "host_scenes: B*S exceeds SVBRDF_HOST_SCENES_MAX_ROWS (upload the table and use the device-pointer entry)");
-    if (!aligned(input, 4) || !aligned(photos, 4) || !aligned(scenes, 4) || !aligned(xrow, 4) || !aligned(loss_out, 4) ||
-        !aligned(workspace, 8) || (grad_input && !aligned(grad_input, 4)))
-        return fail(SVBRDF_ERR_ALIGN, "photo_loss: pointers must be 4-byte aligned (workspace 8-byte)");
-    if (workspace_bytes < svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
-        return fail(SVBRDF_ERR_WORKSPACE, "photo_loss: workspace too small");
-    const long long plane = (long long)H * W;
-    if (plane > (1LL << 25))
-        return fail(SVBRDF_ERR_DIMS, "photo_loss: H*W exceeds 2^25 (one item's 12 planes are addressed with 32-bit byte offsets)");
-    const dim3 grid((unsigned)((plane + kLossThreads - 1) / kLossThreads), (unsigned)B, 1);
-    const double count = (double)B * S * 3.0 * (double)plane;
-    const float inv_count = (float)(1.0 / count);
-    int k = 24;     // fixed-point scale 2^k of the per-workgroup partial sums (loss_impl)
-    const double worst_per_slot = count * 32.0 / (double)kLossSlots + 32.0 * kLossThreads * 3 * S;
-    while (k > 0 && worst_per_slot * std::ldexp(1.0, k) >= std::ldexp(1.0, kLossCountShift - 1)) --k;
-    const float fixed_scale = (float)std::ldexp(1.0, k);
-    const double loss_scale = std::ldexp(1.0, -k) / count;
-    if ((unsigned long long)grid.x * grid.y >= (1ULL << 16) * kLossSlots)
-        return fail(SVBRDF_ERR_DIMS, "photo_loss: too many workgroups for the arrival counters");
-    const size_t lds_bytes = grad_input ? 0 : (size_t)S * 9 * sizeof(float);
-    if (lds_bytes > 60 * 1024) return fail(SVBRDF_ERR_DIMS, "photo_loss: too many scenes per item for the LDS stage (max 1706)");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    unsigned long long *ws = static_cast<unsigned long long *>(workspace);
+    LossPlan p;
+    if (int e = plan_loss(who, scenes_on_host, {input, photos, scenes, xrow, loss_out}, grad_input, workspace,
+                          workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
     const float *rows = scenes_on_host ? scenes : nullptr;
 #define SVBRDF_LAUNCH_PHOTO(G, HD)                                                                                      \
-    launch_photo<G, HD>(rows, grid, lds_bytes, st, input, photos, scenes, xrow, eps, inv_count, loss_scale, fixed_scale, \
-                        grad_input, ws, loss_out, B, S, H, W)
+    launch_photo<G, HD>(rows, p.grid, p.lds_bytes, static_cast<hipStream_t>(stream), input, photos, scenes, xrow, eps,  \
+                        p.inv_count, p.loss_scale, p.fixed_scale, grad_input, p.ws, loss_out, B, S, H, W)
     if (head) {
         if (grad_input) SVBRDF_LAUNCH_PHOTO(true, true);
         else SVBRDF_LAUNCH_PHOTO(false, true);

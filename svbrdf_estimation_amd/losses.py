@@ -53,29 +53,44 @@ class _FusedRenderingLoss(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        if ctx.grads is None:
-            raise RuntimeError("Trying to backward through the fused rendering loss a second time: its gradient buffers "
-                               "were handed to the first backward.  Specify retain_graph=True for the first one.")
-        if torch.is_grad_enabled():
+        if torch.is_grad_enabled() and ctx.grads is not None:
             # backward(create_graph=True): the kernel's gradient buffers are constants to autograd; recompute the loss
             # from differentiable pieces instead (same scenes) and let autograd derive a gradient it can differentiate
             input, target = ctx.saved_tensors
             return differentiable_loss_backward(input, target, *ctx.second_order, grad_loss,
                                                 ctx.needs_input_grad[0], ctx.needs_input_grad[1]) + (None,) * 5
-        grad_in, grad_tg = ctx.grads
-        # chain rule through the scalar loss on the device (no host sync).  This is the FALLBACK host path (the native
-        # extension is the default and does the same in csrc/host_ext.cpp): a plain backward hands the kernel's buffers
-        # over and scales them in place -- no copy, no extra pass; under retain_graph=True they stay with the graph and
-        # every backward receives a scaled copy, so repeated backwards work as through the reference's plain-autograd
-        # loss (losses.py:29-52), and a second backward without it fails like autograd's own nodes do.
-        keep = _current_backward_keeps_graph()
-        if not keep:
-            ctx.grads = None
-        scale = grad_loss.detach().to(torch.float32).reshape(1)
-        outs = []
-        for g in (grad_in, grad_tg):
-            outs.append(None if g is None else _native.scale_inplace_(g.clone() if keep else g, scale))
-        return outs[0], outs[1], None, None, None, None, None
+        # This is the FALLBACK host path (the native extension is the default and does the same in csrc/host_ext.cpp)
+        grad_in, grad_tg = _hand_over_gradients(ctx, grad_loss, "Trying to backward through the fused rendering loss a "
+                                                "second time: its gradient buffers were handed to the first backward.  "
+                                                "Specify retain_graph=True for the first one.")
+        return grad_in, grad_tg, None, None, None, None, None
+
+
+def _hand_over_gradients(ctx, grad_loss, second_time):
+    """The plain backward of a fused loss whose kernel already produced the gradients ``ctx.grads`` (a tuple, None where
+    not wanted) for upstream gradient 1: the chain rule through the scalar loss on the device, no host sync.  A plain
+    backward hands the kernel's buffers over and scales them in place -- no copy, no extra pass; under retain_graph=True
+    they stay with the graph and every backward receives a scaled copy, so repeated backwards work as through the
+    reference's plain-autograd loss (losses.py:29-52), and a second backward without it fails like autograd's own nodes
+    do (``second_time``: the message).  The cached 1.0 of ``_UnitGradientLoss`` is recognised (once somebody has asked
+    for one): nothing to scale, nothing to launch.  -> the list of gradients, in ``ctx.grads``' order."""
+    grads = ctx.grads
+    if grads is None:
+        raise RuntimeError(second_time)
+    keep = _current_backward_keeps_graph()
+    if not keep:
+        ctx.grads = None
+    unit = bool(_unit_gradients) and _is_unit_gradient(grad_loss)
+    scale = None if unit else grad_loss.detach().to(torch.float32).reshape(1)
+    outs = []
+    for g in grads:
+        if g is not None:
+            if keep:
+                g = g.clone()
+            if scale is not None:
+                _native.scale_inplace_(g, scale)
+        outs.append(g)
+    return outs
 
 
 # private autograd accessor, looked up once: a torch build without it falls back to "the graph is kept" -- every backward
@@ -118,7 +133,18 @@ def differentiable_loss_backward(input, target, scenes, eps, l1_weight, eps_l1, 
     return g_in, g_tg
 
 
-class _FusedLossTensor(torch.Tensor):
+class _UnitGradientLoss(torch.Tensor):
+    """A 0-dim loss whose PLAIN ``backward()`` hands autograd a cached device-resident 1.0 instead of a fresh ones tensor."""
+
+    __torch_function__ = torch._C._disabled_torch_function_impl      # ops on it return plain tensors, no dispatch cost
+
+    def _plain_backward(self, gradient, create_graph):
+        """no explicit gradient, no create_graph, and nobody watches the loss's gradient (a hook, retain_grad): whoever
+        does gets the engine's own fresh ones tensor, theirs to edit; the node then sees an ordinary gradient and applies it"""
+        return gradient is None and not create_graph and self._backward_hooks is None and not self.retains_grad
+
+
+class _FusedLossTensor(_UnitGradientLoss):
     """The 0-dim loss the native host path returns when a gradient is wanted: an ordinary tensor, attached to the autograd
     graph as usual, whose PLAIN ``backward()`` (no explicit gradient, no create_graph) costs one kernel launch and no
     Python in front of the engine:
@@ -138,23 +164,18 @@ class _FusedLossTensor(torch.Tensor):
     Every other use -- an explicit gradient, ``create_graph=True``, a second ``backward()``, arithmetic on the loss (which
     yields a plain tensor), ``torch.autograd.grad`` -- goes through autograd unchanged."""
 
-    __torch_function__ = torch._C._disabled_torch_function_impl      # ops on it return plain tensors, no dispatch cost
-
     def backward(self, gradient=None, retain_graph=None, create_graph=False, inputs=None):
         src = self.__dict__.pop("_svbrdf_src", None)
-        if src is not None and gradient is None and not create_graph:
+        if src is not None and _UNIT_GRADIENT and self._plain_backward(gradient, create_graph):
             inner, ext = src
-            # not when someone watches the loss's gradient (a hook, retain_grad): they get the engine's own fresh ones
-            # tensor, theirs to edit; the node then sees an ordinary gradient and applies it
-            if _UNIT_GRADIENT and self._backward_hooks is None and not self.retains_grad:
-                if inputs is None and _ENGINE_FROM_NATIVE and not _functorch_active():
-                    # the same engine run, entered through torch::autograd::backward from the extension (no Python
-                    # argument processing in front of the engine: ~6 us of the ~20 us a step spends on the host)
-                    # (from `inner`, the extension's own tensor: `self` is an alias of it that nobody watches -- checked
-                    # above -- so its AliasBackward node would only be one more node for the engine to walk)
-                    ext.engine_backward(inner, bool(retain_graph))
-                    return None
-                gradient = ext.unit_gradient(inner)
+            if inputs is None and _ENGINE_FROM_NATIVE and not _functorch_active():
+                # the same engine run, entered through torch::autograd::backward from the extension (no Python
+                # argument processing in front of the engine: ~6 us of the ~20 us a step spends on the host)
+                # (from `inner`, the extension's own tensor: `self` is an alias of it that nobody watches -- checked
+                # above -- so its AliasBackward node would only be one more node for the engine to walk)
+                ext.engine_backward(inner, bool(retain_graph))
+                return None
+            gradient = ext.unit_gradient(inner)
         return torch.Tensor.backward(self, gradient, retain_graph, create_graph, inputs)
 
 
@@ -271,7 +292,8 @@ class _FusedPhotoLoss(torch.autograd.Function):
         need_in = ctx.needs_input_grad[0]
         ctx.save_for_backward(input, photos)        # (for backward(create_graph=True) only: references, no copies)
         ctx.second_order = (scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head))
-        loss, ctx.grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head)
+        loss, grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head)
+        ctx.grads = None if grad is None else (grad,)
         return loss.view(())
 
     @staticmethod
@@ -286,31 +308,21 @@ class _FusedPhotoLoss(torch.autograd.Function):
                 loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes, eps)
                 g, = torch.autograd.grad(loss, [input], grad_loss.to(torch.float64).reshape(()), create_graph=True)
             return g.to(input.dtype), None, None, None, None
-        if ctx.grad is None:
-            raise RuntimeError("Trying to backward through the fused photo loss a second time: its gradient buffer was "
-                               "handed to the first backward.  Specify retain_graph=True for the first one.")
-        # chain rule through the scalar loss on the device, no host sync (as _FusedRenderingLoss.backward)
-        keep = _current_backward_keeps_graph()
-        grad = ctx.grad
-        if not keep:
-            ctx.grad = None
-        if _is_unit_gradient(grad_loss):     # _PhotoLossTensor.backward's cached 1.0: nothing to scale, nothing to launch
-            return (grad.clone() if keep else grad), None, None, None, None
-        scale = grad_loss.detach().to(torch.float32).reshape(1)
-        return _native.scale_inplace_(grad.clone() if keep else grad, scale), None, None, None, None
+        grad, = _hand_over_gradients(ctx, grad_loss, "Trying to backward through the fused photo loss a second time: its "
+                                     "gradient buffer was handed to the first backward.  Specify retain_graph=True for "
+                                     "the first one.")
+        return grad, None, None, None, None
 
 
-class _PhotoLossTensor(torch.Tensor):
+class _PhotoLossTensor(_UnitGradientLoss):
     """The 0-dim loss PhotoLoss returns when a gradient is wanted: an ordinary tensor whose PLAIN ``backward()`` (no
     explicit gradient, no create_graph, nobody watching the loss's gradient) hands autograd a cached device-resident 1.0
     as the upstream gradient; the loss's node recognises that tensor and skips its (no-op) scale launch, so a step is
     ONE kernel launch.  Same values bit for bit: multiplying by 1.0 is what was skipped.  Every other use goes through
     autograd unchanged (``_FusedLossTensor`` does the same for the native host path of the other losses)."""
 
-    __torch_function__ = torch._C._disabled_torch_function_impl
-
     def backward(self, gradient=None, retain_graph=None, create_graph=False, inputs=None):
-        if gradient is None and not create_graph and self._backward_hooks is None and not self.retains_grad:
+        if self._plain_backward(gradient, create_graph):
             gradient = _unit_gradient(self.device)
         return torch.Tensor.backward(self, gradient, retain_graph, create_graph, inputs)
 
@@ -336,6 +348,20 @@ def composed_photo_loss(input, photos, scenes, eps):
     maps take and what ``backward(create_graph=True)`` of the fused loss differentiates.  ``scenes`` [B,S,9] float32."""
     rendered = renderers._RenderFunction.apply(input, scenes)
     return nn.functional.l1_loss(torch.log(rendered + eps), torch.log(photos.to(rendered.dtype) + eps))
+
+
+def _check_fused_photo_inputs(loss_name, input_name, input, photos):
+    """The fused photo losses' device and dtype rules, raised as errors: tensors on a ROCm device, float32 or float64.
+    -> "promote": double on either side (the reference's torch ops would promote, so the caller takes the composed
+    float64 definition)."""
+    if not input.is_cuda:
+        raise _native.NativeLibraryError("%s with the MI355X LocalRenderer needs tensors on a ROCm device "
+                                         "(got %s); there is no CPU fallback" % (loss_name, input.device))
+    if input.dtype == torch.float64 or photos.dtype == torch.float64:
+        return True
+    if input.dtype != torch.float32 or photos.dtype != torch.float32:
+        raise TypeError("%s and photos must be float32 or float64 (got %s, %s)" % (input_name, input.dtype, photos.dtype))
+    return False
 
 
 class PhotoLoss(nn.Module):
@@ -410,14 +436,8 @@ class PhotoLoss(nn.Module):
         if not self.uses_fused_kernel():
             return self._forward_plugin(input, photos, self._scene_objects(scenes, B, S))
         table = self._scene_table(scenes, B, S)
-        if not input.is_cuda:
-            raise _native.NativeLibraryError("PhotoLoss with the MI355X LocalRenderer needs tensors on a ROCm device "
-                                             "(got %s); there is no CPU fallback" % input.device)
-        if input.dtype == torch.float64 or photos.dtype == torch.float64:
-            # double on either side: the reference's torch ops would promote, so does this (float64 K1 / K2)
-            return composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps)
-        if input.dtype != torch.float32 or photos.dtype != torch.float32:
-            raise TypeError("input and photos must be float32 or float64 (got %s, %s)" % (input.dtype, photos.dtype))
+        if _check_fused_photo_inputs("PhotoLoss", "input", input, photos):
+            return composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps)     # float64 K1 / K2
         loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps), False)
         return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
 
@@ -504,13 +524,7 @@ class HeadPhotoLoss(nn.Module):
         if not self.uses_fused_kernel():
             return composed(decode_head(encoded9), photos, scenes)
         table = PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
-        if not encoded9.is_cuda:
-            raise _native.NativeLibraryError("HeadPhotoLoss with the MI355X LocalRenderer needs tensors on a ROCm device "
-                                             "(got %s); there is no CPU fallback" % encoded9.device)
-        if encoded9.dtype == torch.float64 or photos.dtype == torch.float64:
-            # double on either side: promoted in front of the decode, as the reference's torch ops would
-            return composed(decode_head(encoded9.to(torch.float64)), photos, table)
-        if encoded9.dtype != torch.float32 or photos.dtype != torch.float32:
-            raise TypeError("encoded9 and photos must be float32 or float64 (got %s, %s)" % (encoded9.dtype, photos.dtype))
+        if _check_fused_photo_inputs("HeadPhotoLoss", "encoded9", encoded9, photos):
+            return composed(decode_head(encoded9.to(torch.float64)), photos, table)     # promoted in front of the decode
         loss = _FusedPhotoLoss.apply(encoded9, photos, table, float(self.eps), True)
         return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss

@@ -1,0 +1,100 @@
+"""Which C entry point the ctypes binding reaches for each form of a fused-loss call, and what every such call must leave
+behind: one launch, a finite loss, zeroed scratch, one begin/end pair for the launch hook.  4 x 4 pixels and one scene are
+the smallest shapes at which a wrong route, a lost hook or a missing ``zero_`` shows; 289 rows is one more than a table
+that rides in the launch's argument block, so a host table of that size is uploaded and reaches the device entry."""
+import numpy as np
+import pytest
+import torch
+
+import head_checks
+import synth
+
+pytestmark = pytest.mark.gpu
+
+H = 4
+# (call, input channels, scenes on the host, S, options) -> entry
+ROUTES = [
+    ("rendering_loss", 12, True, 1, {"l1_weight": 0.0}, "svbrdf_mixed_loss_fwd_bwd_host_scenes"),
+    ("rendering_loss", 12, True, 1, {"l1_weight": 0.1}, "svbrdf_mixed_loss_fwd_bwd_host_scenes"),
+    ("rendering_loss", 9, True, 1, {"head": True}, "svbrdf_head_loss_fwd_bwd_host_scenes"),
+    ("rendering_loss", 12, False, 1, {"l1_weight": 0.0}, "svbrdf_rendering_loss_fwd_bwd"),
+    ("rendering_loss", 12, False, 1, {"l1_weight": 0.1}, "svbrdf_mixed_loss_fwd_bwd"),
+    ("rendering_loss", 9, True, 289, {"head": True}, "svbrdf_head_loss_fwd_bwd"),
+    ("photo_loss", 12, True, 1, {}, "svbrdf_photo_loss_fwd_bwd_host_scenes"),
+    ("photo_loss", 12, False, 1, {}, "svbrdf_photo_loss_fwd_bwd"),
+    ("photo_loss", 9, True, 1, {"head": True}, "svbrdf_head_photo_loss_fwd_bwd_host_scenes"),
+    ("photo_loss", 9, False, 1, {"head": True}, "svbrdf_head_photo_loss_fwd_bwd"),
+    ("photo_loss", 12, True, 289, {}, "svbrdf_photo_loss_fwd_bwd"),
+]
+
+
+class _Recorder:
+    """stands in for the loaded library: every svbrdf_* function looked up on it is called through, its name noted"""
+
+    def __init__(self, lib):
+        self._lib, self.called = lib, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if not name.startswith("svbrdf_"):
+            return fn
+
+        def call(*args):
+            self.called.append(name)
+            return fn(*args)
+        return call
+
+
+@pytest.fixture(scope="module")
+def inputs():
+    """device tensors shared by every case (never written): maps, encoded head output, target maps, scene tables and
+    clamped photos of other maps for S = 1 and S = 289"""
+    from svbrdf_estimation_amd import _native, environment
+    assert torch.cuda.is_available(), "GPU tests need an MI355X (select CPU tests with -m 'not gpu')"
+    dev = torch.device("cuda:0")
+    torch.manual_seed(7)
+    out = {12: torch.from_numpy(synth.make_maps(1, 1, H)).to(dev),
+           9: torch.from_numpy(head_checks.interior(2, 1, H)).to(dev),
+           "target": torch.from_numpy(synth.make_maps(3, 1, H)).to(dev)}
+    other = torch.from_numpy(synth.make_maps(4, 1, H)).to(dev)
+    for S in (1, 289):
+        table = environment.scene_table(S // 2, S - S // 2).unsqueeze(0).contiguous()
+        assert tuple(table.shape) == (1, S, 9) and table.dtype == torch.float32
+        out["scenes", S] = table
+        out["photos", S] = _native.render_fwd(other, table).clamp(0.0, 1.0)
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("want_grad", [True, False], ids=["grad", "forward_only"])
+@pytest.mark.parametrize("route", ROUTES, ids=["%02d_%s" % (i + 1, r[-1][len("svbrdf_"):]) for i, r in enumerate(ROUTES)])
+def test_fused_loss_call_reaches_its_entry(route, want_grad, inputs, monkeypatch):
+    from svbrdf_estimation_amd import _native
+    call, channels, on_host, S, options, entry = route
+    assert 288 == _native.host_scenes_max_rows()
+    x = inputs[channels]
+    other = inputs["photos", S] if call == "photo_loss" else inputs["target"]
+    scenes = inputs["scenes", S] if on_host else inputs["scenes", S].to(x.device)
+    _native.xrow(x.device, H)           # (the cached x row: its first use is no part of the call under test)
+    rec = _Recorder(_native._load())
+    monkeypatch.setattr(_native, "_load", lambda: rec)
+    seen = []
+    _native.set_launch_hook(seen.append)
+    try:
+        before = _native.launch_count()
+        loss, grad = getattr(_native, call)(x, other, scenes, want_grad=want_grad, **options)
+        after = _native.launch_count()
+    finally:
+        _native.set_launch_hook(None)
+    torch.cuda.synchronize()
+    reached = [n for n in rec.called if "loss_fwd_bwd" in n]
+    print("%s -> %s, launches %d, loss %r, hook %r" % (route[:5], reached, after - before, loss.item(), seen))
+    assert reached == [entry]
+    assert after - before == 1
+    assert np.isfinite(loss.item())
+    if want_grad:
+        assert grad.shape == x.shape and torch.isfinite(grad).all()
+    else:
+        assert grad is None
+    assert seen == ["begin", "end"]
+    assert _native._workspace_cache and all(not ws.any().item() for ws in _native._workspace_cache.values())

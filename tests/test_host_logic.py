@@ -37,6 +37,14 @@ def _declared_symbols():
     return re.findall(r"SVBRDF_API\s+[\w\s\*]+?\b(svbrdf_\w+)\s*\(", text)
 
 
+def _declared_parameter_counts():
+    """{function: number of parameters} of every SVBRDF_API declaration of the header; `(void)` counts as 0"""
+    text = open(os.path.join(ROOT, "include", "svbrdf_hip.h")).read()
+    text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    found = re.findall(r"SVBRDF_API\s+[\w\s\*]+?\b(svbrdf_\w+)\s*\(([^()]*)\)\s*;", text)
+    return {name: 0 if params.strip() in ("", "void") else params.count(",") + 1 for name, params in found}
+
+
 def test_library_loads_and_exports_every_declared_symbol():
     from svbrdf_estimation_amd import _native
     lib = _native._load()                     # dlopen + ABI version check, no GPU needed
@@ -45,6 +53,15 @@ def test_library_loads_and_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), "libsvbrdf_hip.so does not export %s" % n
     assert lib.svbrdf_abi_version() == _native.ABI_VERSION
+    # the binding's signature table against the header: a miscounted argtypes list would hand a launch garbage
+    counts = _declared_parameter_counts()
+    assert sorted(counts) == sorted(names)
+    assert counts["svbrdf_abi_version"] == 0 and counts["svbrdf_mixed_loss_fwd_bwd"] == 16
+    for n in names:
+        assert n in _native.SIGNATURES, "no ctypes signature for %s" % n
+        restype, argtypes = _native.SIGNATURES[n]
+        assert len(argtypes) == counts[n], (n, len(argtypes), counts[n])
+        assert getattr(lib, n).restype is restype and list(getattr(lib, n).argtypes or []) == list(argtypes), n
 
 
 def test_make_xrow_matches_reference_linspace_bits(golden):

@@ -44,9 +44,17 @@ def test_library_exports_the_photo_loss_and_abi_8(lib):
         assert "SVBRDF_API int %s(" % name in header
 
 
-@pytest.mark.parametrize("entry", ENTRIES)
+# all nine fused-loss entry points share one set of argument checks (plan_loss in csrc/svbrdf_kernels.hip); the mixed and
+# head K3 entries take `l1_weight, eps_l1` after `eps`
+LOSS_ENTRIES = ENTRIES + ("svbrdf_head_photo_loss_fwd_bwd", "svbrdf_head_photo_loss_fwd_bwd_host_scenes",
+                          "svbrdf_rendering_loss_fwd_bwd")
+LOSS_ENTRIES_L1 = ("svbrdf_mixed_loss_fwd_bwd", "svbrdf_mixed_loss_fwd_bwd_host_scenes", "svbrdf_head_loss_fwd_bwd",
+                   "svbrdf_head_loss_fwd_bwd_host_scenes")
+
+
+@pytest.mark.parametrize("entry", LOSS_ENTRIES + LOSS_ENTRIES_L1)
 def test_argument_errors_come_before_any_launch(lib, entry):
-    """error codes of svbrdf_rendering_loss_fwd_bwd: -1 null pointer, -2 bad dims / H != W / eps out of range, -3 misaligned,
+    """error codes of every fused-loss entry point: -1 null pointer, -2 bad dims / H != W / eps out of range, -3 misaligned,
     -4 workspace too small.  Host buffers stand in for device memory: every check fails before anything is enqueued."""
     fn = getattr(lib, entry)
     B, S, H = 1, 2, 8
@@ -54,19 +62,20 @@ def test_argument_errors_come_before_any_launch(lib, entry):
     p = (ctypes.cast(buf, ctypes.c_void_p).value + 63) & ~63
     need = lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, H)
     assert need == 65 * 8
+    l1 = (ctypes.c_float(0.1), ctypes.c_float(0.01)) if entry in LOSS_ENTRIES_L1 else ()
 
-    def call(input=p, photos=p + 256, scenes=p + 512, xrow=p + 1024, eps=0.1, loss=p + 2048, grad=p + 4096, ws=p + 8192,
+    def call(input=p, other=p + 256, scenes=p + 512, xrow=p + 1024, eps=0.1, loss=p + 2048, grad=p + 4096, ws=p + 8192,
              ws_bytes=need, B=B, S=S, H=H, W=H):
-        return fn(input, photos, scenes, xrow, ctypes.c_float(eps), loss, grad, ws, ws_bytes, B, S, H, W, None)
+        return fn(input, other, scenes, xrow, ctypes.c_float(eps), *l1, loss, grad, ws, ws_bytes, B, S, H, W, None)
 
     launches = lib.svbrdf_debug_launch_count()
-    for name in ("input", "photos", "scenes", "xrow", "loss", "ws"):
+    for name in ("input", "other", "scenes", "xrow", "loss", "ws"):
         assert call(**{name: None}) == -1, name
     assert lib.svbrdf_last_error()
     assert call(W=H + 1) == -2
     assert call(B=0) == -2 and call(S=0) == -2
     assert call(eps=0.0) == -2 and call(eps=float("nan")) == -2 and call(eps=1e10) == -2
-    assert call(photos=p + 2) == -3 and call(ws=p + 8196) == -3
+    assert call(other=p + 2) == -3 and call(ws=p + 8196) == -3 and call(input=p + 1) == -3 and call(grad=p + 4098) == -3
     assert call(ws_bytes=need - 8) == -4
     if entry.endswith("host_scenes"):
         assert call(B=17, S=17) == -2                    # 289 rows: beyond the argument block
