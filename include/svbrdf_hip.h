@@ -224,6 +224,52 @@ SVBRDF_API int svbrdf_head_photo_loss_fwd_bwd_host_scenes(const float *encoded9,
                                                           size_t workspace_bytes, int B, int S, int H, int W,
                                                           void *stream);
 
+/* The two photo losses with a CONFIDENCE WEIGHT per photo pixel, still ONE launch: what captured photographs need, whose
+ * clipped highlights, pixels outside the rectified patch, noise-floor shadows and invalid (NaN) pixels of an HDR merge
+ * must not vote.  With w in [0, 1], N = B S 3 H W and p' = (w > 0 ? photo : 0):
+ *   loss_out[0] = (1/N) sum_{b,s,c,i,j} w[b,s,i,j] | log(render(scene[b,s], input[b])[c,i,j] + eps) - log(p'[b,s,c,i,j] + eps) |
+ *   grad_input  = d loss / d input (upstream gradient 1.0), or NULL for forward-only (same loss bitwise).
+ * `weights` holds `weight_planes` planes per item: weight_planes = S is [B,S,H,W], one plane per photo; weight_planes = 1
+ * is [B,1,H,W], one plane per item shared by its photos (the patch outline).  Any other count: SVBRDF_ERR_DIMS.  One
+ * weight serves the three colour channels of its pixel (per-channel confidence: pass the minimum over the channels).
+ *  - A weight of exactly 0 EXCUSES THE PHOTO VALUE UNDER IT: the term is exactly 0 and its gradient exactly 0 whatever
+ *    the photo holds there -- NaN, +-inf, a value at or below -eps.  The photo is replaced, not multiplied: 0 * NaN is
+ *    never formed.  A pixel whose weights are 0 for every photo gets an all-zero (+-0) gradient.
+ *  - A weight does NOT excuse the maps: a NaN or infinity anywhere in `input` / `encoded9` gives loss_out[0] = NaN, also at
+ *    a pixel whose weights are all 0.
+ *  - WEIGHTS MUST LIE IN [0, 1].  A weight that is NaN, negative or above 1 gives loss_out[0] = NaN (the sticky flag) with
+ *    the scratch left zeroed.  The range is what keeps a term within the bound the fixed-point scale of the partial sums
+ *    is planned for (|dlog| <= 32 per term): scale larger confidences down to 1 and the loss by the same factor.
+ *  - A photo value that is NaN, infinite or at or below -eps where w > 0 gives NaN, as in the unweighted entries.
+ *  - Weights of all ones give the loss and the gradient of the unweighted entry point BIT FOR BIT.
+ * The weight of a (pixel, photo) is one more load beside the photo's three values: HBM traffic
+ * (12 + 3 S + P + 12) * 4 bytes per pixel for the maps entries and (9 + 3 S + P + 9) * 4 for the head entries,
+ * P = weight_planes (a shared plane is read from HBM once and from cache for the other photos).  Everything else is the
+ * unweighted entries': PyTorch's sub-gradient conventions, bitwise run-to-run reproducibility, the scratch contract, the
+ * error codes before any launch (`weights` is required: SVBRDF_ERR_NULL; 4-byte aligned: SVBRDF_ERR_ALIGN; every aligned
+ * pointer gives the same results), the eps range and the `_host_scenes` limit.  No gradient w.r.t. weights, photos or
+ * scenes.  ADDED TO ABI VERSION 8 WITHOUT A BUMP, like the head entries above: detect the four by symbol presence. */
+SVBRDF_API int svbrdf_photo_loss_weighted_fwd_bwd(const float *input, const float *photos, const float *weights,
+                                                  int weight_planes, const float *scenes, const float *xrow, float eps,
+                                                  float *loss_out, float *grad_input, void *workspace,
+                                                  size_t workspace_bytes, int B, int S, int H, int W, void *stream);
+SVBRDF_API int svbrdf_photo_loss_weighted_fwd_bwd_host_scenes(const float *input, const float *photos,
+                                                              const float *weights, int weight_planes,
+                                                              const float *scenes_host, const float *xrow, float eps,
+                                                              float *loss_out, float *grad_input, void *workspace,
+                                                              size_t workspace_bytes, int B, int S, int H, int W,
+                                                              void *stream);
+SVBRDF_API int svbrdf_head_photo_loss_weighted_fwd_bwd(const float *encoded9, const float *photos, const float *weights,
+                                                       int weight_planes, const float *scenes, const float *xrow,
+                                                       float eps, float *loss_out, float *grad_encoded9, void *workspace,
+                                                       size_t workspace_bytes, int B, int S, int H, int W, void *stream);
+SVBRDF_API int svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes(const float *encoded9, const float *photos,
+                                                                   const float *weights, int weight_planes,
+                                                                   const float *scenes_host, const float *xrow, float eps,
+                                                                   float *loss_out, float *grad_encoded9,
+                                                                   void *workspace, size_t workspace_bytes, int B, int S,
+                                                                   int H, int W, void *stream);
+
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd
  * wrapper to apply the upstream gradient of the loss (the chain rule through

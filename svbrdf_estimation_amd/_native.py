@@ -42,6 +42,7 @@ def library_path():
 _fp, _int, _float, _size, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_ulonglong
 _DIMS = [_int] * 4 + [_fp]                                            # B, S (or R), H, W, stream
 _LOSS = [_fp] * 4 + [_float] + [_fp] * 3 + [_size] + _DIMS            # input, other, scenes, xrow, eps, loss, grad, ws, bytes
+_LOSS_W = [_fp] * 3 + [_int] + [_fp] * 2 + [_float] + [_fp] * 3 + [_size] + _DIMS   # input, photos, weights, planes, scenes, ...
 _LOSS_L1 = [_fp] * 4 + [_float] * 3 + [_fp] * 3 + [_size] + _DIMS     # ... eps, l1_weight, eps_l1 ...
 _INPUTS = [_fp] * 3 + [_u64] * 2 + [_fp] * 2 + _DIMS
 # name -> (restype, argtypes) of every SVBRDF_API function of include/svbrdf_hip.h, applied once in _load();
@@ -67,6 +68,10 @@ SIGNATURES = {
     "svbrdf_photo_loss_fwd_bwd_host_scenes": (_int, _LOSS),
     "svbrdf_head_photo_loss_fwd_bwd": (_int, _LOSS),
     "svbrdf_head_photo_loss_fwd_bwd_host_scenes": (_int, _LOSS),
+    "svbrdf_photo_loss_weighted_fwd_bwd": (_int, _LOSS_W),
+    "svbrdf_photo_loss_weighted_fwd_bwd_host_scenes": (_int, _LOSS_W),
+    "svbrdf_head_photo_loss_weighted_fwd_bwd": (_int, _LOSS_W),
+    "svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes": (_int, _LOSS_W),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
     "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
     "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
@@ -469,10 +474,11 @@ def _loss_scene_table(scenes, device, what):
     return scenes.contiguous(), on_host
 
 
-def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W):
+def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W, extra=()):
     """One launch of the fused-loss entry point `entry` (looked up on the loaded library): contiguous device tensors
     `input` and `other` (target maps or photos), the scene table as _loss_scene_table returned it, `floats` = eps
-    (and l1_weight, eps_l1 for the entries that take them).  -> (loss [1] device tensor, grad like `input` or None)"""
+    (and l1_weight, eps_l1 for the entries that take them), `extra` = what the entry takes between `other` and the scene
+    table (the weighted photo entries: weights pointer, plane count).  -> (loss [1] device tensor, grad like `input` or None)"""
     lib = _load()
     ws = _workspace(input.device, lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
     loss = torch.empty(1, dtype=torch.float32, device=input.device)
@@ -482,7 +488,7 @@ def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W)
     with _on_device(input.device):
         if hook is not None:
             hook("begin")
-        rc = getattr(lib, entry)(input.data_ptr(), other.data_ptr(), scenes.data_ptr(), xr.data_ptr(), *floats,
+        rc = getattr(lib, entry)(input.data_ptr(), other.data_ptr(), *extra, scenes.data_ptr(), xr.data_ptr(), *floats,
                                  loss.data_ptr(), grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel() * 8,
                                  B, S, H, W, _stream(input.device))
         if hook is not None:
@@ -527,13 +533,15 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
     return _fused_loss_call(entry, input.contiguous(), target.contiguous(), scenes, floats, want_grad, B, S, H, W)
 
 
-def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False):
+def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weights=None):
     """Fused photo loss (svbrdf_photo_loss_fwd_bwd*): mean |log(render(scenes[b,s], input[b]) + eps) - log(photos[b,s] + eps)|
     and d loss/d input in ONE launch.  input [B,12,H,W] and photos [B,S,3,H,W] device fp32; scenes [B,S,9] fp32 on the
     maps' device, or on the HOST (at most host_scenes_max_rows() rows ride in the launch's argument block, a larger table
     is uploaded).  With head=True `input` is the generator's [B,9,H,W] post-tanh output, the network head is decoded in
-    the kernel (svbrdf_head_photo_loss_fwd_bwd*) and the gradient has its 9 channels.  Returns (loss [1] device tensor,
-    grad or None)."""
+    the kernel (svbrdf_head_photo_loss_fwd_bwd*) and the gradient has its 9 channels.  ``weights``: per-pixel confidence
+    in [0, 1], float32 [B,S,H,W] (one plane per photo) or [B,1,H,W] (one per item, shared by its photos) on the maps'
+    device -- the svbrdf_*photo_loss_weighted_fwd_bwd* entries: sum of w |..| over B S 3 H W, a weight of exactly 0
+    excuses the photo value under it (NaN included).  Returns (loss [1] device tensor, grad or None)."""
     _require_device_f32(input, "input")
     _require_device_f32(photos, "photos")
     scenes, on_host = _loss_scene_table(scenes, input.device, "input, photos and scenes must be on the same device")
@@ -545,9 +553,20 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False):
     if tuple(photos.shape) != (B, S, 3, H, W):
         raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
                          % ((B, S, 3, H, W), tuple(photos.shape)))
-    entry = ("svbrdf_head_photo_loss_fwd_bwd" if head else "svbrdf_photo_loss_fwd_bwd") + ("_host_scenes" if on_host else "")
+    stem = "svbrdf_head_photo_loss" if head else "svbrdf_photo_loss"
+    extra = ()
+    if weights is not None:
+        _require_device_f32(weights, "weights")
+        if weights.device != input.device:
+            raise ValueError("input, photos and weights must be on the same device")
+        if tuple(weights.shape) not in ((B, S, H, W), (B, 1, H, W)):
+            raise ValueError("weights must be [B,S,H,W] = %s or [B,1,H,W] for these maps and photos, got %s"
+                             % ((B, S, H, W), tuple(weights.shape)))
+        weights = weights.contiguous()      # (kept alive by this frame until the launch is enqueued, stream-ordered)
+        stem, extra = stem + "_weighted", (weights.data_ptr(), int(weights.shape[1]))
+    entry = stem + "_fwd_bwd" + ("_host_scenes" if on_host else "")
     return _fused_loss_call(entry, input.contiguous(), photos.contiguous(), scenes, (ctypes.c_float(eps),), want_grad,
-                            B, S, H, W)
+                            B, S, H, W, extra)
 
 
 def mix_materials(svbrdf0, svbrdf1, alpha):

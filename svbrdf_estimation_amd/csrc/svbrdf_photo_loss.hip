@@ -30,10 +30,29 @@ __device__ __forceinline__ void photo_terms(const float ph[3], float s10, float 
     for (int k = 0; k < 3; ++k) bt[k] = fma_(ph[k], s10, ec);
 }
 
-// one (pixel, scene), tied roughness: loss_pixel_scene with the target shading replaced by the photo's three values
-template <bool WITH_GRAD, int DEFER>
+// The confidence weight of one (pixel, render) of the WEIGHTED kernels, checked once: a weight outside [0, 1] or NaN
+// becomes NaN (v_med3 + compare + select) and poisons the loss sum through weighted_term's FMA whatever the term is.
+__device__ __forceinline__ float checked_weight(float w)
+{
+    return (__builtin_amdgcn_fmed3f(w, 0.0f, 1.0f) == w) ? w : __builtin_nanf("");
+}
+
+// lsum += w |lg|.  fma(1, x, y) is x + y exactly: weights of all ones give the unweighted kernels' sum bit for bit.
+template <bool WEIGHTED>
+__device__ __forceinline__ void add_term(float w, float lg, float &lsum)
+{
+    if (WEIGHTED) lsum = fma_(w, fabsf(lg), lsum);
+    else lsum += fabsf(lg);
+}
+
+// one (pixel, scene), tied roughness: loss_pixel_scene with the target shading replaced by the photo's three values.
+// WEIGHTED: `w` is the render's checked weight and `inv_count` already carries it (w / N, folded once per render); a
+// weight of exactly 0 selects every term to exactly 0 -- whatever the photo holds, NaN included: 0 * NaN is never
+// formed -- and lg = 0 with M = 0 gives a gradient of exactly (+-)0.
+template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false>
 __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
-                                                  float s10, float eps, float inv_count, float &lsum, Grad &acc)
+                                                  float s10, float eps, float inv_count, float &lsum, Grad &acc,
+                                                  [[maybe_unused]] float w = 1.0f)
 {
     const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
     float bt[3];
@@ -53,17 +72,19 @@ __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const float lg = (b[k] != bt[k]) ? log2_(bt[k] * ib[k]) : 0.0f;
-        lsum += fabsf(lg);
+        const bool differ = WEIGHTED ? (b[k] != bt[k] && w != 0.0f) : (b[k] != bt[k]);
+        const float lg = differ ? log2_(bt[k] * ib[k]) : 0.0f;
+        add_term<WEIGHTED>(w, lg, lsum);
         g_rad[k] = loss_grad_of_b(K, lg, inv_count * ib[k]);
     }
     if (WITH_GRAD) shade_bwd<1, (DEFER & 1) != 0, (DEFER & 2) != 0, (DEFER & 4) != 0>(K, g, mi, di, li, Fi, fi, g_rad, acc);
 }
 
 // independent roughness channels: loss_pixel_scene_by_channel with the photo as the target side
-template <bool WITH_GRAD, int DEFER>
+template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false>
 __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
-                                                             float s10, float eps, float inv_count, float &lsum, Grad &acc)
+                                                             float s10, float eps, float inv_count, float &lsum, Grad &acc,
+                                                             [[maybe_unused]] float w = 1.0f)
 {
     const Dots di = dots(K, g, mi);
     const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
@@ -77,8 +98,9 @@ __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, co
         const float fi = fma_(Fi, li.GD - mi.dpi[k], mi.dpi[k]);
         const float b = fma_(fi, g.E[k] * di.LNp, ec);
         const float ib = rcp_(b);
-        const float lg = (b != bt) ? log2_(bt * ib) : 0.0f;
-        lsum += fabsf(lg);
+        const bool differ = WEIGHTED ? (b != bt && w != 0.0f) : (b != bt);
+        const float lg = differ ? log2_(bt * ib) : 0.0f;
+        add_term<WEIGHTED>(w, lg, lsum);
         if (WITH_GRAD) {
             const float gE = loss_grad_of_b(K, lg, inv_count * ib) * g.E[k];
             const float g_f = gE * di.LNp;
@@ -106,11 +128,19 @@ __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, co
     }
 }
 
-template <int NL, bool WITH_GRAD, int DEFER>
+template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false>
 __device__ __forceinline__ void photo_pixel_scene_any(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
-                                                      float s10, float eps, float inv_count, float &lsum, Grad &acc)
+                                                      float s10, float eps, float inv_count, float &lsum, Grad &acc,
+                                                      [[maybe_unused]] float w_raw = 1.0f)
 {
-    if (NL == 3)
+    if (WEIGHTED) {
+        const float w = checked_weight(w_raw);
+        const float icw = inv_count * w;        // the weight folded into 1/N once per render
+        if (NL == 3)
+            photo_pixel_scene_by_channel<WITH_GRAD, DEFER & 3, true>(K, g, mi, ph, s10, eps, icw, lsum, acc, w);
+        else
+            photo_pixel_scene<WITH_GRAD, DEFER, true>(K, g, mi, ph, s10, eps, icw, lsum, acc, w);
+    } else if (NL == 3)
         photo_pixel_scene_by_channel<WITH_GRAD, DEFER & 3>(K, g, mi, ph, s10, eps, inv_count, lsum, acc);
     else
         photo_pixel_scene<WITH_GRAD, DEFER>(K, g, mi, ph, s10, eps, inv_count, lsum, acc);
@@ -125,6 +155,19 @@ __device__ __forceinline__ void load_photo(const float *__restrict__ render_base
     for (int k = 0; k < 3; ++k) ph[k] = plane_load(pb, k);
 }
 
+// WEIGHTED: the render's confidence weight as a fourth load of the same back-to-back group.  Its plane lives in another
+// allocation, hence a second resource (scalar arithmetic, made in front of the group).
+__device__ __forceinline__ void load_photo_weight(const float *__restrict__ render_base, const float *__restrict__ weight_base,
+                                                  size_t plane, size_t pix, float ph[3], float &w)
+{
+    const PlaneBuf pb = plane_buf(render_base, 3, plane, pix);
+    const PlaneBuf wb = plane_buf(weight_base, 1, plane, pix);
+    __builtin_amdgcn_sched_barrier(0);      // both resources stand: nothing but the four loads from here to the caller's barrier
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ph[k] = plane_load(pb, k);
+    w = plane_load(wb, 0);
+}
+
 // Scene loop, software-pipelined like K3's (loss_scene_loop): the geometry of render s+1 is computed beside the shading /
 // loss / adjoint of render s, and the three photo values of render s+1 -- the only loads inside the loop -- are issued at
 // the top of the pass that shades render s: they have a whole pass (~200 VALU instructions) to arrive, and because they
@@ -136,27 +179,41 @@ __device__ __forceinline__ void load_photo(const float *__restrict__ render_base
 // empty asm that reads the three registers at the end of the issuing pass keeps the loads in that pass -- in front of its
 // scheduling barrier -- and puts their wait at its end (behind a second scheduling barrier: the empty asm may otherwise be
 // moved up), a whole pass of arithmetic behind the issue.
-#define SVBRDF_PHOTO_PIN(P) __builtin_amdgcn_sched_barrier(0); asm volatile("" ::"v"(P[0]), "v"(P[1]), "v"(P[2]));
-template <int NL, bool WITH_GRAD, int DEFER>
+// WEIGHTED: the weight of render s+1 travels with its photo values -- fourth load of the group, same prefetch distance,
+// pinned by the same empty asm -- and its pointer advances by the wave-uniform `wstride`: one plane ([B,S,H,W] weights) or
+// zero ([B,1,H,W]: the item's one plane, re-read from cache).
+#define SVBRDF_PHOTO_PIN(P, WT)                                                                                      \
+    __builtin_amdgcn_sched_barrier(0);                                                                               \
+    if (WEIGHTED) asm volatile("" ::"v"(P[0]), "v"(P[1]), "v"(P[2]), "v"(WT));                                       \
+    else asm volatile("" ::"v"(P[0]), "v"(P[1]), "v"(P[2]));
+#define SVBRDF_PHOTO_LOAD(P, WT)                                                                                     \
+    if (WEIGHTED) load_photo_weight(pp, wp, plane, pix, P, WT);                                                      \
+    else load_photo(pp, plane, pix, P);
+template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false>
 __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float y, const float *__restrict__ scp,
                                                   const float *sc_lds, const float *__restrict__ pp, size_t plane,
-                                                  size_t pix, int S, float eps, float inv_count, Grad &acc)
+                                                  size_t pix, int S, float eps, float inv_count, Grad &acc,
+                                                  [[maybe_unused]] const float *__restrict__ wp = nullptr,
+                                                  [[maybe_unused]] size_t wstride = 0, [[maybe_unused]] float poison = 0.0f)
 {
     constexpr int ST = 9;
-    float lsum = 0.0f;
+    // WEIGHTED: the sum starts from the maps' non-finite guard (+0, or NaN which every FMA below keeps) instead of holding
+    // it in a register of its own across the loop; 1/N stays a scalar operand of the one multiply per render that uses it
+    float lsum = WEIGHTED ? poison : 0.0f;
     const VConst K = make_vconst();
     const float s10 = vreg(0.0009765625f);      // 2^-10 (kLossScaleExp) as a VGPR operand of photo_terms' FMA
     eps = vreg(eps);
-    inv_count = vreg(inv_count);
+    if (!WEIGHTED) inv_count = vreg(inv_count);
     const size_t render = 3 * plane;            // floats per photo
     float sc[9];
     float pa[3], pb[3];
-    load_photo(pp, plane, pix, pa);             // render 0
+    [[maybe_unused]] float wa = 1.0f, wb = 1.0f;
+    SVBRDF_PHOTO_LOAD(pa, wa)                   // render 0
     if (WITH_GRAD) {
         load_scene(scp, sc);
         Geom ga = geometry<true>(K, sc, x, y), gb;
         load_scene(scp + (S > 1 ? ST : 0), sc);
-#define SVBRDF_PHOTO_PASS(G_CUR, G_NEXT, P_CUR, P_NEXT, SI)                                                           \
+#define SVBRDF_PHOTO_PASS(G_CUR, G_NEXT, P_CUR, P_NEXT, W_CUR, W_NEXT, SI)                                                        \
         {                                                                                                          \
             asm volatile("" ::"s"(sc[0]), "s"(sc[8]));                                                             \
             float cur[9];                                                                                          \
@@ -164,16 +221,18 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
             load_scene(scp + ((SI) + 2 < S ? 2 * ST : ((SI) + 1 < S ? ST : 0)), sc);                               \
             scp += ((SI) + 1 < S) ? ST : 0;                                                                        \
             pp += ((SI) + 1 < S) ? render : 0;          /* photo of render s+1 (a harmless repeat on the last pass) */ \
-            load_photo(pp, plane, pix, P_NEXT);                                                                    \
+            if (WEIGHTED) wp += ((SI) + 1 < S) ? wstride : 0;                                                      \
+            SVBRDF_PHOTO_LOAD(P_NEXT, W_NEXT)                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                                     \
             G_NEXT = geometry<true>(K, cur, x, y);                                                                 \
-            photo_pixel_scene_any<NL, WITH_GRAD, DEFER>(K, G_CUR, mi, P_CUR, s10, eps, inv_count, lsum, acc);      \
-            SVBRDF_PHOTO_PIN(P_NEXT)                                                                               \
+            photo_pixel_scene_any<NL, WITH_GRAD, DEFER, WEIGHTED>(K, G_CUR, mi, P_CUR, s10, eps, inv_count, lsum,  \
+                                                                  acc, W_CUR);                                     \
+            SVBRDF_PHOTO_PIN(P_NEXT, W_NEXT)                                                                       \
         }
         for (int s = 0;;) {
-            SVBRDF_PHOTO_PASS(ga, gb, pa, pb, s)
+            SVBRDF_PHOTO_PASS(ga, gb, pa, pb, wa, wb, s)
             if (++s >= S) break;
-            SVBRDF_PHOTO_PASS(gb, ga, pb, pa, s)
+            SVBRDF_PHOTO_PASS(gb, ga, pb, pa, wb, wa, s)
             if (++s >= S) break;
         }
 #undef SVBRDF_PHOTO_PASS
@@ -184,17 +243,20 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
         for (int s = 0; s < S; ++s) {
             const Geom g = g_next;
             pp += (s + 1 < S) ? render : 0;
-            load_photo(pp, plane, pix, pb);
+            if (WEIGHTED) wp += (s + 1 < S) ? wstride : 0;
+            SVBRDF_PHOTO_LOAD(pb, wb)
             __builtin_amdgcn_sched_barrier(0);      // (the scheduler otherwise sinks the three loads to their first use)
             load_scene(sc_lds + (s + 1 < S ? s + 1 : s) * 9, sc);
             g_next = geometry<true>(K, sc, x, y);
-            photo_pixel_scene_any<NL, WITH_GRAD, DEFER>(K, g, mi, pa, s10, eps, inv_count, lsum, acc);
-            SVBRDF_PHOTO_PIN(pb)
+            photo_pixel_scene_any<NL, WITH_GRAD, DEFER, WEIGHTED>(K, g, mi, pa, s10, eps, inv_count, lsum, acc, wa);
+            SVBRDF_PHOTO_PIN(pb, wb)
 #pragma unroll
             for (int k = 0; k < 3; ++k) pa[k] = pb[k];
+            if (WEIGHTED) wa = wb;
         }
     }
 #undef SVBRDF_PHOTO_PIN
+#undef SVBRDF_PHOTO_LOAD
     lsum *= 0.693147180559945309417f;       // the loop sums |log2|
     if (WITH_GRAD && DEFER) {               // the per-pixel constants the adjoint left out (shade_bwd's DEFER_*)
 #pragma unroll
@@ -211,12 +273,17 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
 // HEAD: `input` is the generator's [B,9,H,W] post-tanh output and `grad_input` its gradient: the network head
 // (decode_head / head_bwd, K3's own: svbrdf_head_loss_fwd_bwd) is folded in, 9 planes in and 9 out instead of 12 and 12.
 // Decoded roughness is one channel repeated, so only the tied scene loop is instantiated for it.
-template <bool WITH_GRAD, bool EARLY_COORDS, bool HEAD = false>
+// WEIGHTED: `weights` holds `weight_planes` = S ([B,S,H,W]) or 1 ([B,1,H,W]) confidence planes per item.  A zero weight
+// deselects the shading's value, so the non-finite guard of the maps is ALSO added to the pixel's loss sum: a weight does
+// not excuse the maps.
+template <bool WITH_GRAD, bool EARLY_COORDS, bool HEAD = false, bool WEIGHTED = false>
 __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input, const float *__restrict__ photos,
                                                 const float *__restrict__ scenes, const float *__restrict__ xrow,
                                                 float eps, float inv_count, double loss_scale, float fixed_scale,
                                                 float *__restrict__ grad_input, unsigned long long *__restrict__ ws,
-                                                float *__restrict__ loss_out, int S, int H, int W)
+                                                float *__restrict__ loss_out, int S, int H, int W,
+                                                [[maybe_unused]] const float *__restrict__ weights = nullptr,
+                                                [[maybe_unused]] int weight_planes = 0)
 {
     extern __shared__ __attribute__((aligned(16))) float sc_lds[];      // [S][9], forward-only kernels
     const size_t plane = (size_t)H * W;
@@ -233,6 +300,7 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
         Grad acc;
         [[maybe_unused]] Head head;
         [[maybe_unused]] float head_chk = 0.0f;
+        [[maybe_unused]] float poison = 0.0f;       // WEIGHTED: +0 for finite maps, NaN otherwise; added to the loss sum
         // pixel coordinates issued in front of the plane loads (by-value-table kernels, power-of-two width): see
         // rendering_loss_body
         [[maybe_unused]] float x_early = 0.0f, y_early = 0.0f;
@@ -253,6 +321,8 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
             // the guard below, from the encoded values that feed the normal and the roughness (each on its own: a sum
             // of large finite values must not overflow into a NaN report)
             head_chk = ((e[0] - e[0]) + (e[1] - e[1])) + (e[5] - e[5]);
+            if (WEIGHTED)       // the diffuse and specular planes too: their way through the arithmetic ends at a select
+                poison = (((e[2] - e[2]) + (e[3] - e[3])) + ((e[4] - e[4]) + (e[6] - e[6]))) + ((e[7] - e[7]) + (e[8] - e[8]));
         } else {
             load_maps_k3(input + (size_t)b * 12 * plane, plane, pix, in);
         }
@@ -276,15 +346,29 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
             // specular and the photo values propagate through the arithmetic by themselves.
             if (HEAD) {
                 x[0] += head_chk;
+                if (WEIGHTED) poison += head_chk;
             } else {
                 const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
                 x[0] += chk - chk;
+                if (WEIGHTED) {
+                    const float ds = ((in.d[0] + in.d[1]) + (in.d[2] + in.s[0])) + (in.s[1] + in.s[2]);
+                    poison = (chk - chk) + (ds - ds);
+                }
             }
         }
         const float *__restrict__ scp = scenes + (size_t)b * S * 9;
         const float *__restrict__ pp = photos + (size_t)b * S * 3 * plane;
         constexpr int kDefer = WITH_GRAD ? 7 : 0;
-        if (HEAD || __all(tied))     // wave-uniform
+        if (WEIGHTED) {
+            const float *__restrict__ wp = weights + (size_t)b * weight_planes * plane;
+            const size_t wstride = weight_planes == 1 ? 0 : plane;
+            if (HEAD || __all(tied))
+                lsum = photo_scene_loop<1, WITH_GRAD, kDefer, true>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps,
+                                                                    inv_count, acc, wp, wstride, poison);
+            else
+                lsum = photo_scene_loop<3, WITH_GRAD, kDefer & 3, true>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps,
+                                                                        inv_count, acc, wp, wstride, poison);
+        } else if (HEAD || __all(tied))     // wave-uniform
             lsum = photo_scene_loop<1, WITH_GRAD, kDefer>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc);
         else
             lsum = photo_scene_loop<3, WITH_GRAD, kDefer & 3>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc);
@@ -365,6 +449,72 @@ __global__ SVBRDF_PHOTO_LOSS_ATTRS void k_head_photo_inl([[maybe_unused]] const 
                                            grad_encoded9, ws, loss_out, S, H, W);
 }
 
+// The WEIGHTED kernels (svbrdf_*photo_loss_weighted_fwd_bwd*): the same four shapes with `weights` and its plane count.
+// (Names that hold neither "k_photo_loss" nor "k_head_photo": the unweighted kernels are counted by those.)
+#define SVBRDF_WPHOTO_KERNEL(NAME, EARLY, HEAD)                                                                       \
+    template <bool WITH_GRAD>                                                                                         \
+    __global__ SVBRDF_PHOTO_LOSS_ATTRS void NAME(const float *__restrict__ input, const float *__restrict__ photos,   \
+                                                 const float *__restrict__ weights, int weight_planes,                \
+                                                 const float *__restrict__ scenes, const float *__restrict__ xrow,    \
+                                                 float eps, float inv_count, double loss_scale, float fixed_scale,    \
+                                                 float *__restrict__ grad_input, unsigned long long *__restrict__ ws, \
+                                                 float *__restrict__ loss_out, int S, int H, int W)                   \
+    {                                                                                                                 \
+        photo_loss_body<WITH_GRAD, EARLY, HEAD, true>(input, photos, scenes, xrow, eps, inv_count, loss_scale,        \
+                                                      fixed_scale, grad_input, ws, loss_out, S, H, W, weights,        \
+                                                      weight_planes);                                                 \
+    }
+#define SVBRDF_WPHOTO_KERNEL_INL(NAME, HEAD)                                                                          \
+    template <bool WITH_GRAD>                                                                                         \
+    __global__ SVBRDF_PHOTO_LOSS_ATTRS void NAME([[maybe_unused]] const SceneBlock table,                             \
+                                                 const float *__restrict__ input, const float *__restrict__ photos,   \
+                                                 const float *__restrict__ weights, int weight_planes,                \
+                                                 const float *__restrict__ xrow, float eps, float inv_count,          \
+                                                 double loss_scale, float fixed_scale,                                \
+                                                 float *__restrict__ grad_input, unsigned long long *__restrict__ ws, \
+                                                 float *__restrict__ loss_out, int S, int H, int W)                   \
+    {                                                                                                                 \
+        const float *__restrict__ rows = (const float *)__builtin_amdgcn_kernarg_segment_ptr();                       \
+        photo_loss_body<WITH_GRAD, true, HEAD, true>(input, photos, rows, xrow, eps, inv_count, loss_scale,           \
+                                                     fixed_scale, grad_input, ws, loss_out, S, H, W, weights,         \
+                                                     weight_planes);                                                  \
+    }
+SVBRDF_WPHOTO_KERNEL(k_wphoto, false, false)
+SVBRDF_WPHOTO_KERNEL_INL(k_wphoto_inl, false)
+SVBRDF_WPHOTO_KERNEL(k_head_wphoto, false, true)
+SVBRDF_WPHOTO_KERNEL_INL(k_head_wphoto_inl, true)
+#undef SVBRDF_WPHOTO_KERNEL
+#undef SVBRDF_WPHOTO_KERNEL_INL
+
+template <bool G, bool HEAD>
+void launch_wphoto(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st, const float *input, const float *photos,
+                   const float *weights, int weight_planes, const float *scenes, const float *xrow, float eps,
+                   float inv_count, double loss_scale, float fixed_scale, float *grad_input, unsigned long long *ws,
+                   float *loss_out, int B, int S, int H, int W)
+{
+    if (rows) {
+        SceneBlock block_arg;      // only the first B*S rows are ever read
+        std::memcpy(block_arg.v, rows, (size_t)B * S * 9 * sizeof(float));
+        if (HEAD)
+            hipLaunchKernelGGL((k_head_wphoto_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos,
+                               weights, weight_planes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
+                               loss_out, S, H, W);
+        else
+            hipLaunchKernelGGL((k_wphoto_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos,
+                               weights, weight_planes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
+                               loss_out, S, H, W);
+    } else {
+        if (HEAD)
+            hipLaunchKernelGGL((k_head_wphoto<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, weights,
+                               weight_planes, scenes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
+                               loss_out, S, H, W);
+        else
+            hipLaunchKernelGGL((k_wphoto<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, weights,
+                               weight_planes, scenes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
+                               loss_out, S, H, W);
+    }
+}
+
 template <bool G, bool HEAD>
 void launch_photo(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st, const float *input, const float *photos,
                   const float *scenes, const float *xrow, float eps, float inv_count, double loss_scale, float fixed_scale,
@@ -414,9 +564,76 @@ int photo_impl(const char *who, bool scenes_on_host, bool head, const float *inp
     return launch_status(who);
 }
 
+// The weighted entries: the same plan (a weight in [0, 1] keeps a term within plan_loss's bound of 32, so the fixed-point
+// scale stands), `weights` among the required pointers, `weight_planes` 1 or S -- all before any launch.
+int wphoto_impl(const char *who, bool scenes_on_host, bool head, const float *input, const float *photos,
+                const float *weights, int weight_planes, const float *scenes, const float *xrow, float eps, float *loss_out,
+                float *grad_input, void *workspace, size_t workspace_bytes, int B, int S, int H, int W, void *stream)
+{
+    LossPlan p;
+    if (int e = plan_loss(who, scenes_on_host, {input, photos, weights, scenes, xrow, loss_out}, grad_input, workspace,
+                          workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
+    if (weight_planes != 1 && weight_planes != S) {
+        char text[200];
+        std::snprintf(text, sizeof(text), "%s: weight_planes must be 1 (one plane per item) or S (one per photo)", who);
+        return fail(SVBRDF_ERR_DIMS, text);
+    }
+    const float *rows = scenes_on_host ? scenes : nullptr;
+#define SVBRDF_LAUNCH_WPHOTO(G, HD)                                                                                     \
+    launch_wphoto<G, HD>(rows, p.grid, p.lds_bytes, static_cast<hipStream_t>(stream), input, photos, weights,          \
+                         weight_planes, scenes, xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, grad_input, p.ws, \
+                         loss_out, B, S, H, W)
+    if (head) {
+        if (grad_input) SVBRDF_LAUNCH_WPHOTO(true, true);
+        else SVBRDF_LAUNCH_WPHOTO(false, true);
+    } else {
+        if (grad_input) SVBRDF_LAUNCH_WPHOTO(true, false);
+        else SVBRDF_LAUNCH_WPHOTO(false, false);
+    }
+#undef SVBRDF_LAUNCH_WPHOTO
+    return launch_status(who);
+}
+
 }  // namespace
 
 extern "C" {
+
+// Per-pixel confidence weights (added to ABI version 8 without a bump: see include/svbrdf_hip.h)
+int svbrdf_photo_loss_weighted_fwd_bwd(const float *input, const float *photos, const float *weights, int weight_planes,
+                                       const float *scenes, const float *xrow, float eps, float *loss_out,
+                                       float *grad_input, void *workspace, size_t workspace_bytes, int B, int S, int H,
+                                       int W, void *stream)
+{
+    return wphoto_impl("photo_loss_weighted", false, false, input, photos, weights, weight_planes, scenes, xrow, eps,
+                       loss_out, grad_input, workspace, workspace_bytes, B, S, H, W, stream);
+}
+
+int svbrdf_photo_loss_weighted_fwd_bwd_host_scenes(const float *input, const float *photos, const float *weights,
+                                                   int weight_planes, const float *scenes_host, const float *xrow,
+                                                   float eps, float *loss_out, float *grad_input, void *workspace,
+                                                   size_t workspace_bytes, int B, int S, int H, int W, void *stream)
+{
+    return wphoto_impl("photo_loss_weighted_host_scenes", true, false, input, photos, weights, weight_planes, scenes_host,
+                       xrow, eps, loss_out, grad_input, workspace, workspace_bytes, B, S, H, W, stream);
+}
+
+int svbrdf_head_photo_loss_weighted_fwd_bwd(const float *encoded9, const float *photos, const float *weights,
+                                            int weight_planes, const float *scenes, const float *xrow, float eps,
+                                            float *loss_out, float *grad_encoded9, void *workspace, size_t workspace_bytes,
+                                            int B, int S, int H, int W, void *stream)
+{
+    return wphoto_impl("head_photo_loss_weighted", false, true, encoded9, photos, weights, weight_planes, scenes, xrow, eps,
+                       loss_out, grad_encoded9, workspace, workspace_bytes, B, S, H, W, stream);
+}
+
+int svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes(const float *encoded9, const float *photos, const float *weights,
+                                                        int weight_planes, const float *scenes_host, const float *xrow,
+                                                        float eps, float *loss_out, float *grad_encoded9, void *workspace,
+                                                        size_t workspace_bytes, int B, int S, int H, int W, void *stream)
+{
+    return wphoto_impl("head_photo_loss_weighted_host_scenes", true, true, encoded9, photos, weights, weight_planes,
+                       scenes_host, xrow, eps, loss_out, grad_encoded9, workspace, workspace_bytes, B, S, H, W, stream);
+}
 
 int svbrdf_photo_loss_fwd_bwd(const float *input, const float *photos, const float *scenes, const float *xrow, float eps,
                               float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes, int B, int S,

@@ -288,11 +288,11 @@ class _FusedPhotoLoss(torch.autograd.Function):
     ``head``: ``input`` is the generator's [B,9,H,W] post-tanh output, decoded in the kernel (HeadPhotoLoss)."""
 
     @staticmethod
-    def forward(ctx, input, photos, scenes, eps, head):
+    def forward(ctx, input, photos, scenes, eps, head, weights=None):
         need_in = ctx.needs_input_grad[0]
         ctx.save_for_backward(input, photos)        # (for backward(create_graph=True) only: references, no copies)
-        ctx.second_order = (scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head))
-        loss, grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head)
+        ctx.second_order = (scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head), weights)
+        loss, grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights)
         ctx.grads = None if grad is None else (grad,)
         return loss.view(())
 
@@ -302,16 +302,16 @@ class _FusedPhotoLoss(torch.autograd.Function):
             # backward(create_graph=True): the kernel's gradient is a constant to autograd; differentiate the composed
             # definition instead (same scenes), in float64 like the other fused losses do
             input, photos = ctx.saved_tensors
-            scenes, eps, head = ctx.second_order
+            scenes, eps, head, weights = ctx.second_order
             with torch.enable_grad():
                 x = input.to(torch.float64)
-                loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes, eps)
+                loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes, eps, weights)
                 g, = torch.autograd.grad(loss, [input], grad_loss.to(torch.float64).reshape(()), create_graph=True)
-            return g.to(input.dtype), None, None, None, None
+            return g.to(input.dtype), None, None, None, None, None
         grad, = _hand_over_gradients(ctx, grad_loss, "Trying to backward through the fused photo loss a second time: its "
                                      "gradient buffer was handed to the first backward.  Specify retain_graph=True for "
                                      "the first one.")
-        return grad, None, None, None, None
+        return grad, None, None, None, None, None
 
 
 class _PhotoLossTensor(_UnitGradientLoss):
@@ -342,12 +342,71 @@ def _is_unit_gradient(grad):
     return t is not None and grad.data_ptr() == t.data_ptr() and t._version == 0 and grad.dtype == torch.float32
 
 
-def composed_photo_loss(input, photos, scenes, eps):
+def weighted_log_l1(rendered, photos, eps, weights):
+    """The weighted photo loss of given renderings, literally as specified: with w in [0, 1] broadcast over the colour
+    channels, N the number of terms and p' = where(w > 0, photo, 0),
+
+        (1/N) sum w | log(rendered + eps) - log(p' + eps) |
+
+    ``rendered`` and ``photos`` [B,S,3,H,W], ``weights`` [B,S,H,W] or [B,1,H,W].  The photo is REPLACED under a zero
+    weight before anything is computed from it, so a NaN there reaches neither the loss nor, through 0 * NaN, autograd."""
+    w = weights.to(rendered.dtype).unsqueeze(2)                              # [B,S|1,1,H,W]
+    p = photos.to(rendered.dtype)
+    p = torch.where((w > 0).expand_as(p), p, torch.zeros((), dtype=p.dtype, device=p.device))
+    return (w * (torch.log(rendered + eps) - torch.log(p + eps)).abs()).sum() / rendered.numel()
+
+
+def composed_photo_loss(input, photos, scenes, eps, weights=None):
     """The photo loss from differentiable pieces -- S renders per item through K1 / K2 (``renderers._RenderFunction``:
     float32 maps through the float32 kernels, float64 maps through the float64 ones), log / L1 mean by torch.  What float64
-    maps take and what ``backward(create_graph=True)`` of the fused loss differentiates.  ``scenes`` [B,S,9] float32."""
+    maps take and what ``backward(create_graph=True)`` of the fused loss differentiates.  ``scenes`` [B,S,9] float32.
+    ``weights`` ([B,S,H,W] or [B,1,H,W], or None): the weighted definition, ``weighted_log_l1``."""
     rendered = renderers._RenderFunction.apply(input, scenes)
+    if weights is not None:
+        return weighted_log_l1(rendered, photos, eps, weights)
     return nn.functional.l1_loss(torch.log(rendered + eps), torch.log(photos.to(rendered.dtype) + eps))
+
+
+_NORMALIZE = ("count", "weights")
+_WEIGHT_SUM_FLOOR = 2.0 ** -126      # the "tiny" of normalize="weights": the smallest normal float32, one weight's worth
+
+
+def _check_weights(weights, input, photos):
+    """``weights`` as the photo losses take them -> float32 [B,S,H,W] or [B,1,H,W] (None passes).  ``photos`` [B,S,3,H,W]"""
+    if weights is None:
+        return None
+    if not isinstance(weights, torch.Tensor):
+        raise TypeError("weights must be a tensor")
+    B, S, _, H, W = photos.shape
+    if weights.dim() == 5 and tuple(weights.shape) == (B, S, 3, H, W):
+        raise ValueError("per-channel weights [B,S,3,H,W] are not supported: one weight serves the three channels of a "
+                         "pixel -- take the minimum over the channels (weights.amin(dim=2))")
+    if weights.dim() == 3:
+        weights = weights.unsqueeze(1)              # [B,H,W]: one plane per item, shared by its photos
+    if tuple(weights.shape) not in ((B, S, H, W), (B, 1, H, W)):
+        raise ValueError("weights must be [B,S,H,W], [B,1,H,W] or [B,H,W] with the photos' B, S, H and W, got %s"
+                         % (tuple(weights.shape),))
+    if weights.requires_grad:
+        raise RuntimeError("the photo losses have no gradient w.r.t. the weights: pass weights.detach()")
+    if weights.device != input.device:
+        raise ValueError("input and weights must be on the same device")
+    if weights.dtype in (torch.bool, torch.uint8):
+        weights = weights.to(torch.float32)
+    if weights.dtype != torch.float32:
+        raise TypeError("weights must be float32, bool or uint8 (got %s)" % weights.dtype)
+    return weights
+
+
+def _normalized(loss, weights, photos, normalize):
+    """normalize="weights": the fused mean over all N terms -> the weighted mean sum w|d| / (3 sum w), sum w over the
+    broadcast [B,S,H,W] weights.  Stock torch ops on the device, no host sync; 0 when every weight is 0."""
+    if weights is None or normalize == "count":
+        return loss
+    B, S, _, H, W = photos.shape
+    total = weights.sum(dtype=torch.float64) * (3.0 * S / weights.shape[1])       # 3 sum w, shared planes counted S times
+    # (the floor only binds when every weight is 0 -- then the loss is exactly 0 and N / floor must stay finite)
+    scale = float(B * S * 3 * H * W) / total.clamp_min(_WEIGHT_SUM_FLOOR)
+    return (loss.to(torch.float64) * scale).to(loss.dtype)
 
 
 def _check_fused_photo_inputs(loss_name, input_name, input, photos):
@@ -377,12 +436,26 @@ class PhotoLoss(nn.Module):
     With this package's ``LocalRenderer`` and float32 maps on a ROCm device it is ONE fused HIP kernel (forward and the
     analytic backward; csrc/svbrdf_photo_loss.hip).  Any other renderer object, float64 maps and
     ``backward(create_graph=True)`` take the composed definition: ``renderer.render`` per scene, ``log``, L1 mean --
-    which is also the semantic specification of the fused path."""
+    which is also the semantic specification of the fused path.
 
-    def __init__(self, renderer, eps=0.1):
+    ``weights`` (optional): a confidence in [0, 1] per photo pixel, for captured photographs whose clipped highlights,
+    pixels outside the patch, noise-floor shadows or invalid (NaN) pixels must not vote -- ``[B,S,H,W]`` (one plane per
+    photo), ``[B,1,H,W]`` or ``[B,H,W]`` (one plane per item, shared by its photos); float32, or bool / uint8 masks.  The
+    loss becomes ``(1/N) sum w |log(render + eps) - log(p' + eps)|`` with ``p' = where(w > 0, photo, 0)``
+    (``weighted_log_l1``): a weight of exactly 0 excuses the photo value under it -- term and gradient exactly 0 even
+    where the photo is NaN or infinite -- but never the maps; a weight that is NaN, negative or above 1 gives a NaN loss;
+    weights of all ones give the unweighted loss and gradient bit for bit.  Still one launch, one more load per
+    pixel-render.  ``normalize="count"`` (default) divides by the number N = B S 3 H W of terms as above;
+    ``normalize="weights"`` returns the weighted mean ``sum w|d| / (3 sum w)`` instead (0 when every weight is 0), which
+    costs a reduction over the weights and a scale of the loss on the device (two small launches, no host sync)."""
+
+    def __init__(self, renderer, eps=0.1, normalize="count"):
         super().__init__()
+        if normalize not in _NORMALIZE:
+            raise ValueError("normalize must be one of %s, got %r" % (_NORMALIZE, normalize))
         self.renderer = renderer
         self.eps = eps
+        self.normalize = normalize
 
     def uses_fused_kernel(self):
         return RenderingLoss(self.renderer).uses_fused_kernel()
@@ -430,21 +503,36 @@ class PhotoLoss(nn.Module):
         rows = PhotoLoss._scene_objects(scenes, B, S)
         return torch.stack([torch.stack([environment.scene_to_row(sc) for sc in r]) for r in rows])
 
-    def forward(self, input, photos, scenes):
+    def forward(self, input, photos, scenes, weights=None):
         photos = self._check(input, photos)
         B, S = photos.shape[0], photos.shape[1]
+        if weights is None:
+            if not self.uses_fused_kernel():
+                return self._forward_plugin(input, photos, self._scene_objects(scenes, B, S))
+            table = self._scene_table(scenes, B, S)
+            if _check_fused_photo_inputs("PhotoLoss", "input", input, photos):
+                return composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps)     # float64 K1 / K2
+            loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps), False)
+            return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
+        weights = _check_weights(weights, input, photos)
         if not self.uses_fused_kernel():
-            return self._forward_plugin(input, photos, self._scene_objects(scenes, B, S))
-        table = self._scene_table(scenes, B, S)
-        if _check_fused_photo_inputs("PhotoLoss", "input", input, photos):
-            return composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps)     # float64 K1 / K2
-        loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps), False)
-        return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
+            loss = self._forward_plugin(input, photos, self._scene_objects(scenes, B, S), weights)
+        else:
+            table = self._scene_table(scenes, B, S)
+            if _check_fused_photo_inputs("PhotoLoss", "input", input, photos):
+                loss = composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps, weights)
+            else:
+                loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps), False, weights)
+                if self.normalize == "count" and loss.requires_grad:
+                    return loss.as_subclass(_PhotoLossTensor)
+        return _normalized(loss, weights, photos, self.normalize)
 
-    def _forward_plugin(self, input, photos, scenes):
+    def _forward_plugin(self, input, photos, scenes, weights=None):
         """the composed definition with a foreign renderer object: its own render() per scene, log, L1 mean"""
         rendered = torch.stack([torch.cat([self.renderer.render(sc, input[b]) for sc in scenes[b]], dim=0)
                                 for b in range(input.shape[0])], dim=0)
+        if weights is not None:
+            return weighted_log_l1(rendered, photos, self.eps, weights)
         return nn.functional.l1_loss(torch.log(rendered + self.eps), torch.log(photos + self.eps))
 
 
@@ -508,23 +596,38 @@ class HeadPhotoLoss(nn.Module):
     and the gradient w.r.t. the NINE encoded channels are ONE fused HIP kernel (csrc/svbrdf_photo_loss.hip: 9 planes in,
     9 out, no 12-channel map tensor, none of the head's elementwise launches).  Any other renderer object, float64 on
     either side and ``backward(create_graph=True)`` take the composed definition above, which is also the specification
-    of the fused path."""
+    of the fused path.  ``weights`` and ``normalize``: per-pixel confidence, exactly as ``PhotoLoss`` documents them."""
 
-    def __init__(self, renderer, eps=0.1):
+    def __init__(self, renderer, eps=0.1, normalize="count"):
         super().__init__()
+        if normalize not in _NORMALIZE:
+            raise ValueError("normalize must be one of %s, got %r" % (_NORMALIZE, normalize))
         self.renderer = renderer
         self.eps = eps
+        self.normalize = normalize
 
     def uses_fused_kernel(self):
         return RenderingLoss(self.renderer).uses_fused_kernel()
 
-    def forward(self, encoded9, photos, scenes):
+    def forward(self, encoded9, photos, scenes, weights=None):
         photos = PhotoLoss._check(encoded9, photos, channels=9)
-        composed = PhotoLoss(self.renderer, self.eps)
+        if weights is None:
+            composed = PhotoLoss(self.renderer, self.eps)
+            if not self.uses_fused_kernel():
+                return composed(decode_head(encoded9), photos, scenes)
+            table = PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
+            if _check_fused_photo_inputs("HeadPhotoLoss", "encoded9", encoded9, photos):
+                return composed(decode_head(encoded9.to(torch.float64)), photos, table)     # promoted in front of the decode
+            loss = _FusedPhotoLoss.apply(encoded9, photos, table, float(self.eps), True)
+            return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
+        weights = _check_weights(weights, encoded9, photos)
+        composed = PhotoLoss(self.renderer, self.eps, self.normalize)
         if not self.uses_fused_kernel():
-            return composed(decode_head(encoded9), photos, scenes)
+            return composed(decode_head(encoded9), photos, scenes, weights)
         table = PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
         if _check_fused_photo_inputs("HeadPhotoLoss", "encoded9", encoded9, photos):
-            return composed(decode_head(encoded9.to(torch.float64)), photos, table)     # promoted in front of the decode
-        loss = _FusedPhotoLoss.apply(encoded9, photos, table, float(self.eps), True)
-        return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
+            return composed(decode_head(encoded9.to(torch.float64)), photos, table, weights)
+        loss = _FusedPhotoLoss.apply(encoded9, photos, table, float(self.eps), True, weights)
+        if self.normalize == "count" and loss.requires_grad:
+            return loss.as_subclass(_PhotoLossTensor)
+        return _normalized(loss, weights, photos, self.normalize)

@@ -1,6 +1,6 @@
 """The fused photo loss against K3 and against the composed form, one process, one box (profiles/r09_photo_loss.txt).
 
-    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...] [--head]
+    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...] [--head] [--weights {none,shared,per-photo}]
 
 At the configuration-2 shape (B = 8, 256 x 256, S = 9, scene table by value, six batches rotating beyond the 256 MB
 Infinity Cache, as bench.py does) it prints the event-timed median per launch of
@@ -17,6 +17,12 @@ wave so that the stream runs them back to back, an event between every two, medi
 [B,9,H,W] output in, its gradient out), the 12-channel photo kernel on the decoded maps and the unfused composition
 PhotoLoss(decode_head(x)) forward + backward through autograd, same shape, one process
 (tests/head_photo_checks.py::measure_head_photo_loss, the method of tests/test_gpu_head_photo_loss.py's speed test).
+
+--weights shared | per-photo: the weighted leg instead -- the photo loss with per-pixel confidence weights
+(svbrdf_photo_loss_weighted_fwd_bwd_host_scenes; one [B,1,H,W] plane per item or one [B,S,H,W] plane per photo), the
+unweighted kernel on the same maps and photos and the unfused weighted composition (K1, the torch ops of the definition and
+their backward, K2), same shape, one process (tests/weighted_photo_checks.py::measure_weighted_photo_loss, the method of
+tests/test_gpu_weighted_photo_loss.py's speed test).  `none` (default) is the unweighted report.
 
 --variants: other builds of the library (tools/build_variant.sh, e.g. the photo-loss unit compiled with another of the
 Makefile's scheduler sets), each measured in a child process of its own on this box, interleaved with the shipped build.
@@ -45,13 +51,14 @@ def isa_lines():
     subprocess.check_call(cmd, cwd=csrc, stderr=subprocess.DEVNULL)
     text, lines = open(out).read(), []
     for k in sorted(isa_stats.kernels(text)):
-        if "k_photo_loss" not in k and "k_head_photo" not in k:
+        if "k_photo_loss" not in k and "k_head_photo" not in k and "wphoto" not in k:
             continue
         _, meta, _, loops, _, _ = isa_stats.analyse(text, k)
         per = 2 if "ILb1E" in k else 1
         for c in sorted((c for c in loops if c["trans"]), key=lambda c: c["valu"]):
-            lines.append("%-24s %s loop: %5.1f VALU, %4.1f transcendentals per pixel-render; %s VGPRs, scratch %s" % (
-                ("head " if "k_head_photo" in k else "") + ("by-value" if "_inl" in k else "device") + (" fwd+bwd" if per == 2 else " fwd only"),
+            lines.append("%-33s %s loop: %5.1f VALU, %4.1f transcendentals per pixel-render; %s VGPRs, scratch %s" % (
+                ("weighted " if "wphoto" in k else "") + ("head " if "k_head_" in k else "") + ("by-value" if "_inl" in k else "device")
+                + (" fwd+bwd" if per == 2 else " fwd only"),
                 "tied  " if c["trans"] / per < 14 else "untied", c["valu"] / per, c["trans"] / per, meta.get("NumVgprs"),
                 meta.get("ScratchSize")))
     return lines
@@ -80,12 +87,15 @@ def measure_composed(dev, native, sets=6, n=30, rounds=3):
                             for _ in range(rounds)]))
 
 
-def child(head=False):
+def child(head=False, weights="none"):
     import torch
     from svbrdf_estimation_amd import _native
     import test_gpu_photo_loss as T
     dev = torch.device("cuda:0")
-    if head:
+    if weights != "none":
+        import weighted_photo_checks
+        res = weighted_photo_checks.measure_weighted_photo_loss(dev, _native, weights)
+    elif head:
         import head_photo_checks
         res = head_photo_checks.measure_head_photo_loss(dev, _native)
     else:
@@ -101,10 +111,14 @@ def main():
     ap.add_argument("--variants", nargs="*", default=[], metavar="TAG=LIB")
     ap.add_argument("--passes", type=int, default=1, help="how often the builds are measured in turn")
     ap.add_argument("--head", action="store_true", help="the head leg: fused head photo loss, 12-channel kernel, unfused composition")
+    ap.add_argument("--weights", choices=("none", "shared", "per-photo"), default="none",
+                    help="the weighted leg: weighted photo loss, unweighted kernel, unfused weighted composition")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.head and args.weights != "none":
+        ap.error("--head and --weights measure different legs: give one of them")
     if args.child:
-        return child(args.head)
+        return child(args.head, args.weights)
     builds = [("shipped", None)] + [tuple(v.split("=", 1)) for v in args.variants]
     rows = []
     for p in range(args.passes):
@@ -112,7 +126,8 @@ def main():
             env = dict(os.environ)
             if lib:
                 env["SVBRDF_HIP_LIB"] = os.path.abspath(lib)
-            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"] + (["--head"] if args.head else []), env=env, text=True, timeout=300,
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--weights", args.weights]
+                                 + (["--head"] if args.head else []), env=env, text=True, timeout=300,
                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
             line = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")]
             if out.returncode != 0 or not line:
@@ -120,7 +135,19 @@ def main():
                 raise SystemExit("measurement of build %r failed (exit status %s): nothing more is started" % (tag, out.returncode))
             rows.append((tag, p, json.loads(line[0][7:])))
     B, H, S = 8, 256, 9
-    if args.head:
+    if args.weights != "none":
+        P = rows[0][2]["planes"]
+        lines = ["# tools/photo_loss_bench.py --weights %s on %s; B = %d, %d x %d, S = %d, scene table by value, %d rotating batches" % (
+            args.weights, rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
+            "# medians of event-timed steps (us per step); algorithmic bytes of the weighted photo loss (12 + 3 S + P + 12) * 4 * H * W * B "
+            "= %.1f MB with P = %d weight planes per item" % ((12 + 3 * S + P + 12) * 4 * H * H * B / 1e6, P)]
+        for tag, p, r in rows:
+            lines.append("%-16s pass %d: weighted photo loss %7.2f  unweighted %7.2f (ratio %.3f; byte ratio %.3f)  unfused weighted "
+                         "composition fwd + bwd %8.2f   weighted = %.3f of 8 TB/s, %.1fx the composition   rounds %s" % (
+                             tag, p, r["weighted_us"], r["unweighted_us"], r["weighted_us"] / r["unweighted_us"],
+                             (12 + 3 * S + P + 12) / (12 + 3 * S + 12.0), r["composition_us"], r["weighted_frac_of_8TBps"],
+                             r["composition_us"] / r["weighted_us"], r["rounds"]))
+    elif args.head:
         lines = ["# tools/photo_loss_bench.py --head on %s; B = %d, %d x %d, S = %d, scene table by value, %d rotating batches" % (
             rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
             "# medians of event-timed steps (us per step); algorithmic bytes of the head photo loss (9 + 3 S + 9) * 4 * H * W * B = %.1f MB"
