@@ -486,111 +486,61 @@ SVBRDF_WPHOTO_KERNEL_INL(k_head_wphoto_inl, true)
 #undef SVBRDF_WPHOTO_KERNEL
 #undef SVBRDF_WPHOTO_KERNEL_INL
 
-template <bool G, bool HEAD>
-void launch_wphoto(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st, const float *input, const float *photos,
-                   const float *weights, int weight_planes, const float *scenes, const float *xrow, float eps,
-                   float inv_count, double loss_scale, float fixed_scale, float *grad_input, unsigned long long *ws,
-                   float *loss_out, int B, int S, int H, int W)
-{
-    if (rows) {
-        SceneBlock block_arg;      // only the first B*S rows are ever read
-        std::memcpy(block_arg.v, rows, (size_t)B * S * 9 * sizeof(float));
-        if (HEAD)
-            hipLaunchKernelGGL((k_head_wphoto_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos,
-                               weights, weight_planes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
-                               loss_out, S, H, W);
-        else
-            hipLaunchKernelGGL((k_wphoto_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos,
-                               weights, weight_planes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
-                               loss_out, S, H, W);
-    } else {
-        if (HEAD)
-            hipLaunchKernelGGL((k_head_wphoto<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, weights,
-                               weight_planes, scenes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
-                               loss_out, S, H, W);
-        else
-            hipLaunchKernelGGL((k_wphoto<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, weights,
-                               weight_planes, scenes, xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws,
-                               loss_out, S, H, W);
-    }
-}
-
-template <bool G, bool HEAD>
+// One launcher for the sixteen kernels: the table by value (`rows`) or in device memory, `weights, weight_planes` for the
+// weighted kernels only, the tail from `xrow` on common to all.
+template <bool G, bool HEAD, bool WEIGHTED>
 void launch_photo(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st, const float *input, const float *photos,
-                  const float *scenes, const float *xrow, float eps, float inv_count, double loss_scale, float fixed_scale,
-                  float *grad_input, unsigned long long *ws, float *loss_out, int B, int S, int H, int W)
+                  const float *weights, int weight_planes, const float *scenes, const float *xrow, float eps,
+                  float inv_count, double loss_scale, float fixed_scale, float *grad_input, unsigned long long *ws,
+                  float *loss_out, int B, int S, int H, int W)
 {
+    const auto launch = [&](auto kernel, const auto &...front) {
+        hipLaunchKernelGGL(kernel, grid, dim3(kLossThreads), lds_bytes, st, front..., xrow, eps, inv_count, loss_scale,
+                           fixed_scale, grad_input, ws, loss_out, S, H, W);
+    };
     if (rows) {
         SceneBlock block_arg;      // only the first B*S rows are ever read
         std::memcpy(block_arg.v, rows, (size_t)B * S * 9 * sizeof(float));
-        if (HEAD)
-            hipLaunchKernelGGL((k_head_photo_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos,
-                               xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+        if constexpr (WEIGHTED)
+            launch(HEAD ? k_head_wphoto_inl<G> : k_wphoto_inl<G>, block_arg, input, photos, weights, weight_planes);
         else
-            hipLaunchKernelGGL((k_photo_loss_inl<G>), grid, dim3(kLossThreads), lds_bytes, st, block_arg, input, photos,
-                               xrow, eps, inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+            launch(HEAD ? k_head_photo_inl<G> : k_photo_loss_inl<G>, block_arg, input, photos);
     } else {
-        if (HEAD)
-            hipLaunchKernelGGL((k_head_photo<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, scenes, xrow, eps,
-                               inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+        if constexpr (WEIGHTED)
+            launch(HEAD ? k_head_wphoto<G> : k_wphoto<G>, input, photos, weights, weight_planes, scenes);
         else
-            hipLaunchKernelGGL((k_photo_loss<G>), grid, dim3(kLossThreads), lds_bytes, st, input, photos, scenes, xrow, eps,
-                               inv_count, loss_scale, fixed_scale, grad_input, ws, loss_out, S, H, W);
+            launch(HEAD ? k_head_photo<G> : k_photo_loss<G>, input, photos, scenes);
     }
 }
 
 // Argument checks, grid and fixed-point scale: K3's own (plan_loss in svbrdf_kernels.hip; no L1 term here).  The launch
 // is counted by the main unit's counter through launch_status() (svbrdf_internal_launch_status).
-// `head`: input and grad_input are the 9 encoded planes (svbrdf_head_photo_loss_fwd_bwd*), same checks
-int photo_impl(const char *who, bool scenes_on_host, bool head, const float *input, const float *photos, const float *scenes,
-               const float *xrow, float eps, float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes,
-               int B, int S, int H, int W, void *stream)
+// `head`: input and grad_input are the 9 encoded planes (svbrdf_head_photo_loss_fwd_bwd*), same checks.
+// `weighted`: the same plan (a weight in [0, 1] keeps a term within plan_loss's bound of 32, so the fixed-point scale
+// stands), `weights` among the required pointers, `weight_planes` 1 or S -- all before any launch.
+int photo_impl(const char *who, bool scenes_on_host, bool head, bool weighted, const float *input, const float *photos,
+               const float *weights, int weight_planes, const float *scenes, const float *xrow, float eps, float *loss_out,
+               float *grad_input, void *workspace, size_t workspace_bytes, int B, int S, int H, int W, void *stream)
 {
+    using Required = std::initializer_list<const void *>;
     LossPlan p;
-    if (int e = plan_loss(who, scenes_on_host, {input, photos, scenes, xrow, loss_out}, grad_input, workspace,
-                          workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    const float *rows = scenes_on_host ? scenes : nullptr;
-#define SVBRDF_LAUNCH_PHOTO(G, HD)                                                                                      \
-    launch_photo<G, HD>(rows, p.grid, p.lds_bytes, static_cast<hipStream_t>(stream), input, photos, scenes, xrow, eps,  \
-                        p.inv_count, p.loss_scale, p.fixed_scale, grad_input, p.ws, loss_out, B, S, H, W)
-    if (head) {
-        if (grad_input) SVBRDF_LAUNCH_PHOTO(true, true);
-        else SVBRDF_LAUNCH_PHOTO(false, true);
-    } else {
-        if (grad_input) SVBRDF_LAUNCH_PHOTO(true, false);
-        else SVBRDF_LAUNCH_PHOTO(false, false);
-    }
-#undef SVBRDF_LAUNCH_PHOTO
-    return launch_status(who);
-}
-
-// The weighted entries: the same plan (a weight in [0, 1] keeps a term within plan_loss's bound of 32, so the fixed-point
-// scale stands), `weights` among the required pointers, `weight_planes` 1 or S -- all before any launch.
-int wphoto_impl(const char *who, bool scenes_on_host, bool head, const float *input, const float *photos,
-                const float *weights, int weight_planes, const float *scenes, const float *xrow, float eps, float *loss_out,
-                float *grad_input, void *workspace, size_t workspace_bytes, int B, int S, int H, int W, void *stream)
-{
-    LossPlan p;
-    if (int e = plan_loss(who, scenes_on_host, {input, photos, weights, scenes, xrow, loss_out}, grad_input, workspace,
-                          workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    if (weight_planes != 1 && weight_planes != S) {
+    if (int e = plan_loss(who, scenes_on_host,
+                          weighted ? Required{input, photos, weights, scenes, xrow, loss_out}
+                                   : Required{input, photos, scenes, xrow, loss_out},
+                          grad_input, workspace, workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
+    if (weighted && weight_planes != 1 && weight_planes != S) {
         char text[200];
         std::snprintf(text, sizeof(text), "%s: weight_planes must be 1 (one plane per item) or S (one per photo)", who);
         return fail(SVBRDF_ERR_DIMS, text);
     }
-    const float *rows = scenes_on_host ? scenes : nullptr;
-#define SVBRDF_LAUNCH_WPHOTO(G, HD)                                                                                     \
-    launch_wphoto<G, HD>(rows, p.grid, p.lds_bytes, static_cast<hipStream_t>(stream), input, photos, weights,          \
-                         weight_planes, scenes, xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, grad_input, p.ws, \
-                         loss_out, B, S, H, W)
-    if (head) {
-        if (grad_input) SVBRDF_LAUNCH_WPHOTO(true, true);
-        else SVBRDF_LAUNCH_WPHOTO(false, true);
-    } else {
-        if (grad_input) SVBRDF_LAUNCH_WPHOTO(true, false);
-        else SVBRDF_LAUNCH_WPHOTO(false, false);
-    }
-#undef SVBRDF_LAUNCH_WPHOTO
+    static constexpr decltype(&launch_photo<false, false, false>) kLaunch[2][2][2] = {     // [weighted][head][gradient]
+        {{launch_photo<false, false, false>, launch_photo<true, false, false>},
+         {launch_photo<false, true, false>, launch_photo<true, true, false>}},
+        {{launch_photo<false, false, true>, launch_photo<true, false, true>},
+         {launch_photo<false, true, true>, launch_photo<true, true, true>}}};
+    kLaunch[weighted][head][grad_input != nullptr](
+        scenes_on_host ? scenes : nullptr, p.grid, p.lds_bytes, static_cast<hipStream_t>(stream), input, photos, weights,
+        weight_planes, scenes, xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, grad_input, p.ws, loss_out, B, S, H, W);
     return launch_status(who);
 }
 
@@ -604,7 +554,7 @@ int svbrdf_photo_loss_weighted_fwd_bwd(const float *input, const float *photos, 
                                        float *grad_input, void *workspace, size_t workspace_bytes, int B, int S, int H,
                                        int W, void *stream)
 {
-    return wphoto_impl("photo_loss_weighted", false, false, input, photos, weights, weight_planes, scenes, xrow, eps,
+    return photo_impl("photo_loss_weighted", false, false, true, input, photos, weights, weight_planes, scenes, xrow, eps,
                        loss_out, grad_input, workspace, workspace_bytes, B, S, H, W, stream);
 }
 
@@ -613,7 +563,7 @@ int svbrdf_photo_loss_weighted_fwd_bwd_host_scenes(const float *input, const flo
                                                    float eps, float *loss_out, float *grad_input, void *workspace,
                                                    size_t workspace_bytes, int B, int S, int H, int W, void *stream)
 {
-    return wphoto_impl("photo_loss_weighted_host_scenes", true, false, input, photos, weights, weight_planes, scenes_host,
+    return photo_impl("photo_loss_weighted_host_scenes", true, false, true, input, photos, weights, weight_planes, scenes_host,
                        xrow, eps, loss_out, grad_input, workspace, workspace_bytes, B, S, H, W, stream);
 }
 
@@ -622,7 +572,7 @@ int svbrdf_head_photo_loss_weighted_fwd_bwd(const float *encoded9, const float *
                                             float *loss_out, float *grad_encoded9, void *workspace, size_t workspace_bytes,
                                             int B, int S, int H, int W, void *stream)
 {
-    return wphoto_impl("head_photo_loss_weighted", false, true, encoded9, photos, weights, weight_planes, scenes, xrow, eps,
+    return photo_impl("head_photo_loss_weighted", false, true, true, encoded9, photos, weights, weight_planes, scenes, xrow, eps,
                        loss_out, grad_encoded9, workspace, workspace_bytes, B, S, H, W, stream);
 }
 
@@ -631,7 +581,7 @@ int svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes(const float *encoded9, c
                                                         float eps, float *loss_out, float *grad_encoded9, void *workspace,
                                                         size_t workspace_bytes, int B, int S, int H, int W, void *stream)
 {
-    return wphoto_impl("head_photo_loss_weighted_host_scenes", true, true, encoded9, photos, weights, weight_planes,
+    return photo_impl("head_photo_loss_weighted_host_scenes", true, true, true, encoded9, photos, weights, weight_planes,
                        scenes_host, xrow, eps, loss_out, grad_encoded9, workspace, workspace_bytes, B, S, H, W, stream);
 }
 
@@ -639,16 +589,16 @@ int svbrdf_photo_loss_fwd_bwd(const float *input, const float *photos, const flo
                               float *loss_out, float *grad_input, void *workspace, size_t workspace_bytes, int B, int S,
                               int H, int W, void *stream)
 {
-    return photo_impl("photo_loss", false, false, input, photos, scenes, xrow, eps, loss_out, grad_input, workspace,
-                      workspace_bytes, B, S, H, W, stream);
+    return photo_impl("photo_loss", false, false, false, input, photos, nullptr, 0, scenes, xrow, eps, loss_out, grad_input,
+                      workspace, workspace_bytes, B, S, H, W, stream);
 }
 
 int svbrdf_photo_loss_fwd_bwd_host_scenes(const float *input, const float *photos, const float *scenes_host,
                                           const float *xrow, float eps, float *loss_out, float *grad_input,
                                           void *workspace, size_t workspace_bytes, int B, int S, int H, int W, void *stream)
 {
-    return photo_impl("photo_loss_host_scenes", true, false, input, photos, scenes_host, xrow, eps, loss_out, grad_input,
-                      workspace, workspace_bytes, B, S, H, W, stream);
+    return photo_impl("photo_loss_host_scenes", true, false, false, input, photos, nullptr, 0, scenes_host, xrow, eps, loss_out,
+                      grad_input, workspace, workspace_bytes, B, S, H, W, stream);
 }
 
 // The network head folded in (added to ABI version 8 without a bump: see include/svbrdf_hip.h)
@@ -656,8 +606,8 @@ int svbrdf_head_photo_loss_fwd_bwd(const float *encoded9, const float *photos, c
                                    float eps, float *loss_out, float *grad_encoded9, void *workspace,
                                    size_t workspace_bytes, int B, int S, int H, int W, void *stream)
 {
-    return photo_impl("head_photo_loss", false, true, encoded9, photos, scenes, xrow, eps, loss_out, grad_encoded9,
-                      workspace, workspace_bytes, B, S, H, W, stream);
+    return photo_impl("head_photo_loss", false, true, false, encoded9, photos, nullptr, 0, scenes, xrow, eps, loss_out,
+                      grad_encoded9, workspace, workspace_bytes, B, S, H, W, stream);
 }
 
 int svbrdf_head_photo_loss_fwd_bwd_host_scenes(const float *encoded9, const float *photos, const float *scenes_host,
@@ -665,8 +615,8 @@ int svbrdf_head_photo_loss_fwd_bwd_host_scenes(const float *encoded9, const floa
                                                void *workspace, size_t workspace_bytes, int B, int S, int H, int W,
                                                void *stream)
 {
-    return photo_impl("head_photo_loss_host_scenes", true, true, encoded9, photos, scenes_host, xrow, eps, loss_out,
-                      grad_encoded9, workspace, workspace_bytes, B, S, H, W, stream);
+    return photo_impl("head_photo_loss_host_scenes", true, true, false, encoded9, photos, nullptr, 0, scenes_host, xrow, eps,
+                      loss_out, grad_encoded9, workspace, workspace_bytes, B, S, H, W, stream);
 }
 
 }  // extern "C"

@@ -423,7 +423,48 @@ def _check_fused_photo_inputs(loss_name, input_name, input, photos):
     return False
 
 
-class PhotoLoss(nn.Module):
+class _PhotoLossModule(nn.Module):
+    """What PhotoLoss and HeadPhotoLoss share: the constructor and the routing of a call."""
+
+    def __init__(self, renderer, eps=0.1, normalize="count"):
+        super().__init__()
+        if normalize not in _NORMALIZE:
+            raise ValueError("normalize must be one of %s, got %r" % (_NORMALIZE, normalize))
+        self.renderer = renderer
+        self.eps = eps
+        self.normalize = normalize
+
+    def uses_fused_kernel(self):
+        return RenderingLoss(self.renderer).uses_fused_kernel()
+
+    def _forward_decoded(self, encoded9, photos, scenes, weights):
+        """the head losses' composed definition: PhotoLoss, which normalises by itself, on the decoded maps"""
+        return PhotoLoss(self.renderer, self.eps, self.normalize)(decode_head(encoded9), photos, scenes, weights)
+
+    def _forward(self, x, photos, scenes, weights, head):
+        """The one routing of both modules; ``x``: the 12 maps, or with ``head`` the 9 encoded channels.  A plugin renderer
+        and double on either side take the composed definition, everything else is the fused kernel."""
+        photos = PhotoLoss._check(x, photos, channels=9 if head else 12)
+        weights = _check_weights(weights, x, photos)
+        B, S = photos.shape[0], photos.shape[1]
+        if not self.uses_fused_kernel():
+            if head:
+                return self._forward_decoded(x, photos, scenes, weights)
+            loss = self._forward_plugin(x, photos, PhotoLoss._scene_objects(scenes, B, S), weights)
+        else:
+            table = PhotoLoss._scene_table(scenes, B, S)
+            if _check_fused_photo_inputs(*(("HeadPhotoLoss", "encoded9") if head else ("PhotoLoss", "input")), x, photos):
+                if head:
+                    return self._forward_decoded(x.to(torch.float64), photos, table, weights)   # promoted in front of the decode
+                loss = composed_photo_loss(x.to(torch.float64), photos, table.to(x.device), self.eps, weights)  # float64 K1 / K2
+            else:
+                loss = _FusedPhotoLoss.apply(x, photos, table, float(self.eps), head, weights)
+                if (weights is None or self.normalize == "count") and loss.requires_grad:
+                    return loss.as_subclass(_PhotoLossTensor)
+        return _normalized(loss, weights, photos, self.normalize)
+
+
+class PhotoLoss(_PhotoLossModule):
     """The rendering loss against PHOTOGRAPHS instead of against the renderings of ground-truth maps:
 
         mean over b,s,c,i,j of | log(render(scenes[b][s], input[b]) + eps) - log(photos[b,s] + eps) |
@@ -448,17 +489,6 @@ class PhotoLoss(nn.Module):
     pixel-render.  ``normalize="count"`` (default) divides by the number N = B S 3 H W of terms as above;
     ``normalize="weights"`` returns the weighted mean ``sum w|d| / (3 sum w)`` instead (0 when every weight is 0), which
     costs a reduction over the weights and a scale of the loss on the device (two small launches, no host sync)."""
-
-    def __init__(self, renderer, eps=0.1, normalize="count"):
-        super().__init__()
-        if normalize not in _NORMALIZE:
-            raise ValueError("normalize must be one of %s, got %r" % (_NORMALIZE, normalize))
-        self.renderer = renderer
-        self.eps = eps
-        self.normalize = normalize
-
-    def uses_fused_kernel(self):
-        return RenderingLoss(self.renderer).uses_fused_kernel()
 
     @staticmethod
     def _check(input, photos, channels=12):
@@ -504,28 +534,7 @@ class PhotoLoss(nn.Module):
         return torch.stack([torch.stack([environment.scene_to_row(sc) for sc in r]) for r in rows])
 
     def forward(self, input, photos, scenes, weights=None):
-        photos = self._check(input, photos)
-        B, S = photos.shape[0], photos.shape[1]
-        if weights is None:
-            if not self.uses_fused_kernel():
-                return self._forward_plugin(input, photos, self._scene_objects(scenes, B, S))
-            table = self._scene_table(scenes, B, S)
-            if _check_fused_photo_inputs("PhotoLoss", "input", input, photos):
-                return composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps)     # float64 K1 / K2
-            loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps), False)
-            return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
-        weights = _check_weights(weights, input, photos)
-        if not self.uses_fused_kernel():
-            loss = self._forward_plugin(input, photos, self._scene_objects(scenes, B, S), weights)
-        else:
-            table = self._scene_table(scenes, B, S)
-            if _check_fused_photo_inputs("PhotoLoss", "input", input, photos):
-                loss = composed_photo_loss(input.to(torch.float64), photos, table.to(input.device), self.eps, weights)
-            else:
-                loss = _FusedPhotoLoss.apply(input, photos, table, float(self.eps), False, weights)
-                if self.normalize == "count" and loss.requires_grad:
-                    return loss.as_subclass(_PhotoLossTensor)
-        return _normalized(loss, weights, photos, self.normalize)
+        return self._forward(input, photos, scenes, weights, head=False)
 
     def _forward_plugin(self, input, photos, scenes, weights=None):
         """the composed definition with a foreign renderer object: its own render() per scene, log, L1 mean"""
@@ -586,7 +595,7 @@ class FusedHeadLoss(nn.Module):
         return self.l1_weight * self.l1_loss(maps, target) + self.rendering_loss(maps, target)
 
 
-class HeadPhotoLoss(nn.Module):
+class HeadPhotoLoss(_PhotoLossModule):
     """``PhotoLoss(renderer, eps)(decode_head(encoded9), photos, scenes)`` in one kernel: what training or fine-tuning the
     network against photographs needs.  ``forward(encoded9 [B,9,H,W], photos [B,S,3,H,W] or [B,3,H,W] (S = 1), scenes)``
     with ``encoded9`` the generator's output after tanh (any finite value: no clamp of its own) and photos / scenes as
@@ -598,36 +607,5 @@ class HeadPhotoLoss(nn.Module):
     either side and ``backward(create_graph=True)`` take the composed definition above, which is also the specification
     of the fused path.  ``weights`` and ``normalize``: per-pixel confidence, exactly as ``PhotoLoss`` documents them."""
 
-    def __init__(self, renderer, eps=0.1, normalize="count"):
-        super().__init__()
-        if normalize not in _NORMALIZE:
-            raise ValueError("normalize must be one of %s, got %r" % (_NORMALIZE, normalize))
-        self.renderer = renderer
-        self.eps = eps
-        self.normalize = normalize
-
-    def uses_fused_kernel(self):
-        return RenderingLoss(self.renderer).uses_fused_kernel()
-
     def forward(self, encoded9, photos, scenes, weights=None):
-        photos = PhotoLoss._check(encoded9, photos, channels=9)
-        if weights is None:
-            composed = PhotoLoss(self.renderer, self.eps)
-            if not self.uses_fused_kernel():
-                return composed(decode_head(encoded9), photos, scenes)
-            table = PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
-            if _check_fused_photo_inputs("HeadPhotoLoss", "encoded9", encoded9, photos):
-                return composed(decode_head(encoded9.to(torch.float64)), photos, table)     # promoted in front of the decode
-            loss = _FusedPhotoLoss.apply(encoded9, photos, table, float(self.eps), True)
-            return loss.as_subclass(_PhotoLossTensor) if loss.requires_grad else loss
-        weights = _check_weights(weights, encoded9, photos)
-        composed = PhotoLoss(self.renderer, self.eps, self.normalize)
-        if not self.uses_fused_kernel():
-            return composed(decode_head(encoded9), photos, scenes, weights)
-        table = PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
-        if _check_fused_photo_inputs("HeadPhotoLoss", "encoded9", encoded9, photos):
-            return composed(decode_head(encoded9.to(torch.float64)), photos, table, weights)
-        loss = _FusedPhotoLoss.apply(encoded9, photos, table, float(self.eps), True, weights)
-        if self.normalize == "count" and loss.requires_grad:
-            return loss.as_subclass(_PhotoLossTensor)
-        return _normalized(loss, weights, photos, self.normalize)
+        return self._forward(encoded9, photos, scenes, weights, head=True)

@@ -54,7 +54,7 @@ import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))     # the repository root: the helpers import the C oracle
 import head_checks  # noqa: E402   (tests/ is on the path through make_golden)
-import head_photo_checks  # noqa: E402
+import photo_checks  # noqa: E402
 import tolerances  # noqa: E402
 
 NAME = "g20_head_photo_loss.npz"
@@ -103,7 +103,7 @@ def make(enc_seed=ENC_SEED, photo_maps_seed=PHOTO_MAPS_SEED, rng_seed=RNG_SEED, 
         torch.set_default_dtype(torch.float32)
     assert x64.grad.dtype == torch.float64 and loss64.dtype == torch.float64
     table = np.stack([np.stack([scene_row(sc) for sc in row]) for row in scenes]).astype(np.float32)
-    ties = head_photo_checks.Reference(enc, photos.numpy(), table, EPS).n_ties()
+    ties = photo_checks.Reference(enc, photos.numpy(), table, EPS, head=True).n_ties()
     arrays = dict(
         B=np.int64(B), H=np.int64(H), eps=np.float32(EPS), enc_seed=np.int64(enc_seed),
         photo_maps_seed=np.int64(photo_maps_seed), rng_seed=np.int64(rng_seed), noise_seed=np.int64(noise_seed),

@@ -48,6 +48,7 @@ import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))     # the repository root: the helpers import the C oracle
 import head_checks  # noqa: E402   (tests/ is on the path through make_golden)
+import photo_checks  # noqa: E402
 import tolerances  # noqa: E402
 import weighted_photo_checks  # noqa: E402
 
@@ -119,8 +120,8 @@ def make():
     loss, grad, loss64, grad64 = both_precisions(inp, photos_t, weights_t, scenes, False)
     hloss, hgrad, hloss64, hgrad64 = both_precisions(enc, photos_t, weights_t, scenes, True)
     table = np.stack([np.stack([scene_row(sc) for sc in row]) for row in scenes]).astype(np.float32)
-    ties = (weighted_photo_checks.Reference(inp, photos, weights, table, EPS).n_ties(),
-            weighted_photo_checks.Reference(enc, photos, weights, table, EPS, head=True).n_ties())
+    ties = (photo_checks.Reference(inp, photos, table, EPS, weights=weights).n_ties(),
+            photo_checks.Reference(enc, photos, table, EPS, head=True, weights=weights).n_ties())
     arrays = dict(
         B=np.int64(B), H=np.int64(H), eps=np.float32(EPS), masked_row=np.int64(MASKED_ROW),
         input_seed=np.int64(INPUT_SEED), enc_seed=np.int64(ENC_SEED), photo_maps_seed=np.int64(PHOTO_MAPS_SEED),

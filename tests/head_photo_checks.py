@@ -5,11 +5,11 @@
 as a composition of what exists, the photographs the cases are compared under, an independent definition in torch float64
 autograd and the speed measurement.
 
-Comparison values of one case (class Reference):
+Comparison values of one case (photo_checks.Reference with head=True):
 
     maps        = c_oracle.head_decode(enc)                 the float32 decode with the reference's rounding
     loss, g12   = photo_checks.oracle_photo_loss(maps, ...) float32, and f64=True on the same float32-decoded maps
-    g9          = chain9(enc, maps, g12)                    12 -> 9 channels in float64, the formulas of
+    g9          = photo_checks.chain9(enc, maps, g12)       12 -> 9 channels in float64, the formulas of
                                                             head_checks.head_loss_f64_on_f32_decode
     tie map     = photo_checks.tie_map(maps, photos, scenes, delta_f64)
 
@@ -26,62 +26,15 @@ import torch
 
 import head_checks
 import photo_checks
-import tolerances
 from oracle import c_oracle
 
-EPS = 0.1
+EPS = photo_checks.EPS
 ENTRIES = ("svbrdf_head_photo_loss_fwd_bwd", "svbrdf_head_photo_loss_fwd_bwd_host_scenes")
-
-
-def chain9(enc, maps, g12, n=None):
-    """d loss / d encoded9 [B,9,H,W] float64 from d loss / d maps [B,12,H,W]: the chain rule through the head decode in
-    float64 (head_checks.head_loss_f64_on_f32_decode).  `n`: the unit normal the Jacobian is taken at, default the
-    float32-decoded one of `maps`."""
-    enc = np.asarray(enc, np.float32)
-    g12 = np.asarray(g12, np.float64)
-    n = np.asarray(maps)[:, 0:3].astype(np.float64) if n is None else np.asarray(n, np.float64)
-    ex, ey = 3.0 * enc[:, 0].astype(np.float64), 3.0 * enc[:, 1].astype(np.float64)
-    k = 3.0 / np.sqrt(ex * ex + ey * ey + 1.0)
-    ng = (n * g12[:, 0:3]).sum(axis=1)
-    g9 = np.empty(enc.shape, np.float64)
-    g9[:, 0] = k * (g12[:, 0] - n[:, 0] * ng)
-    g9[:, 1] = k * (g12[:, 1] - n[:, 1] * ng)
-    g9[:, 2:5] = 0.5 * g12[:, 3:6]
-    g9[:, 5] = 0.5 * (g12[:, 6] + g12[:, 7] + g12[:, 8])
-    g9[:, 6:9] = 0.5 * g12[:, 9:12]
-    return g9
 
 
 def photographs(target_maps, scenes, raw=False):
     ph = c_oracle.render_fwd(np.ascontiguousarray(target_maps, np.float32), np.ascontiguousarray(scenes, np.float32))
     return ph if raw else np.clip(ph, 0.0, 1.0)
-
-
-class Reference:
-    """the oracle's values of one case: fp32 and fp64 loss and 9-channel gradient (both float64 arrays), tie map"""
-
-    def __init__(self, enc, photos, scenes, eps=EPS):
-        self.enc = np.ascontiguousarray(enc, np.float32)
-        self.maps = c_oracle.head_decode(self.enc)
-        self.loss, g12, _ = photo_checks.oracle_photo_loss(self.maps, photos, scenes, eps)
-        self.loss64, g12_64, self.delta64 = photo_checks.oracle_photo_loss(self.maps, photos, scenes, eps, f64=True)
-        self.grad12_64 = np.asarray(g12_64, np.float64)
-        self.grad = chain9(self.enc, self.maps, g12)
-        self.grad64 = chain9(self.enc, self.maps, g12_64)
-        self.tie = photo_checks.tie_map(self.maps, photos, scenes, self.delta64)
-
-    def n_ties(self):
-        return int((self.tie < tolerances.TIE_LEVEL).sum())
-
-    def n_widened(self):
-        """elements, tie pixels excluded, where the fp32 oracle is outside the strict bound against the fp64 oracle"""
-        strict = tolerances.GRAD_RTOL * np.abs(self.grad64) + tolerances.GRAD_ATOL_FRAC * np.abs(self.grad64).max()
-        ties = np.broadcast_to((self.tie < tolerances.TIE_LEVEL)[:, None], self.grad64.shape)
-        return int(((np.abs(self.grad - self.grad64) > strict) & ~ties).sum())
-
-    def assert_close(self, loss, grad, what, max_ties=tolerances.MAX_TIE_PIXELS):
-        tolerances.assert_loss_close(loss, self.loss, what + " loss")
-        return photo_checks.assert_photo_grad_close(grad, self.grad, self.grad64, self.tie, what + " grad9", max_ties=max_ties)
 
 
 def upstream_rounding_term(maps, photos, scenes, eps=EPS):
@@ -151,32 +104,7 @@ def argument_inputs():
 RAW_POW2 = "64_device"      # the power-of-two case that is also run with raw (unclipped) photographs
 
 
-# ------------------------------------------------------------------------------------------------ the device side
-
-def call_abi(native, enc, photos, scenes, eps=EPS, want_grad=True):
-    """the C ABI through the binding: scenes on the device -> the device-table entry, on the host -> the by-value entry
-    -> (loss: float, gradient [B,9,H,W] float32 or None)"""
-    loss, grad = native.photo_loss(enc, photos, scenes, eps, want_grad=want_grad, head=True)
-    return loss.item(), (None if grad is None else grad.detach().cpu().numpy())
-
-
-def _event_timed_median(enqueue, n, block, dev):
-    """median over n steps of the time between the events recorded around each; the steps are enqueued while the device
-    is held by `block()` (a spinning wave), so the stream runs them back to back whatever the host's pace
-    (tests/test_gpu_photo_loss.py)"""
-    stream = torch.cuda.current_stream(dev)
-    for i in range(16):
-        enqueue(i)
-    torch.cuda.synchronize(dev)
-    block()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
-    ev[0].record(stream)
-    for i in range(n):
-        enqueue(i)
-        ev[i + 1].record(stream)
-    torch.cuda.synchronize(dev)
-    return float(np.median([ev[i].elapsed_time(ev[i + 1]) * 1e3 for i in range(n)]))
-
+# ------------------------------------------------------------------------------------------------ the speed measurement
 
 def measure_head_photo_loss(dev, native, sets=6, n=40, rounds=3):
     """-> dict of medians (us per step) at the configuration-2 shape, B = 8, 256 x 256, S = 9, by-value scene table, `sets`
@@ -205,7 +133,6 @@ def measure_head_photo_loss(dev, native, sets=6, n=40, rounds=3):
     ws = torch.zeros(65, dtype=torch.int64, device=dev)
     loss = torch.empty(1, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    clk = torch.zeros(2, dtype=torch.int64, device=dev)
     unfused = losses.PhotoLoss(renderers.LocalRenderer(), EPS)
 
     def head(i):
@@ -227,15 +154,8 @@ def measure_head_photo_loss(dev, native, sets=6, n=40, rounds=3):
         leaves[k].grad = None
         unfused(losses.decode_head(leaves[k]), photos[k], table).backward()
 
-    def block():        # one wave spins for 8 ms on the stream: the timed steps queue up behind it
-        native.clock_probe(clk, ticks=800000)
-
     legs = (("head_photo_us", head), ("composition_us", composition), ("photo12_us", photo12))
-    res = {name: [] for name, _ in legs}
-    for _ in range(rounds):
-        for name, fn in legs:
-            res[name].append(_event_timed_median(fn, n, block, dev))
-    out = {name: float(np.median(v)) for name, v in res.items()}
+    out, res = photo_checks.timed_legs(legs, n, rounds, photo_checks.spinning_wave(native, dev), dev)
     out.update(rounds=res, device=torch.cuda.get_device_name(dev), steps_per_round=n, sets=sets)
     out["head_photo_frac_of_8TBps"] = (9 + 3 * S + 9) * 4 * H * H * B / (out["head_photo_us"] * 1e-6) / 8.0e12
     return out

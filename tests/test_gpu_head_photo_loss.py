@@ -26,6 +26,7 @@ import head_photo_checks as hp
 import photo_checks
 import synth
 import tolerances
+from photo_checks import assert_scratch_is_zero as _scratch_is_zero, to_device as _t, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
 EPS = hp.EPS
@@ -52,24 +53,12 @@ def head_photo_loss():
     return fn
 
 
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
 def _table(sc, host, dev):
     return torch.from_numpy(np.ascontiguousarray(sc, np.float32)) if host else _t(sc, dev)
 
 
-def _scratch_is_zero(native):
-    torch.cuda.synchronize()
-    assert native._workspace_cache, "no call has allocated the scratch yet"
-    for ws in native._workspace_cache.values():
-        assert ws.numel() * 8 >= 65 * 8
-        assert not ws.any().item(), "scratch left dirty: %s" % (ws.cpu().numpy()[:65],)
+def _call_abi(native, enc, photos, scenes, want_grad=True):
+    return photo_checks.call_abi(native, enc, photos, scenes, EPS, want_grad, head=True)
 
 
 def _four_ways(native, dev, head_photo_loss, enc, ph, sc):
@@ -78,7 +67,7 @@ def _four_ways(native, dev, head_photo_loss, enc, ph, sc):
     results = {}
     for form, host in (("device table", False), ("by-value table", True)):
         table = _table(sc, host, dev)
-        results["C ABI, " + form] = hp.call_abi(native, d_enc, d_ph, table)
+        results["C ABI, " + form] = _call_abi(native, d_enc, d_ph, table)
         x = d_enc.clone().requires_grad_(True)
         l = head_photo_loss(x, d_ph, table)
         assert l.dim() == 0
@@ -95,7 +84,7 @@ def test_reference_fixture(dev, native, head_photo_loss, golden):
     g = golden("g20_head_photo_loss.npz")
     enc = head_checks.fixture_input(int(g["enc_seed"]), int(g["B"]), int(g["H"]))
     assert synth.checksum(enc) == str(g["enc_sha256"])
-    ref = hp.Reference(enc, g["photos"], g["scenes"], EPS)
+    ref = photo_checks.Reference(enc, g["photos"], g["scenes"], EPS, head=True)
     results = _four_ways(native, dev, head_photo_loss, enc, g["photos"], g["scenes"])
     print("[head-photo] g20: four ways in, bitwise equal: yes")
     for how, (loss, grad) in results.items():
@@ -113,13 +102,13 @@ def test_seeded_sweep_against_the_oracle(dev, native):
     for c in cases:
         enc, ph, sc = hp.sweep_inputs(c)
         what = "photo " + head_checks.sweep_name(c)
-        ref = hp.Reference(enc, ph, sc)
+        ref = photo_checks.Reference(enc, ph, sc, head=True)
         d_enc, d_ph = _t(enc, dev), _t(ph, dev)
-        loss, grad = hp.call_abi(native, d_enc, d_ph, _table(sc, c["host_table"], dev))
+        loss, grad = _call_abi(native, d_enc, d_ph, _table(sc, c["host_table"], dev))
         assert grad.shape == enc.shape
         ref.assert_close(loss, grad, what)
         for host in (False, True):      # forward only: the same loss bit for bit, both table forms
-            fwd, none = hp.call_abi(native, d_enc, d_ph, _table(sc, host, dev), want_grad=False)
+            fwd, none = _call_abi(native, d_enc, d_ph, _table(sc, host, dev), want_grad=False)
             assert none is None and fwd == loss, (what, host, fwd, loss)
         _scratch_is_zero(native)
     print("[head-photo] sweep: forward-only loss bitwise equal to forward + adjoint in both table forms: yes (24 cases)")
@@ -135,8 +124,8 @@ def test_power_of_two_widths_every_pixel(dev, native, oracle, name):
     enc, ph, sc = hp.pow2_inputs(base, raw=raw)
     if raw:
         assert ph.max() > 1.0, "the raw photographs should hold values the clamp would have cut"
-    ref = hp.Reference(enc, ph, sc)
-    loss, grad = hp.call_abi(native, _t(enc, dev), _t(ph, dev), _table(sc, host, dev))
+    ref = photo_checks.Reference(enc, ph, sc, head=True)
+    loss, grad = _call_abi(native, _t(enc, dev), _t(ph, dev), _table(sc, host, dev))
     ref.assert_close(loss, grad, "photo head pow2 " + name)
     _scratch_is_zero(native)
 
@@ -169,9 +158,9 @@ def _raw_call(native, dev, entry, enc, ph, scenes, xrow, loss, grad):
 @pytest.mark.parametrize("H", [13, 17])
 def test_every_device_pointer_four_bytes_off_alignment(dev, native, H):
     enc, ph, sc = hp.alignment_inputs(H)
-    ref = hp.Reference(enc, ph, sc)
+    ref = photo_checks.Reference(enc, ph, sc, head=True)
     d_enc, d_ph, d_sc = _t(enc, dev), _t(ph, dev), _t(sc, dev)
-    loss, grad = hp.call_abi(native, d_enc, d_ph, d_sc)
+    loss, grad = _call_abi(native, d_enc, d_ph, d_sc)
     ref.assert_close(loss, grad, "photo head alignment %d" % H)
     xr = native.xrow(dev, H)
     l_al, g_al = _raw_call(native, dev, hp.ENTRIES[0], d_enc, d_ph, d_sc, xr, torch.empty(1, device=dev), torch.empty_like(d_enc))
@@ -209,7 +198,7 @@ def test_launch_count_reproducibility_scratch_and_non_finite_inputs(dev, native,
     assert runs[0][0] == runs[1][0] == runs[2][0]
     assert np.array_equal(runs[0][1], runs[1][1])                               # two runs: bitwise equal
     assert np.array_equal(runs[2][1], runs[0][1] * np.float32(2.5))
-    hp.Reference(enc, ph, sc).assert_close(runs[0][0], runs[0][1], "photo head arguments case")
+    photo_checks.Reference(enc, ph, sc, head=True).assert_close(runs[0][0], runs[0][1], "photo head arguments case")
     with torch.no_grad():                           # no gradient wanted: the forward-only kernel, one launch
         n0 = native.launch_count()
         assert head_photo_loss(d_enc, d_ph, d_sc).item() == runs[0][0] and native.launch_count() - n0 == 1
@@ -229,10 +218,10 @@ def test_launch_count_reproducibility_scratch_and_non_finite_inputs(dev, native,
               ("photo < -eps", d_enc, poisoned(ph, (0, 3, 1, 5, 5), -0.5))]
     for what, bad_enc, bad_ph in cases:
         for want_grad in (True, False):
-            l, _ = hp.call_abi(native, bad_enc, bad_ph, d_sc, want_grad=want_grad)
+            l, _ = _call_abi(native, bad_enc, bad_ph, d_sc, want_grad=want_grad)
             assert np.isnan(l), (what, want_grad, l)
             _scratch_is_zero(native)
-    l, g = hp.call_abi(native, d_enc, d_ph, d_sc)
+    l, g = _call_abi(native, d_enc, d_ph, d_sc)
     assert l == runs[0][0] and np.array_equal(g, runs[0][1])
     _scratch_is_zero(native)
     print("[head-photo] %d non-finite cases x 2 kernels: NaN loss, scratch zero, the next clean call bitwise as before: yes" % len(cases))
@@ -261,7 +250,7 @@ def test_gradient_of_each_encoded_group_in_isolation(dev, head_photo_loss):
 def test_against_the_unfused_composition(dev, native, head_photo_loss):
     from svbrdf_estimation_amd import losses, renderers
     enc, ph, sc = hp.pow2_inputs("64_host")
-    ref = hp.Reference(enc, ph, sc)
+    ref = photo_checks.Reference(enc, ph, sc, head=True)
     d_ph, table = _t(ph, dev), _table(sc, True, dev)
     x = _t(enc, dev).requires_grad_(True)
     fused = head_photo_loss(x, d_ph, table)
@@ -278,7 +267,7 @@ def test_against_the_unfused_composition(dev, native, head_photo_loss):
 
 def test_float64_and_second_order_take_the_composed_definition(dev, head_photo_loss):
     enc, ph, sc = hp.pow2_inputs("16_host")
-    ref = hp.Reference(enc, ph, sc)
+    ref = photo_checks.Reference(enc, ph, sc, head=True)
     d_ph, d_sc = _t(ph, dev), _t(sc, dev)
     x64 = _t(enc, dev).double().requires_grad_(True)
     composed = head_photo_loss(x64, d_ph, d_sc)

@@ -1,7 +1,9 @@
 """Which C entry point the ctypes binding reaches for each form of a fused-loss call, and what every such call must leave
 behind: one launch, a finite loss, zeroed scratch, one begin/end pair for the launch hook.  4 x 4 pixels and one scene are
 the smallest shapes at which a wrong route, a lost hook or a missing ``zero_`` shows; 289 rows is one more than a table
-that rides in the launch's argument block, so a host table of that size is uploaded and reaches the device entry."""
+that rides in the launch's argument block, so a host table of that size is uploaded and reaches the device entry.  The
+weighted photo rows ({"weights": P}: P weight planes per item, uniform in (0, 1) from a fixed seed) repeat the unweighted
+ones: a wrong kernel pick for (gradient, head, weighted) shows as a wrong entry, a non-finite loss or a wrong gradient shape."""
 import numpy as np
 import pytest
 import torch
@@ -25,6 +27,11 @@ ROUTES = [
     ("photo_loss", 9, True, 1, {"head": True}, "svbrdf_head_photo_loss_fwd_bwd_host_scenes"),
     ("photo_loss", 9, False, 1, {"head": True}, "svbrdf_head_photo_loss_fwd_bwd"),
     ("photo_loss", 12, True, 289, {}, "svbrdf_photo_loss_fwd_bwd"),
+    ("photo_loss", 12, True, 1, {"weights": 1}, "svbrdf_photo_loss_weighted_fwd_bwd_host_scenes"),
+    ("photo_loss", 12, False, 1, {"weights": 1}, "svbrdf_photo_loss_weighted_fwd_bwd"),
+    ("photo_loss", 9, True, 1, {"head": True, "weights": 1}, "svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes"),
+    ("photo_loss", 9, False, 1, {"head": True, "weights": 1}, "svbrdf_head_photo_loss_weighted_fwd_bwd"),
+    ("photo_loss", 12, True, 289, {"weights": 289}, "svbrdf_photo_loss_weighted_fwd_bwd"),
 ]
 
 
@@ -48,7 +55,7 @@ class _Recorder:
 @pytest.fixture(scope="module")
 def inputs():
     """device tensors shared by every case (never written): maps, encoded head output, target maps, scene tables and
-    clamped photos of other maps for S = 1 and S = 289"""
+    clamped photos of other maps for S = 1 and S = 289, weights [1,P,4,4] for P = 1 and P = 289"""
     from svbrdf_estimation_amd import _native, environment
     assert torch.cuda.is_available(), "GPU tests need an MI355X (select CPU tests with -m 'not gpu')"
     dev = torch.device("cuda:0")
@@ -62,6 +69,8 @@ def inputs():
         assert tuple(table.shape) == (1, S, 9) and table.dtype == torch.float32
         out["scenes", S] = table
         out["photos", S] = _native.render_fwd(other, table).clamp(0.0, 1.0)
+        out["weights", S] = torch.from_numpy(synth.uniform01(5 + S, (1, S, H, H))).to(dev)
+        assert 0.0 < out["weights", S].min() and out["weights", S].max() < 1.0
     torch.cuda.synchronize()
     return out
 
@@ -75,6 +84,8 @@ def test_fused_loss_call_reaches_its_entry(route, want_grad, inputs, monkeypatch
     x = inputs[channels]
     other = inputs["photos", S] if call == "photo_loss" else inputs["target"]
     scenes = inputs["scenes", S] if on_host else inputs["scenes", S].to(x.device)
+    if "weights" in options:
+        options = dict(options, weights=inputs["weights", options["weights"]])
     _native.xrow(x.device, H)           # (the cached x row: its first use is no part of the call under test)
     rec = _Recorder(_native._load())
     monkeypatch.setattr(_native, "_load", lambda: rec)
@@ -87,7 +98,7 @@ def test_fused_loss_call_reaches_its_entry(route, want_grad, inputs, monkeypatch
     finally:
         _native.set_launch_hook(None)
     torch.cuda.synchronize()
-    reached = [n for n in rec.called if "loss_fwd_bwd" in n]
+    reached = [n for n in rec.called if "loss_fwd_bwd" in n or "loss_weighted_fwd_bwd" in n]
     print("%s -> %s, launches %d, loss %r, hook %r" % (route[:5], reached, after - before, loss.item(), seen))
     assert reached == [entry]
     assert after - before == 1

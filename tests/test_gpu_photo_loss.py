@@ -15,7 +15,6 @@ Speed (test_photo_loss_is_no_slower_than_k3, figures of the last run on an MI355
 event-timed launches at the configuration-2 shape, batches rotating beyond the Infinity Cache, same process, same box: the
 photo loss takes no longer per launch than K3's rendering loss on the same maps.
 """
-import ctypes
 import os
 
 import numpy as np
@@ -25,6 +24,7 @@ import torch
 import photo_checks
 import synth
 import tolerances
+from photo_checks import assert_scratch_is_zero as _scratch_is_zero, scene_table as _table, to_device as _t, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,31 +50,6 @@ def photo_loss():
     fn = losses.PhotoLoss(renderers.LocalRenderer())
     assert fn.uses_fused_kernel() and fn.eps == EPS
     return fn
-
-
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _table(B, seed, n_random=3, n_specular=6):
-    """[B,S,9] host table: what RenderingLoss draws after torch.manual_seed(seed)"""
-    from svbrdf_estimation_amd import losses, renderers
-    fn = losses.RenderingLoss(renderers.LocalRenderer())
-    fn.random_configuration_count, fn.specular_configuration_count = n_random, n_specular
-    torch.manual_seed(seed)
-    return fn.sample_scene_table(B).numpy().copy()
-
-
-def _scratch_is_zero(native):
-    torch.cuda.synchronize()
-    assert native._workspace_cache, "no call has allocated the scratch yet"
-    for ws in native._workspace_cache.values():
-        assert ws.numel() * 8 >= 65 * 8
-        assert not ws.any().item(), "scratch left dirty: %s" % (ws.cpu().numpy()[:65],)
 
 
 def _edge_maps(seed):
@@ -337,77 +312,10 @@ def test_fifty_adam_steps_lower_the_loss(dev, photo_loss, oracle):
     assert np.isfinite(history).all() and history[-1] < history[0]
 
 
-def _event_timed_median(enqueue, n, block, dev):
-    """median over n launches of the time between the events recorded around each; the launches are enqueued while the
-    device is held by `block()` (a spinning wave), so the stream runs them back to back whatever the host's pace"""
-    stream = torch.cuda.current_stream(dev)
-    for i in range(16):
-        enqueue(i)                                   # warm: code objects loaded, clocks up
-    torch.cuda.synchronize(dev)
-    block()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(n + 1)]
-    ev[0].record(stream)
-    for i in range(n):
-        enqueue(i)
-        ev[i + 1].record(stream)
-    torch.cuda.synchronize(dev)
-    return float(np.median([ev[i].elapsed_time(ev[i + 1]) * 1e3 for i in range(n)]))
-
-
-def measure_photo_loss_against_k3(dev, native, sets=6, n=60, rounds=3):
-    """-> dict of medians (us per launch) at the configuration-2 shape, B = 8, 256 x 256, S = 9, by-value scene table,
-    `sets` rotating batches (642 MB for the photo loss, 453 MB for K3: beyond the 256 MB Infinity Cache); the two kernels
-    alternate round by round in one process"""
-    from bench import synthetic_maps
-    from svbrdf_estimation_amd import environment
-    B, H, S = 8, 256, 9
-    lib = native._load()
-    gen = torch.Generator().manual_seed(5)
-    torch.manual_seed(11)
-    table = environment.BatchSceneSampler(B, 3, 6).sample().contiguous()
-    ins = [synthetic_maps(gen, B, H, tied=True).to(dev) for _ in range(sets)]
-    tgs = [synthetic_maps(gen, B, H, tied=True).to(dev) for _ in range(sets)]
-    photos = [native.render_fwd(t, table).clamp_(0.0, 1.0) for t in tgs]          # photographs of the target maps
-    grads = [torch.empty_like(a) for a in ins]
-    xr = native.xrow(dev, H)
-    ws = torch.zeros(65, dtype=torch.int64, device=dev)
-    loss = torch.empty(1, device=dev)
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    clk = torch.zeros(2, dtype=torch.int64, device=dev)
-
-    def photo(i):
-        k = i % sets
-        rc = lib.svbrdf_photo_loss_fwd_bwd_host_scenes(ins[k].data_ptr(), photos[k].data_ptr(), table.data_ptr(), xr.data_ptr(),
-                                                       ctypes.c_float(EPS), loss.data_ptr(), grads[k].data_ptr(), ws.data_ptr(),
-                                                       ws.numel() * 8, B, S, H, H, st)
-        assert rc == 0, lib.svbrdf_last_error()
-
-    def k3(i):
-        k = i % sets
-        rc = lib.svbrdf_mixed_loss_fwd_bwd_host_scenes(ins[k].data_ptr(), tgs[k].data_ptr(), table.data_ptr(), xr.data_ptr(),
-                                                       ctypes.c_float(EPS), ctypes.c_float(0.0), ctypes.c_float(0.01),
-                                                       loss.data_ptr(), grads[k].data_ptr(), ws.data_ptr(), ws.numel() * 8,
-                                                       B, S, H, H, st)
-        assert rc == 0, lib.svbrdf_last_error()
-
-    def block():        # one wave spins for 8 ms on the stream: the timed launches queue up behind it
-        native.clock_probe(clk, ticks=800000)
-
-    res = {"photo_loss_us": [], "k3_us": []}
-    for _ in range(rounds):
-        res["photo_loss_us"].append(_event_timed_median(photo, n, block, dev))
-        res["k3_us"].append(_event_timed_median(k3, n, block, dev))
-    out = {"photo_loss_us": float(np.median(res["photo_loss_us"])), "k3_us": float(np.median(res["k3_us"])), "rounds": res,
-           "device": torch.cuda.get_device_name(dev), "launches_per_round": n, "sets": sets}
-    algorithmic = (12 + 3 * S + 12) * 4 * H * H * B
-    out["photo_loss_frac_of_8TBps"] = algorithmic / (out["photo_loss_us"] * 1e-6) / 8.0e12
-    return out
-
-
 def test_photo_loss_is_no_slower_than_k3(dev, native):
     """K3 is the parent's unchanged kernel and does strictly more arithmetic per pixel-render (two shadings, where this
     kernel has one shading and three loads): no margin."""
-    res = measure_photo_loss_against_k3(dev, native)
+    res = photo_checks.measure_photo_loss_against_k3(dev, native)
     print("[photo-loss] config-2 shape, median us per launch: photo loss %.2f, K3 rendering loss %.2f (rounds %s); "
           "%.3f of 8 TB/s at the algorithmic bytes" % (res["photo_loss_us"], res["k3_us"], res["rounds"],
                                                       res["photo_loss_frac_of_8TBps"]))

@@ -4,7 +4,7 @@ losses.PhotoLoss / HeadPhotoLoss with `weights`):
     L = (1/N) sum w | log(render(scene[b,s], input[b]) + eps) - log(where(w > 0, photo[b,s], 0) + eps) |
 
 against the reference (tests/golden/g21_weighted_photo_loss.npz) and the C oracle's composition
-(tests/weighted_photo_checks.py), through the C ABI -- scene table in device memory and by value -- and through the
+(tests/photo_checks.py with `weights`), through the C ABI -- scene table in device memory and by value -- and through the
 modules, with one weight plane per photo and one per item.  Bounds: tests/tolerances.py unchanged -- loss 1e-6 relative;
 gradient 1e-4 |b| + 1e-5 max|b|, widened by 2 |b - f64| for at most MAX_WIDENED_GRAD elements; at most MAX_TIE_PIXELS tie
 pixels.  By the oracle alone the cases have 0 tie pixels and at most 2 widened elements
@@ -28,6 +28,7 @@ import photo_checks
 import synth
 import tolerances
 import weighted_photo_checks as wp
+from photo_checks import assert_scratch_is_zero as _scratch_is_zero, to_device as _t, to_numpy as _np
 
 pytestmark = pytest.mark.gpu
 EPS = wp.EPS
@@ -53,24 +54,9 @@ def _module(head, normalize="count"):
     return fn
 
 
-def _t(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _scratch_is_zero(native):
-    torch.cuda.synchronize()
-    assert native._workspace_cache, "no call has allocated the scratch yet"
-    for ws in native._workspace_cache.values():
-        assert not ws.any().item(), "scratch left dirty: %s" % (ws.cpu().numpy()[:65],)
-
-
 def _run_all_ways(native, dev, what, x, ph, w, sc, head, ref=None, cap=tolerances.MAX_TIE_PIXELS):
     """C ABI with the device table and with the by-value table, the module through backward(): each within the bounds of
-    `ref` (a wp.Reference, or None), the same bits as each other, forward-only the same loss bitwise, scratch zeroed
+    `ref` (a photo_checks.Reference, or None), the same bits as each other, forward-only the same loss bitwise, scratch zeroed
     -> (loss, gradient) of the device-table C ABI call"""
     d_x, d_ph, d_w, d_sc, h_sc = _t(x, dev), _t(ph, dev), _t(w, dev), _t(sc, dev), torch.from_numpy(np.ascontiguousarray(sc))
     results = {}
@@ -119,7 +105,7 @@ def test_reference_fixture(dev, native, golden, head):
     B, H = int(g["B"]), int(g["H"])
     x = head_checks.fixture_input(int(g["enc_seed"]), B, H) if head else synth.make_maps(int(g["input_seed"]), B, H)
     assert synth.checksum(x) == str(g["enc_sha256" if head else "input_sha256"])
-    ref = wp.Reference(x, g["photos"], g["weights"], g["scenes"], EPS, head=head)
+    ref = photo_checks.Reference(x, g["photos"], g["scenes"], EPS, head=head, weights=g["weights"])
     loss, grad = _run_all_ways(native, dev, "g21 %s vs the oracle" % ("head" if head else "maps"), x, g["photos"], g["weights"],
                                g["scenes"], head, ref)
     ref_loss, ref_grad, ref_grad64 = (g["head_loss"], g["grad9"], g["grad9_f64"]) if head else \
@@ -157,7 +143,7 @@ def test_a_zero_weight_excuses_whatever_the_photo_holds(dev, native, head):
     junk = np.array([np.nan, np.inf, -1.0], np.float32)[(synth.uniform01(991, mask.shape) * 3).astype(np.int64)]
     spoiled = np.where((mask == 0)[:, :, None], junk[:, :, None], c["photos"]).astype(np.float32)
     assert np.isnan(spoiled).any() and np.isposinf(spoiled).any() and (spoiled == -1.0).any()
-    ref = wp.Reference(x, c["photos"], mask, sc, EPS, head=head)            # the clean photos: the spoiled terms dropped
+    ref = photo_checks.Reference(x, c["photos"], sc, EPS, head=head, weights=mask)     # the clean photos: the spoiled terms dropped
     loss, grad = _run_all_ways(native, dev, "mask over spoiled photos", x, spoiled, mask, sc, head, ref)
     assert np.isfinite(loss) and np.isfinite(grad).all()
     dead = np.broadcast_to((mask.max(axis=1) == 0)[:, None], grad.shape)
@@ -254,7 +240,7 @@ def test_edge_forms_of_the_module(dev, native, head):
     for layout in wp.LAYOUTS:
         w9 = c9["weights"][layout]
         _, ref = wp.reference("45_s9", layout, head)
-        full = wp.broadcast_weights(w9, c9["S"]).astype(np.float64)
+        full = photo_checks.broadcast_weights(w9, c9["S"]).astype(np.float64)
         want = ref.loss64 * full.size * 3 / (3.0 * full.sum())
         leaf = _t(x9, dev).requires_grad_(True)
         got = _module(head, "weights")(leaf, _t(c9["photos"], dev), _t(c9["scenes"], dev), _t(w9, dev))

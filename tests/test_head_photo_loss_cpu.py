@@ -20,6 +20,7 @@ import torch
 
 import head_checks
 import head_photo_checks as hp
+import photo_checks
 import synth
 import tolerances
 from test_photo_loss_cpu import (PHOTO_TIED_LOOP_TRANS, PHOTO_TIED_LOOP_VALU_MAX, PREFETCH_MIN_DISTANCE, _compile, _isa_stats,
@@ -57,7 +58,7 @@ def g20(golden):
     g = golden("g20_head_photo_loss.npz")
     enc = head_checks.fixture_input(int(g["enc_seed"]), int(g["B"]), int(g["H"]))
     assert synth.checksum(enc) == str(g["enc_sha256"]), "synthetic inputs are not bit-reproducible here"
-    return g, enc, hp.Reference(enc, g["photos"], g["scenes"], float(g["eps"]))
+    return g, enc, photo_checks.Reference(enc, g["photos"], g["scenes"], float(g["eps"]), head=True)
 
 
 def test_fixture_is_what_its_generator_describes(g20):
@@ -90,7 +91,6 @@ def test_oracle_composition_reproduces_the_reference_fixture(g20):
     tolerances.assert_loss_close(ref.loss, g["loss"], "oracle fp32 vs reference fp32")
     tolerances.assert_loss_close(ref.loss64, g["loss_f64"], "oracle fp64 vs reference fp64")
     tolerances.assert_loss_close(ref.loss, g["loss_f64"], "oracle fp32 vs reference fp64")
-    import photo_checks
     # (the reference's double evaluation decodes in double, the composition shades the float32 decode: the project's
     # gradient bound, not the 1e-6 of two double evaluations of the same maps)
     photo_checks.assert_photo_grad_close(ref.grad64, g["grad9_f64"], None, ref.tie, "g20 oracle fp64 vs reference fp64")
@@ -113,11 +113,11 @@ def test_oracle_composition_against_torch_float64_autograd(gen):
     sc = head_checks.scene_table(81, B, 2, 3)
     photos = hp.photographs(synth.make_maps(8101, B, H, tiled_roughness=(gen != "full")), sc)
     for eps in (0.1, 0.02):
-        ref = hp.Reference(enc, photos, sc, eps)
+        ref = photo_checks.Reference(enc, photos, sc, eps, head=True)
         t_loss, t_grad, t_maps = hp.torch_head_photo_loss(enc, photos, sc, eps, maps_values=ref.maps)
         scale = np.abs(t_grad).max()
         exact12 = ref.grad12_64 + hp.upstream_rounding_term(ref.maps, photos, sc, eps)
-        exact = hp.chain9(enc, ref.maps, exact12, n=t_maps[:, 0:3])
+        exact = photo_checks.chain9(enc, ref.maps, exact12, n=t_maps[:, 0:3])
         print("[head-photo] %s eps %.2f: loss %.15g vs torch %.15g, gradient off by %.2e of max (as compared on the GPU: %.2e)" % (
             gen, eps, ref.loss64, t_loss, np.abs(exact - t_grad).max() / scale, np.abs(ref.grad64 - t_grad).max() / scale))
         assert abs(ref.loss64 - t_loss) <= 1e-12 * abs(t_loss)
@@ -148,7 +148,7 @@ def test_gpu_cases_stay_inside_the_caps_by_the_comparison_values_alone():
     tests/test_gpu_head_photo_loss.py compares element-wise (the 256 x 256 case is counted there, on the device's box)"""
     worst = 0
     for name, (enc, photos, sc) in _gpu_cases():
-        ref = hp.Reference(enc, photos, sc)
+        ref = photo_checks.Reference(enc, photos, sc, head=True)
         ties, widened = ref.n_ties(), ref.n_widened()
         if ties or widened:
             print("[head-photo] %s: %d tie pixels, %d widened" % (name, ties, widened))

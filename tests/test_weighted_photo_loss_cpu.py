@@ -5,7 +5,7 @@ HeadPhotoLoss with `weights`), everything that needs no GPU:
     arguments before it launches anything;
   * tests/golden/g21_weighted_photo_loss.npz -- written by the reference (tests/golden/make_golden_weighted_photo.py), NaN
     in the photos under zero weights -- is what its generator describes and is reproduced by the oracle's composition
-    (tests/weighted_photo_checks.py) within the project's bounds, maps and head;
+    (tests/photo_checks.py with `weights`) within the project's bounds, maps and head;
   * the inputs the GPU tests use stay inside the caps by the comparison values alone;
   * PhotoLoss / HeadPhotoLoss with a plugin renderer and weights ARE the composed definition bit for bit; NaN photos under
     zero weights give a finite loss and a finite gradient through autograd; normalize="weights"; argument checks;
@@ -131,7 +131,7 @@ def test_fixture_is_what_its_generator_describes(g21):
 @pytest.mark.parametrize("head", [False, True], ids=["maps", "head"])
 def test_oracle_composition_reproduces_the_reference_fixture(g21, head):
     g, inp, enc = g21
-    ref = wp.Reference(enc if head else inp, g["photos"], g["weights"], g["scenes"], float(g["eps"]), head=head)
+    ref = photo_checks.Reference(enc if head else inp, g["photos"], g["scenes"], float(g["eps"]), head=head, weights=g["weights"])
     loss, loss64 = (g["head_loss"], g["head_loss_f64"]) if head else (g["loss"], g["loss_f64"])
     grad, grad64 = (g["grad9"], g["grad9_f64"]) if head else (g["grad_input"], g["grad_input_f64"])
     print("[weighted-photo] g21 %s: fixture loss %.9g (f64 %.12g), oracle %.9g (f64 %.12g); %d tie pixels, %d widened" % (

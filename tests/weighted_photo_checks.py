@@ -1,110 +1,16 @@
-"""Shared by tests/test_weighted_photo_loss_cpu.py and tests/test_gpu_weighted_photo_loss.py: the ORACLE's weighted photo
-loss, composed as tests/photo_checks.py composes the unweighted one.
-
-With w[b,s,i,j] in [0, 1] ([B,S,H,W], or [B,1,H,W] shared by the item's photos), N = B S 3 H W and
-p' = where(w > 0, photo, 0):
-
-    rad   = c_oracle.render_fwd(input, scenes)
-    delta = log(rad + eps) - log(p' + eps)              the photo is REPLACED under a zero weight, never multiplied
-    loss  = sum(w |delta|) / N
-    g     = w sign(delta) / (N (rad + eps))
-    grad  = c_oracle.render_bwd(input, scenes, g)
-
-f64=True evaluates everything in double on the same float32 inputs.  For the head losses the 12-channel gradient goes
-through head_photo_checks.chain9 at the float32-decoded maps (class Reference with head=True).
-
-Ties: photo_checks.tie_map's rule, and a term under a weight of exactly 0 is STRUCTURAL as well -- it is exactly 0 with
-gradient exactly 0 in every evaluation, whatever its delta.  The comparison goes through photo_checks.assert_photo_grad_close,
-hence tolerances.assert_grad_close: every allowance lands in the session's ledger.
+"""Shared by tests/test_weighted_photo_loss_cpu.py and tests/test_gpu_weighted_photo_loss.py: the weight fields and the cases
+the photo losses with per-pixel confidence weights are compared at, and their speed measurement.  The oracle's composition,
+its tie rule and the comparison values of one case are tests/photo_checks.py's, with `weights`.
 """
 import numpy as np
 
-import head_photo_checks
 import photo_checks
 import synth
-import tolerances
 from oracle import c_oracle
 
-EPS = 0.1
+EPS = photo_checks.EPS
 ENTRIES = ("svbrdf_photo_loss_weighted_fwd_bwd", "svbrdf_photo_loss_weighted_fwd_bwd_host_scenes",
            "svbrdf_head_photo_loss_weighted_fwd_bwd", "svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes")
-
-
-def broadcast_weights(weights, S):
-    """[B,S,H,W] float32 from [B,S,H,W] or [B,1,H,W]"""
-    w = np.asarray(weights, np.float32)
-    assert w.ndim == 4 and w.shape[1] in (1, S), w.shape
-    return np.ascontiguousarray(np.broadcast_to(w, (w.shape[0], S) + w.shape[2:]))
-
-
-def excused_photos(photos, weights):
-    """p' = where(w > 0, photo, 0): [B,S,3,H,W] float32"""
-    photos = np.asarray(photos, np.float32)
-    w = broadcast_weights(weights, photos.shape[1])
-    return np.where((w > 0)[:, :, None], photos, np.float32(0.0)).astype(np.float32)
-
-
-def oracle_weighted_photo_loss(inp, photos, weights, scenes, eps=EPS, f64=False, want_grad=True):
-    """-> (loss: float, grad [B,12,H,W] float32 / float64 or None, delta [B,S,3,H,W] of the excused photos)"""
-    inp = np.ascontiguousarray(inp, np.float32)
-    scenes = np.ascontiguousarray(scenes, np.float32)
-    p = excused_photos(photos, weights)
-    w = broadcast_weights(weights, p.shape[1]).astype(np.float64)[:, :, None]
-    rad = c_oracle.render_fwd(inp, scenes, f64=f64)
-    assert rad.shape == p.shape, (rad.shape, p.shape)
-    if f64:
-        a = rad + np.float64(np.float32(eps))
-        b = p.astype(np.float64) + np.float64(np.float32(eps))
-    else:
-        a = rad + np.float32(eps)
-        b = p + np.float32(eps)
-    with np.errstate(invalid="ignore", divide="ignore"):
-        delta = np.log(a) - np.log(b)
-    loss = float((w * np.abs(delta.astype(np.float64))).sum() / float(delta.size))
-    if not want_grad:
-        return loss, None, delta
-    g = (w * np.sign(delta).astype(np.float64) / (float(delta.size) * a.astype(np.float64))).astype(np.float32)
-    return loss, c_oracle.render_bwd(inp, scenes, g, f64=f64), delta
-
-
-def tie_map(inp, photos, weights, scenes, delta_f64):
-    """[B,H,W] float64: smallest |delta_f64| over the pixel's non-structural terms; structural: photo_checks' rule on the
-    excused photos, or a weight of exactly 0"""
-    p = excused_photos(photos, weights)
-    w = broadcast_weights(weights, p.shape[1])
-    structural = ((p == 0.0) & (photo_checks.unclamped_n_dot_wi(inp, scenes) < -1e-6)[:, :, None]) | (w == 0.0)[:, :, None]
-    d = np.where(structural, np.inf, np.abs(np.asarray(delta_f64, np.float64)))
-    return d.min(axis=(1, 2))
-
-
-class Reference:
-    """the oracle's values of one case, computed once: fp32 and fp64 loss and gradient (12 channels, or the 9 encoded ones
-    with head=True: `x` is then the encoded [B,9,H,W] tensor), tie map"""
-
-    def __init__(self, x, photos, weights, scenes, eps=EPS, head=False):
-        self.x = np.ascontiguousarray(x, np.float32)
-        self.maps = c_oracle.head_decode(self.x) if head else self.x
-        self.loss, g32, _ = oracle_weighted_photo_loss(self.maps, photos, weights, scenes, eps)
-        self.loss64, g64, self.delta64 = oracle_weighted_photo_loss(self.maps, photos, weights, scenes, eps, f64=True)
-        if head:
-            self.grad = head_photo_checks.chain9(self.x, self.maps, g32)
-            self.grad64 = head_photo_checks.chain9(self.x, self.maps, g64)
-        else:
-            self.grad, self.grad64 = np.asarray(g32), np.asarray(g64, np.float64)
-        self.tie = tie_map(self.maps, photos, weights, scenes, self.delta64)
-
-    def n_ties(self):
-        return int((self.tie < tolerances.TIE_LEVEL).sum())
-
-    def n_widened(self):
-        """elements, tie pixels excluded, where the fp32 oracle is outside the strict bound against the fp64 oracle"""
-        strict = tolerances.GRAD_RTOL * np.abs(self.grad64) + tolerances.GRAD_ATOL_FRAC * np.abs(self.grad64).max()
-        ties = np.broadcast_to((self.tie < tolerances.TIE_LEVEL)[:, None], self.grad64.shape)
-        return int(((np.abs(self.grad - self.grad64) > strict) & ~ties).sum())
-
-    def assert_close(self, loss, grad, what, max_ties=tolerances.MAX_TIE_PIXELS):
-        tolerances.assert_loss_close(loss, self.loss, what + " loss")
-        return photo_checks.assert_photo_grad_close(grad, self.grad, self.grad64, self.tie, what + " grad", max_ties=max_ties)
 
 
 def weight_field(seed, B, P, H, masked_rows=True):
@@ -141,23 +47,13 @@ LAYOUTS = ("per-photo", "shared")
 B_CASES = 2
 
 
-def scene_table(B, seed, n_random=3, n_specular=6):
-    """[B,S,9] host table: what RenderingLoss draws after torch.manual_seed(seed) (tests/test_gpu_photo_loss.py `_table`)"""
-    import torch
-    from svbrdf_estimation_amd import losses, renderers
-    fn = losses.RenderingLoss(renderers.LocalRenderer())
-    fn.random_configuration_count, fn.specular_configuration_count = n_random, n_specular
-    torch.manual_seed(seed)
-    return fn.sample_scene_table(B).numpy().copy()
-
-
 def case_inputs(name):
     """-> dict of one case: maps [2,12,H,H], enc [2,9,H,H], photos = clip(oracle.render_fwd(target), 0, 1), scenes, and the
     weight field in both layouts, {"per-photo": [2,S,H,H], "shared": [2,1,H,H]}"""
     idx = [c[0] for c in CASES].index(name)
     _, H, (nr, ns), seed, tied = CASES[idx]
     S = nr + ns
-    sc = scene_table(B_CASES, seed, nr, ns)
+    sc = photo_checks.scene_table(B_CASES, seed, nr, ns)
     maps = synth.make_maps(6100 + 2 * idx, B_CASES, H, tiled_roughness=tied)
     target = synth.make_maps(6101 + 2 * idx, B_CASES, H, tiled_roughness=tied)
     photos = np.clip(c_oracle.render_fwd(target, sc), 0.0, 1.0)
@@ -174,8 +70,8 @@ def reference(name, layout, head):
     key = (name, layout, bool(head))
     if key not in _REFERENCES:
         c = case_inputs(name)
-        _REFERENCES[key] = (c, Reference(c["enc"] if head else c["maps"], c["photos"], c["weights"][layout], c["scenes"],
-                                         EPS, head=head))
+        _REFERENCES[key] = (c, photo_checks.Reference(c["enc"] if head else c["maps"], c["photos"], c["scenes"], EPS,
+                                                      head=head, weights=c["weights"][layout]))
     return _REFERENCES[key]
 
 
@@ -212,7 +108,6 @@ def measure_weighted_photo_loss(dev, native, layout="per-photo", sets=6, n=40, r
     ws = torch.zeros(65, dtype=torch.int64, device=dev)
     loss = torch.empty(1, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    clk = torch.zeros(2, dtype=torch.int64, device=dev)
 
     def weighted(i):
         k = i % sets
@@ -233,15 +128,8 @@ def measure_weighted_photo_loss(dev, native, layout="per-photo", sets=6, n=40, r
         leaves[k].grad = None
         losses.composed_photo_loss(leaves[k], photos[k], table, EPS, weights[k]).backward()
 
-    def block():        # one wave spins for 8 ms on the stream: the timed steps queue up behind it
-        native.clock_probe(clk, ticks=800000)
-
     legs = (("weighted_us", weighted), ("unweighted_us", unweighted), ("composition_us", composition))
-    res = {name: [] for name, _ in legs}
-    for _ in range(rounds):
-        for name, fn in legs:
-            res[name].append(head_photo_checks._event_timed_median(fn, n, block, dev))
-    out = {name: float(np.median(v)) for name, v in res.items()}
+    out, res = photo_checks.timed_legs(legs, n, rounds, photo_checks.spinning_wave(native, dev), dev)
     out.update(rounds=res, device=torch.cuda.get_device_name(dev), steps_per_round=n, sets=sets, layout=layout, planes=P)
     out["weighted_frac_of_8TBps"] = (12 + 3 * S + P + 12) * 4 * H * H * B / (out["weighted_us"] * 1e-6) / 8.0e12
     return out

@@ -10,8 +10,9 @@ Infinity Cache, as bench.py does) it prints the event-timed median per launch of
     here on float32 maps),
 the fraction of 8 TB/s at the algorithmic bytes (12 + 3 S + 12) * 4 * H * W * B, and the VALU instructions per
 pixel-render of the scene loops from tools/isa_stats.py (where hipcc is present).  The method is that of
-tests/test_gpu_photo_loss.py::test_photo_loss_is_no_slower_than_k3, which it imports: launches enqueued behind a spinning
-wave so that the stream runs them back to back, an event between every two, medians of interleaved rounds.
+tests/test_gpu_photo_loss.py::test_photo_loss_is_no_slower_than_k3 (tests/photo_checks.py::measure_photo_loss_against_k3, the
+tests' helper module, which this tool imports): launches enqueued behind a spinning wave so that the stream runs them back
+to back, an event between every two, medians of interleaved rounds.
 
 --head: the head leg instead -- the head-fused photo loss (svbrdf_head_photo_loss_fwd_bwd_host_scenes: the generator's
 [B,9,H,W] output in, its gradient out), the 12-channel photo kernel on the decoded maps and the unfused composition
@@ -65,32 +66,30 @@ def isa_lines():
 
 
 def measure_composed(dev, native, sets=6, n=30, rounds=3):
-    import numpy as np
     import torch
     from bench import synthetic_maps
     from svbrdf_estimation_amd import environment, losses
-    import test_gpu_photo_loss as T
+    import photo_checks
     B, H = 8, 256
     gen = torch.Generator().manual_seed(5)
     torch.manual_seed(11)
     table = environment.BatchSceneSampler(B, 3, 6).sample().contiguous()
     ins = [synthetic_maps(gen, B, H, tied=True).to(dev).requires_grad_(True) for _ in range(sets)]
     photos = [native.render_fwd(synthetic_maps(gen, B, H, tied=True).to(dev), table).clamp_(0.0, 1.0) for _ in range(sets)]
-    clk = torch.zeros(2, dtype=torch.int64, device=dev)
 
     def step(i):
         k = i % sets
         ins[k].grad = None
         losses.composed_photo_loss(ins[k], photos[k], table, 0.1).backward()
 
-    return float(np.median([T._event_timed_median(step, n, lambda: native.clock_probe(clk, ticks=800000), dev)
-                            for _ in range(rounds)]))
+    medians, _ = photo_checks.timed_legs((("composed_us", step),), n, rounds, photo_checks.spinning_wave(native, dev), dev)
+    return medians["composed_us"]
 
 
 def child(head=False, weights="none"):
     import torch
     from svbrdf_estimation_amd import _native
-    import test_gpu_photo_loss as T
+    import photo_checks
     dev = torch.device("cuda:0")
     if weights != "none":
         import weighted_photo_checks
@@ -99,7 +98,7 @@ def child(head=False, weights="none"):
         import head_photo_checks
         res = head_photo_checks.measure_head_photo_loss(dev, _native)
     else:
-        res = T.measure_photo_loss_against_k3(dev, _native)
+        res = photo_checks.measure_photo_loss_against_k3(dev, _native)
         res["composed_us"] = measure_composed(dev, _native)
     res["library"] = _native.library_path()
     print("RESULT " + json.dumps(res))
