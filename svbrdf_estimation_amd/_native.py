@@ -5,6 +5,7 @@ autograd glue.  No arithmetic of the hot path happens in Python.  If the shared
 library is missing or fails to load, every entry point raises NativeLibraryError --
 there is deliberately no fallback.
 """
+import collections
 import ctypes
 import os
 import threading
@@ -125,10 +126,24 @@ def _check(rc, what):
         raise NativeLibraryError("%s failed (rc=%d): %s" % (what, rc, msg.decode() if msg else "?"))
 
 
+def _call(entry, device, *args, stream=None):
+    """THE call into the library.  `entry`, a key of SIGNATURES, is looked up on the loaded library and called with `device`
+    selected, `args` and -- as its last argument -- the current raw stream of `device` (or `stream`, a raw handle of the
+    caller's own); a non-zero status raises NativeLibraryError under that same name.  device=None: a host-only entry,
+    nothing to select and no stream to pass."""
+    fn = getattr(_load(), entry)
+    if device is None:
+        rc = fn(*args)
+    else:
+        with _on_device(device):
+            rc = fn(*args, _stream(device) if stream is None else ctypes.c_void_p(stream))
+    _check(rc, entry)
+
+
 def make_xrow_host(W):
     """torch.linspace(-1, 1, W) bit pattern of the reference's CPU path (renderers.py:73)."""
     buf = (ctypes.c_float * W)()
-    _check(_load().svbrdf_make_xrow(ctypes.cast(buf, _fp), W), "svbrdf_make_xrow")
+    _call("svbrdf_make_xrow", None, ctypes.cast(buf, _fp), W)
     return torch.tensor(list(buf), dtype=torch.float32)
 
 
@@ -187,8 +202,37 @@ class _on_device:
             self.ctx.__exit__(*a)
 
 
-def _dims(maps, scenes, channels=12):
-    """-> (B, S, H, W, shared): `scenes` is [B,S,9], or [S,9] = the same S scenes for every map (host tables only)"""
+# How one entry family takes its scene table -- the rule of _scene_table as data, with the family's own wording:
+#   shared         True: a HOST [S,9] table, the same S scenes for every map, is accepted; else the ValueError that refuses it
+#   always_device  the entries take a device table only: a host table is copied over (a plain copy) whatever its size
+#   dtype_note     appended to "scenes must be float32 (got ...)"
+#   elsewhere      the ValueError for a device table that does not live with the maps ({}: its device, the maps')
+#   pair           None, or the two ValueErrors of the second per-row table that travels with the scenes (size or dtype;
+#                  not on the scenes' side)
+_TableRule = collections.namedtuple("_TableRule", "shared always_device dtype_note elsewhere pair")
+_RENDER_TABLE = _TableRule(True, False, "", "scenes are on {}, the maps on {}: a device scene table must live with the maps", None)
+_F64_TABLE = _RENDER_TABLE._replace(
+    always_device=True, elsewhere="scenes are on {}, the maps on {}",
+    dtype_note=": positions and colours are float32 in the reference whatever the maps' dtype (torch.Tensor(...), "
+               "renderers.py:79,91,98)")
+_INPUTS_TABLE = _TableRule("render_inputs needs one scene row per photo: scenes must be [B,S,9]", False, "",
+                           "device scene / noise tables must live with the maps",
+                           ("noise_std must be a float32 tensor of B*S = %d levels",
+                            "scenes and noise_std must both be on the host or both on the maps' device"))
+_LOSS_TABLE = _TableRule("the loss needs one scene table per batch item: scenes must be [B,S,9]", False, "",
+                         "input, target and scenes must be on the same device", None)
+_PHOTO_TABLE = _LOSS_TABLE._replace(shared="the loss needs one scene row per photo: scenes must be [B,S,9]",
+                                    elsewhere="input, photos and scenes must be on the same device")
+
+
+def _scene_table(rule, maps, scenes, pair=None, channels=12):
+    """THE hand-over of a scene table to a launch on the device of `maps` ([B,channels,H,W], H = W), by `rule` (above).
+    `scenes` is fp32 [B,S,9], or on the host [S,9] = the same S scenes for every map.  A HOST table of at most
+    host_scenes_max_rows() rows rides in the launch's kernel-argument block: no copy.  A larger one is uploaded through
+    the pinned ring, shared rows expanded per map first, and `pair` (one fp32 value per row, on the scenes' side) with
+    it.  A device table must live with the maps.
+    -> (table, B, S, H, W, on_host, shared, pair): contiguous tensors; on_host: `table` goes by value (the *_host_scenes
+    entries), with `shared` its rows serve every map."""
     if not isinstance(scenes, torch.Tensor):
         raise TypeError("scenes must be a torch.Tensor")
     if maps.dim() != 4 or maps.shape[1] != channels:
@@ -196,29 +240,46 @@ def _dims(maps, scenes, channels=12):
     B, _, H, W = maps.shape
     if H != W:
         raise ValueError("H must equal W (got %dx%d): the reference transposes the x grid, renderers.py:75" % (H, W))
-    if scenes.dim() == 2 and not scenes.is_cuda and scenes.shape[1] == 9:
-        return B, scenes.shape[0], H, W, True
-    if scenes.dim() != 3 or scenes.shape[0] != B or scenes.shape[2] != 9:
+    on_host = not scenes.is_cuda
+    shared = on_host and scenes.dim() == 2 and scenes.shape[1] == 9
+    if shared:
+        if rule.shared is not True:
+            raise ValueError(rule.shared)
+    elif scenes.dim() != 3 or scenes.shape[0] != B or scenes.shape[2] != 9:
         raise ValueError("scenes must be [B,S,9], got %s for B=%d" % (tuple(scenes.shape), B))
-    return B, scenes.shape[1], H, W, False
-
-
-def _scene_table_for_launch(scenes, device):
-    """A HOST fp32 table that fits rides in the launch's kernel-argument block (-> host tensor, True); a larger one
-    is uploaded, shared rows expanded per map by the caller (-> device tensor, False); a device table passes."""
-    if not isinstance(scenes, torch.Tensor):
-        raise TypeError("scenes must be a torch.Tensor")
+    S = scenes.shape[-2]
     if scenes.dtype != torch.float32:
-        raise TypeError("scenes must be float32 (got %s)" % scenes.dtype)
-    if scenes.is_cuda:
-        if scenes.device != device:     # the raw pointer would be dereferenced by a kernel running on `device`
-            raise ValueError("scenes are on %s, the maps on %s: a device scene table must live with the maps"
-                             % (scenes.device, device))
-        return (scenes if scenes.is_contiguous() else scenes.contiguous()), False
-    rows = scenes.numel() // 9
-    if rows <= host_scenes_max_rows():
-        return (scenes if scenes.is_contiguous() else scenes.contiguous()), True
-    return upload_scene_table(scenes, device), False
+        raise TypeError("scenes must be float32 (got %s)%s" % (scenes.dtype, rule.dtype_note))
+    if pair is not None:
+        if not isinstance(pair, torch.Tensor) or pair.dtype != torch.float32 or pair.numel() != B * S:
+            raise ValueError(rule.pair[0] % (B * S))
+        if pair.is_cuda == on_host:
+            raise ValueError(rule.pair[1])
+    device = maps.device
+    if on_host and (rule.always_device or (S if shared else B * S) > host_scenes_max_rows()):
+        if shared:
+            scenes, shared = scenes.unsqueeze(0).expand(B, S, 9), False
+        if rule.always_device:
+            scenes = scenes.to(device)
+        else:
+            scenes = upload_scene_table(scenes, device)
+            pair = upload_scene_table(pair.reshape(-1), device) if pair is not None else None
+        on_host = False
+    if not on_host and (scenes.device != device or (pair is not None and pair.device != device)):
+        # (the raw pointer would be dereferenced by a kernel running on `device`)
+        raise ValueError(rule.elsewhere.format(scenes.device, device))
+    if not scenes.is_contiguous():
+        scenes = scenes.contiguous()
+    if pair is not None and not pair.is_contiguous():
+        pair = pair.contiguous()
+    return scenes, B, S, H, W, on_host, shared, pair
+
+
+def loss_scene_table(input, scenes, head=False):
+    """The scene table of a rendering_loss call on `input`, handed over ahead of it: the device table a large host table
+    was uploaded to, else the table itself.  For a caller that launches more than once on one table
+    (losses.RenderingLoss when the target's gradient is wanted too): one upload serves all its launches."""
+    return _scene_table(_LOSS_TABLE, input, scenes, channels=9 if head else 12)[0]
 
 
 def _require_device_float(t, name):
@@ -229,40 +290,32 @@ def _require_device_float(t, name):
     return False
 
 
-def _scene_table_f64(maps, scenes):
-    """the float32 DEVICE table [B,S,9] the float64 entry points take (shared rows expanded per map)"""
-    B, S, H, W, shared = _dims(maps, scenes)
-    if scenes.dtype != torch.float32:
-        raise TypeError("scenes must be float32 (got %s): positions and colours are float32 in the reference whatever the "
-                        "maps' dtype (torch.Tensor(...), renderers.py:79,91,98)" % scenes.dtype)
-    if shared:
-        scenes = scenes.unsqueeze(0).expand(B, S, 9)
-    if scenes.is_cuda and scenes.device != maps.device:
-        raise ValueError("scenes are on %s, the maps on %s" % (scenes.device, maps.device))
-    return scenes.to(maps.device).contiguous(), B, S, H, W
-
-
-def _render_fwd_f64(maps, scenes):
-    table, B, S, H, W = _scene_table_f64(maps, scenes)
-    out = torch.empty((B, S, 3, H, W), dtype=torch.float64, device=maps.device)
-    with _on_device(maps.device):
-        _check(_load().svbrdf_render_fwd_f64(maps.data_ptr(), table.data_ptr(), xrow(maps.device, W).data_ptr(),
-                                             out.data_ptr(), B, S, H, W, _stream(maps.device)), "svbrdf_render_fwd_f64")
+def _render(maps, scenes, bwd, grad_out=None):
+    """the one body of render_fwd and render_bwd (`bwd`: with the cotangent `grad_out`), float32 and float64 maps"""
+    f64 = _require_device_float(maps, "maps")
+    if not maps.is_contiguous():
+        maps = maps.contiguous()
+    if bwd:
+        if not f64:
+            _require_device_f32(grad_out, "grad_out")
+        elif grad_out.dtype != torch.float64 or not grad_out.is_cuda:
+            raise TypeError("grad_out must be a float64 device tensor for float64 maps")
+        if not grad_out.is_contiguous():
+            grad_out = grad_out.contiguous()
+    table, B, S, H, W, on_host, shared, _ = _scene_table(_F64_TABLE if f64 else _RENDER_TABLE, maps, scenes)
+    if bwd:
+        if grad_out.numel() != B * S * 3 * H * W or grad_out.shape[-2:] != maps.shape[-2:]:
+            raise ValueError("grad_out must be [B,S,3,H,W]")
+        out = torch.empty_like(maps)
+        results = (grad_out.data_ptr(), out.data_ptr())
+    else:
+        out = torch.empty((B, S, 3, H, W), dtype=maps.dtype, device=maps.device)
+        results = (out.data_ptr(),)
+    # svbrdf_render_{fwd,bwd}[_f64 | _host_scenes]; the by-value entries take the shared flag behind the table
+    _call("svbrdf_render_" + ("bwd" if bwd else "fwd") + ("_f64" if f64 else "_host_scenes" if on_host else ""), maps.device,
+          maps.data_ptr(), table.data_ptr(), *((int(shared),) if on_host else ()), xrow(maps.device, W).data_ptr(), *results,
+          B, S, H, W)
     return out
-
-
-def _render_bwd_f64(maps, scenes, grad_out):
-    table, B, S, H, W = _scene_table_f64(maps, scenes)
-    if grad_out.dtype != torch.float64 or not grad_out.is_cuda:
-        raise TypeError("grad_out must be a float64 device tensor for float64 maps")
-    if grad_out.numel() != B * S * 3 * H * W or grad_out.shape[-2:] != maps.shape[-2:]:
-        raise ValueError("grad_out must be [B,S,3,H,W]")
-    grad = torch.empty_like(maps)
-    with _on_device(maps.device):
-        _check(_load().svbrdf_render_bwd_f64(maps.data_ptr(), table.data_ptr(), xrow(maps.device, W).data_ptr(),
-                                             grad_out.contiguous().data_ptr(), grad.data_ptr(), B, S, H, W,
-                                             _stream(maps.device)), "svbrdf_render_bwd_f64")
-    return grad
 
 
 def render_bwd_jvp_f64(maps, tangent, scenes, grad_out):
@@ -273,18 +326,15 @@ def render_bwd_jvp_f64(maps, tangent, scenes, grad_out):
         if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.is_cuda):
             raise TypeError("%s must be a float64 tensor on a ROCm device" % name)
     maps, tangent, grad_out = maps.contiguous(), tangent.contiguous(), grad_out.contiguous()
-    table, B, S, H, W = _scene_table_f64(maps, scenes)
+    table, B, S, H, W = _scene_table(_F64_TABLE, maps, scenes)[:5]
     if tangent.shape != maps.shape or tangent.device != maps.device:
         raise ValueError("tangent must have the maps' shape and device")
     if grad_out.numel() != B * S * 3 * H * W or grad_out.shape[-2:] != maps.shape[-2:] or grad_out.device != maps.device:
         raise ValueError("grad_out must be [B,S,3,H,W] on the maps' device")
     gm_t = torch.empty_like(maps)
     out_t = torch.empty((B, S, 3, H, W), dtype=torch.float64, device=maps.device)
-    with _on_device(maps.device):
-        _check(_load().svbrdf_render_bwd_jvp_f64(maps.data_ptr(), tangent.data_ptr(), table.data_ptr(),
-                                                 xrow(maps.device, W).data_ptr(), grad_out.data_ptr(), gm_t.data_ptr(),
-                                                 out_t.data_ptr(), B, S, H, W, _stream(maps.device)),
-               "svbrdf_render_bwd_jvp_f64")
+    _call("svbrdf_render_bwd_jvp_f64", maps.device, maps.data_ptr(), tangent.data_ptr(), table.data_ptr(),
+          xrow(maps.device, W).data_ptr(), grad_out.data_ptr(), gm_t.data_ptr(), out_t.data_ptr(), B, S, H, W)
     return gm_t, out_t
 
 
@@ -293,25 +343,7 @@ def render_fwd(maps, scenes):
     every map): a host table of at most host_scenes_max_rows() rows travels with the launch (one dispatch, no copy
     command).  -> renderings [B,S,3,H,W].  float64 maps take the mixed-precision path of the reference (float32
     geometry, double shading: svbrdf_render_fwd_f64) and return float64."""
-    if _require_device_float(maps, "maps"):
-        return _render_fwd_f64(maps if maps.is_contiguous() else maps.contiguous(), scenes)
-    if not maps.is_contiguous():
-        maps = maps.contiguous()
-    B, S, H, W, shared = _dims(maps, scenes)
-    if shared and S > host_scenes_max_rows():
-        scenes, shared = scenes.unsqueeze(0).expand(B, S, 9), False
-    table, on_host = _scene_table_for_launch(scenes, maps.device)
-    out = torch.empty((B, S, 3, H, W), dtype=torch.float32, device=maps.device)
-    lib = _load()
-    with _on_device(maps.device):
-        if on_host:
-            _check(lib.svbrdf_render_fwd_host_scenes(maps.data_ptr(), table.data_ptr(), int(shared),
-                                                     xrow(maps.device, W).data_ptr(), out.data_ptr(), B, S, H, W,
-                                                     _stream(maps.device)), "svbrdf_render_fwd_host_scenes")
-        else:
-            _check(lib.svbrdf_render_fwd(maps.data_ptr(), table.data_ptr(), xrow(maps.device, W).data_ptr(),
-                                         out.data_ptr(), B, S, H, W, _stream(maps.device)), "svbrdf_render_fwd")
-    return out
+    return _render(maps, scenes, False)
 
 
 def device_philox_state(device, generator=None):
@@ -334,33 +366,12 @@ def render_inputs(maps, scenes, noise_std=None, seed=0, offset=0):
     _require_device_f32(maps, "maps")
     if not maps.is_contiguous():
         maps = maps.contiguous()
-    B, S, H, W, shared = _dims(maps, scenes)
-    if shared:
-        raise ValueError("render_inputs needs one scene row per photo: scenes must be [B,S,9]")
-    if scenes.dtype != torch.float32:
-        raise TypeError("scenes must be float32 (got %s)" % scenes.dtype)
-    if noise_std is not None:
-        if not isinstance(noise_std, torch.Tensor) or noise_std.dtype != torch.float32 or noise_std.numel() != B * S:
-            raise ValueError("noise_std must be a float32 tensor of B*S = %d levels" % (B * S))
-        if noise_std.is_cuda != scenes.is_cuda:
-            raise ValueError("scenes and noise_std must both be on the host or both on the maps' device")
-    on_host = not scenes.is_cuda
-    if on_host and B * S > host_scenes_max_rows():
-        scenes = upload_scene_table(scenes, maps.device)
-        noise_std = upload_scene_table(noise_std.reshape(-1), maps.device) if noise_std is not None else None
-        on_host = False
-    if not on_host and (scenes.device != maps.device or (noise_std is not None and noise_std.device != maps.device)):
-        raise ValueError("device scene / noise tables must live with the maps")
-    scenes = scenes.contiguous()
-    sig = noise_std.contiguous() if noise_std is not None else None
+    table, B, S, H, W, on_host, _, sig = _scene_table(_INPUTS_TABLE, maps, scenes, noise_std)
     out = torch.empty((B, S, 3, H, W), dtype=torch.float32, device=maps.device)
-    lib = _load()
-    fn = lib.svbrdf_render_inputs_host_scenes if on_host else lib.svbrdf_render_inputs
-    with _on_device(maps.device):
-        _check(fn(maps.data_ptr(), scenes.data_ptr(), sig.data_ptr() if sig is not None else None,
-                  ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_ulonglong(int(offset) & 0xFFFFFFFFFFFFFFFF),
-                  xrow(maps.device, W).data_ptr(), out.data_ptr(), B, S, H, W, _stream(maps.device)),
-               "svbrdf_render_inputs_host_scenes" if on_host else "svbrdf_render_inputs")
+    _call("svbrdf_render_inputs_host_scenes" if on_host else "svbrdf_render_inputs", maps.device,
+          maps.data_ptr(), table.data_ptr(), sig.data_ptr() if sig is not None else None,
+          ctypes.c_ulonglong(int(seed) & 0xFFFFFFFFFFFFFFFF), ctypes.c_ulonglong(int(offset) & 0xFFFFFFFFFFFFFFFF),
+          xrow(maps.device, W).data_ptr(), out.data_ptr(), B, S, H, W)
     return out
 
 
@@ -371,8 +382,7 @@ def debug_copy(dst, src):
     _require_device_f32(src, "src")
     if dst.numel() != src.numel() or not dst.is_contiguous() or not src.is_contiguous() or dst.device != src.device:
         raise ValueError("debug_copy needs two contiguous tensors of one size on one device")
-    with _on_device(dst.device):
-        _check(_load().svbrdf_debug_copy(dst.data_ptr(), src.data_ptr(), dst.numel(), _stream(dst.device)), "svbrdf_debug_copy")
+    _call("svbrdf_debug_copy", dst.device, dst.data_ptr(), src.data_ptr(), dst.numel())
     return dst
 
 
@@ -383,31 +393,7 @@ def launch_count():
 
 def render_bwd(maps, scenes, grad_out):
     """K2: adjoint of render_fwd (same `scenes` forms) -> grad_maps [B,12,H,W]."""
-    if _require_device_float(maps, "maps"):
-        return _render_bwd_f64(maps if maps.is_contiguous() else maps.contiguous(), scenes, grad_out)
-    _require_device_f32(grad_out, "grad_out")
-    if not maps.is_contiguous():
-        maps = maps.contiguous()
-    if not grad_out.is_contiguous():
-        grad_out = grad_out.contiguous()
-    B, S, H, W, shared = _dims(maps, scenes)
-    if grad_out.numel() != B * S * 3 * H * W or grad_out.shape[-2:] != maps.shape[-2:]:
-        raise ValueError("grad_out must be [B,S,3,H,W]")
-    if shared and S > host_scenes_max_rows():
-        scenes, shared = scenes.unsqueeze(0).expand(B, S, 9), False
-    table, on_host = _scene_table_for_launch(scenes, maps.device)
-    grad = torch.empty_like(maps)
-    lib = _load()
-    with _on_device(maps.device):
-        if on_host:
-            _check(lib.svbrdf_render_bwd_host_scenes(maps.data_ptr(), table.data_ptr(), int(shared),
-                                                     xrow(maps.device, W).data_ptr(), grad_out.data_ptr(), grad.data_ptr(),
-                                                     B, S, H, W, _stream(maps.device)), "svbrdf_render_bwd_host_scenes")
-        else:
-            _check(lib.svbrdf_render_bwd(maps.data_ptr(), table.data_ptr(), xrow(maps.device, W).data_ptr(),
-                                         grad_out.data_ptr(), grad.data_ptr(), B, S, H, W, _stream(maps.device)),
-                   "svbrdf_render_bwd")
-    return grad
+    return _render(maps, scenes, True, grad_out)
 
 
 def _ragged_offsets(counts, B, R, device):
@@ -420,84 +406,59 @@ def _ragged_offsets(counts, B, R, device):
     return torch.tensor(off, dtype=torch.int32).to(device)
 
 
-def render_fwd_ragged(maps, scenes, counts):
-    """K1, ragged: maps [B,12,H,W], scenes [R,9] grouped by map, counts[b] renders for map b -> [R,3,H,W]."""
-    _require_device_f32(maps, "maps")
-    _require_device_f32(scenes, "scenes")
+def _render_ragged(maps, scenes, counts, bwd, grad_out=None):
+    """the one body of render_fwd_ragged and render_bwd_ragged (`bwd`: with the cotangent `grad_out` [R,3,H,W])"""
+    for t, name in ((maps, "maps"), (scenes, "scenes")) + (((grad_out, "grad_out"),) if bwd else ()):
+        _require_device_f32(t, name)
     maps, scenes = maps.contiguous(), scenes.contiguous()
     if maps.dim() != 4 or maps.shape[1] != 12 or maps.shape[2] != maps.shape[3] or scenes.dim() != 2 or scenes.shape[1] != 9:
         raise ValueError("maps must be [B,12,H,H] and scenes [R,9]")
     B, _, H, W = maps.shape
     R = scenes.shape[0]
+    if bwd:
+        grad_out = grad_out.contiguous()
+        if tuple(grad_out.shape) != (R, 3, H, W):
+            raise ValueError("grad_out must be [R,3,H,W]")
     off = _ragged_offsets(counts, B, R, maps.device)
-    out = torch.empty((R, 3, H, W), dtype=torch.float32, device=maps.device)
-    with _on_device(maps.device):
-        _check(_load().svbrdf_render_fwd_ragged(maps.data_ptr(), scenes.data_ptr(), off.data_ptr(),
-                                                xrow(maps.device, W).data_ptr(), out.data_ptr(), B, R, H, W,
-                                                _stream(maps.device)), "svbrdf_render_fwd_ragged")
+    out = torch.empty_like(maps) if bwd else torch.empty((R, 3, H, W), dtype=torch.float32, device=maps.device)
+    _call("svbrdf_render_bwd_ragged" if bwd else "svbrdf_render_fwd_ragged", maps.device, maps.data_ptr(), scenes.data_ptr(),
+          off.data_ptr(), xrow(maps.device, W).data_ptr(), *((grad_out.data_ptr(),) if bwd else ()), out.data_ptr(), B, R, H, W)
     return out
+
+
+def render_fwd_ragged(maps, scenes, counts):
+    """K1, ragged: maps [B,12,H,W], scenes [R,9] grouped by map, counts[b] renders for map b -> [R,3,H,W]."""
+    return _render_ragged(maps, scenes, counts, False)
 
 
 def render_bwd_ragged(maps, scenes, counts, grad_out):
     """K2, ragged: adjoint of render_fwd_ragged -> grad_maps [B,12,H,W] (zeros for a map without renders)."""
-    for t, name in ((maps, "maps"), (scenes, "scenes"), (grad_out, "grad_out")):
-        _require_device_f32(t, name)
-    maps, scenes, grad_out = maps.contiguous(), scenes.contiguous(), grad_out.contiguous()
-    B, _, H, W = maps.shape
-    R = scenes.shape[0]
-    if tuple(grad_out.shape) != (R, 3, H, W):
-        raise ValueError("grad_out must be [R,3,H,W]")
-    off = _ragged_offsets(counts, B, R, maps.device)
-    grad = torch.empty_like(maps)
-    with _on_device(maps.device):
-        _check(_load().svbrdf_render_bwd_ragged(maps.data_ptr(), scenes.data_ptr(), off.data_ptr(),
-                                                xrow(maps.device, W).data_ptr(), grad_out.data_ptr(),
-                                                grad.data_ptr(), B, R, H, W, _stream(maps.device)),
-               "svbrdf_render_bwd_ragged")
-    return grad
-
-
-def _loss_scene_table(scenes, device, what):
-    """The scene table of a fused-loss call -> (table, on_host).  A HOST fp32 [B,S,9] table of at most
-    host_scenes_max_rows() rows rides in the kernel-argument block (no upload); a larger one is uploaded; a device table
-    must live on `device` (`what`: the caller's message when it does not)."""
-    on_host = isinstance(scenes, torch.Tensor) and not scenes.is_cuda
-    if on_host:
-        if scenes.dtype != torch.float32:
-            raise TypeError("scenes must be float32 (got %s)" % scenes.dtype)
-        if scenes.dim() == 3 and scenes.shape[0] * scenes.shape[1] > host_scenes_max_rows():
-            scenes, on_host = upload_scene_table(scenes, device), False
-    else:
-        _require_device_f32(scenes, "scenes")
-    if not on_host and scenes.device != device:
-        raise ValueError(what)
-    return scenes.contiguous(), on_host
+    return _render_ragged(maps, scenes, counts, True, grad_out)
 
 
 def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W, extra=()):
-    """One launch of the fused-loss entry point `entry` (looked up on the loaded library): contiguous device tensors
-    `input` and `other` (target maps or photos), the scene table as _loss_scene_table returned it, `floats` = eps
-    (and l1_weight, eps_l1 for the entries that take them), `extra` = what the entry takes between `other` and the scene
-    table (the weighted photo entries: weights pointer, plane count).  -> (loss [1] device tensor, grad like `input` or None)"""
-    lib = _load()
-    ws = _workspace(input.device, lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
+    """One launch of the fused-loss entry point `entry`: contiguous device tensors `input` and `other` (target maps or
+    photos), the scene table as _scene_table returned it, `floats` = eps (and l1_weight, eps_l1 for the entries that take
+    them), `extra` = what the entry takes between `other` and the scene table (the weighted photo entries: weights
+    pointer, plane count).  -> (loss [1] device tensor, grad like `input` or None)"""
+    ws = _workspace(input.device, _load().svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
     loss = torch.empty(1, dtype=torch.float32, device=input.device)
     grad = torch.empty_like(input) if want_grad else None
     xr = xrow(input.device, W)
     hook = _launch_hook
-    with _on_device(input.device):
-        if hook is not None:
-            hook("begin")
-        rc = getattr(lib, entry)(input.data_ptr(), other.data_ptr(), *extra, scenes.data_ptr(), xr.data_ptr(), *floats,
-                                 loss.data_ptr(), grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel() * 8,
-                                 B, S, H, W, _stream(input.device))
-        if hook is not None:
-            hook("end")
-    if rc != 0:
+    if hook is not None:
+        hook("begin")
+    try:
+        _call(entry, input.device, input.data_ptr(), other.data_ptr(), *extra, scenes.data_ptr(), xr.data_ptr(), *floats,
+              loss.data_ptr(), grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel() * 8, B, S, H, W)
+    except NativeLibraryError:
         # a failed launch may leave partial sums / arrival counts behind: the scratch contract ("every completed
         # call leaves it zeroed") only covers completed calls, so restore it before reporting the error
         ws.zero_()
-    _check(rc, entry)
+        raise
+    finally:
+        if hook is not None:
+            hook("end")
     return loss, grad
 
 
@@ -507,7 +468,6 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
     network head is decoded in the kernel.  Returns (loss [1] device tensor, grad or None)."""
     _require_device_f32(input, "input")
     _require_device_f32(target, "target")
-    scenes, on_host = _loss_scene_table(scenes, input.device, "input, target and scenes must be on the same device")
     if head:
         if input.dim() != 4 or input.shape[1] != 9 or (input.shape[0],) + tuple(input.shape[2:]) != \
                 (target.shape[0],) + tuple(target.shape[2:]):
@@ -516,9 +476,7 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
         raise ValueError("input and target shapes differ: %s vs %s" % (tuple(input.shape), tuple(target.shape)))
     if target.device != input.device:
         raise ValueError("input, target and scenes must be on the same device")
-    B, S, H, W, shared = _dims(target, scenes)
-    if shared:
-        raise ValueError("the loss needs one scene table per batch item: scenes must be [B,S,9]")
+    scenes, B, S, H, W, on_host = _scene_table(_LOSS_TABLE, target, scenes)[:6]
     if on_host:     # the by-value entries exist with the L1 arguments only
         entry = "svbrdf_head_loss_fwd_bwd_host_scenes" if head else "svbrdf_mixed_loss_fwd_bwd_host_scenes"
     elif head:
@@ -544,12 +502,9 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
     excuses the photo value under it (NaN included).  Returns (loss [1] device tensor, grad or None)."""
     _require_device_f32(input, "input")
     _require_device_f32(photos, "photos")
-    scenes, on_host = _loss_scene_table(scenes, input.device, "input, photos and scenes must be on the same device")
     if photos.device != input.device:
         raise ValueError("input, photos and scenes must be on the same device")
-    B, S, H, W, shared = _dims(input, scenes, channels=9 if head else 12)
-    if shared:
-        raise ValueError("the loss needs one scene row per photo: scenes must be [B,S,9]")
+    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, input, scenes, channels=9 if head else 12)[:6]
     if tuple(photos.shape) != (B, S, 3, H, W):
         raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
                          % ((B, S, 3, H, W), tuple(photos.shape)))
@@ -583,9 +538,7 @@ def mix_materials(svbrdf0, svbrdf1, alpha):
         raise ValueError("svbrdf0, svbrdf1 and alpha must be on the same device")
     a, b, w = svbrdf0.contiguous(), svbrdf1.contiguous(), alpha.contiguous().view(-1)
     out = torch.empty_like(a)
-    with _on_device(a.device):
-        _check(_load().svbrdf_mix_materials(a.data_ptr(), b.data_ptr(), w.data_ptr(), out.data_ptr(), B, H, W,
-                                            _stream(a.device)), "svbrdf_mix_materials")
+    _call("svbrdf_mix_materials", a.device, a.data_ptr(), b.data_ptr(), w.data_ptr(), out.data_ptr(), B, H, W)
     return out
 
 
@@ -595,9 +548,8 @@ def clock_probe(out, ticks=300000, stream=None):
     (device int64[2]).  cycles / ticks * 0.1 = shader clock in GHz under whatever else is running."""
     if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.int64 and out.numel() >= 2):
         raise TypeError("out must be a device int64 tensor of at least 2 elements")
-    raw = stream.cuda_stream if stream is not None else _raw_stream(out.device)
-    with _on_device(out.device):
-        _check(_load().svbrdf_debug_clock_probe(out.data_ptr(), int(ticks), ctypes.c_void_p(raw)), "svbrdf_debug_clock_probe")
+    _call("svbrdf_debug_clock_probe", out.device, out.data_ptr(), int(ticks),
+          stream=stream.cuda_stream if stream is not None else None)
     return out
 
 
@@ -618,9 +570,7 @@ def scale_inplace_(data, scale):
     _require_device_f32(scale, "scale")
     if not data.is_contiguous() or scale.numel() != 1:
         raise ValueError("scale_inplace_ needs a contiguous tensor and a one-element scale")
-    with _on_device(data.device):
-        _check(_load().svbrdf_scale_inplace(data.data_ptr(), scale.data_ptr(), data.numel(), _stream(data.device)),
-               "svbrdf_scale_inplace")
+    _call("svbrdf_scale_inplace", data.device, data.data_ptr(), scale.data_ptr(), data.numel())
     return data
 
 

@@ -264,9 +264,9 @@ class RenderingLoss(nn.Module):
             raise _native.NativeLibraryError(
                 "RenderingLoss with the MI355X LocalRenderer needs tensors on a ROCm device "
                 "(got %s); there is no CPU fallback" % input.device)
-        # a small table rides in the kernel-argument block of the launch, a large one is uploaded (pinned ring)
-        if table.shape[0] * table.shape[1] > _native.host_scenes_max_rows():
-            table = _native.upload_scene_table(table, input.device)
+        # handed over here, by the binding's one rule (by value, or uploaded): a call that also wants the target's gradient
+        # launches twice on it, and what the node keeps for create_graph=True is the table as it was launched with
+        table = _native.loss_scene_table(input, table, head)
         return _FusedRenderingLoss.apply(input, target, table,
                                          self.epsilon_render, float(l1_weight), float(eps_l1), bool(head))
 

@@ -96,7 +96,7 @@ def differentiable_render_backward(maps, scenes, grad_out):
     ``create_graph=True`` asks for).  Computed in float64 whatever the maps' dtype (the float32 kernels K1/K2/K3 have no
     second-order companion; float32 maps are promoted exactly) and returned in the maps' dtype.  Also the entry point the
     native host extension calls back into (csrc/host_ext.cpp) when its nodes run under create_graph=True."""
-    table = _native._scene_table_f64(maps, scenes)[0]
+    table = _native._scene_table(_native._F64_TABLE, maps, scenes)[0]
     grad = _RenderBackwardF64.apply(maps.to(torch.float64), grad_out.reshape(table.shape[0], table.shape[1], 3, *maps.shape[-2:])
                                     .to(torch.float64), table)
     return grad.to(maps.dtype)

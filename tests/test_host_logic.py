@@ -662,3 +662,176 @@ print("INSTALL-OK")
 """ % (ref, ROOT, ref, ref)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "INSTALL-OK" in r.stdout, r.stderr[-3000:]
+
+
+# ---------------------------------------------------------------- the ctypes binding's one scene-table hand-over
+# _native._scene_table, driven without a library and without a GPU: the maps are a stand-in with the shape and device the
+# function reads, a "device table" is a host tensor that claims a device, the row limit is set to 6 and upload_scene_table
+# records its calls.  Every expected type and message below is the one the four families' own code gave before they
+# shared this function (render_fwd / render_bwd; the float64 entries; render_inputs; rendering_loss and photo_loss).
+_TABLE_LIMIT = 6
+_DEV0, _DEV1 = torch.device("cuda", 0), torch.device("cuda", 1)
+
+
+class _MapsStandIn:
+    def __init__(self, *shape):
+        self.shape, self.device = torch.Size(shape), _DEV0
+
+    def dim(self):
+        return len(self.shape)
+
+
+class _ClaimsDevice(torch.Tensor):
+    @property
+    def is_cuda(self):
+        return True
+
+    @property
+    def device(self):
+        return self.__dict__.get("claimed", _DEV0)
+
+
+def _on(device, t):
+    t = t.as_subclass(_ClaimsDevice)
+    t.claimed = device
+    return t
+
+
+def _rows(*shape, dtype=torch.float32):
+    return torch.arange(int(np.prod(shape)), dtype=dtype).reshape(shape)
+
+
+_F32 = "scenes must be float32 (got torch.float64)"
+_F64_NOTE = (": positions and colours are float32 in the reference whatever the maps' dtype (torch.Tensor(...), "
+             "renderers.py:79,91,98)")
+_NOT_TENSOR = (TypeError, "scenes must be a torch.Tensor")
+_NOISE_SIZE = (ValueError, "noise_std must be a float32 tensor of B*S = 6 levels")
+_NOISE_SIDE = (ValueError, "scenes and noise_std must both be on the host or both on the maps' device")
+_INPUTS_ELSEWHERE = (ValueError, "device scene / noise tables must live with the maps")
+# id, family, B of the maps, scenes, second per-row table, expectation: (exception type, message), or a dict with on_host,
+# shared, uploads (the shapes upload_scene_table was entered with) and optionally same (the table is the caller's tensor)
+_TABLE_ROWS = [
+    # ---- one fault each: render family
+    ("render-not-a-tensor", "render", 2, lambda: np.zeros((2, 3, 9), np.float32), None, _NOT_TENSOR),
+    ("render-last-dim", "render", 2, lambda: _rows(2, 3, 8), None, (ValueError, "scenes must be [B,S,9], got (2, 3, 8) for B=2")),
+    ("render-other-batch", "render", 2, lambda: _rows(3, 3, 9), None, (ValueError, "scenes must be [B,S,9], got (3, 3, 9) for B=2")),
+    ("render-4d", "render", 2, lambda: _rows(2, 3, 9, 1), None, (ValueError, "scenes must be [B,S,9], got (2, 3, 9, 1) for B=2")),
+    ("render-shared-on-device", "render", 2, lambda: _on(_DEV0, _rows(3, 9)), None,
+     (ValueError, "scenes must be [B,S,9], got (3, 9) for B=2")),
+    ("render-float64", "render", 2, lambda: _rows(2, 3, 9, dtype=torch.float64), None, (TypeError, _F32)),
+    ("render-shared-float64", "render", 2, lambda: _rows(3, 9, dtype=torch.float64), None, (TypeError, _F32)),
+    ("render-device-elsewhere", "render", 2, lambda: _on(_DEV1, _rows(2, 3, 9)), None,
+     (ValueError, "scenes are on cuda:1, the maps on cuda:0: a device scene table must live with the maps")),
+    ("render-maps-3d", "render", None, lambda: _rows(2, 3, 9), None, (ValueError, "maps must be [B,12,H,W], got (12, 4, 4)")),
+    ("render-maps-not-square", "render", (2, 12, 4, 8), lambda: _rows(2, 3, 9), None,
+     (ValueError, "H must equal W (got 4x8): the reference transposes the x grid, renderers.py:75")),
+    # ---- float64 entries
+    ("f64-not-a-tensor", "f64", 2, lambda: [[0.0] * 9], None, _NOT_TENSOR),
+    ("f64-last-dim", "f64", 2, lambda: _rows(2, 3, 8), None, (ValueError, "scenes must be [B,S,9], got (2, 3, 8) for B=2")),
+    ("f64-shared-on-device", "f64", 2, lambda: _on(_DEV0, _rows(3, 9)), None,
+     (ValueError, "scenes must be [B,S,9], got (3, 9) for B=2")),
+    ("f64-float64", "f64", 2, lambda: _rows(2, 3, 9, dtype=torch.float64), None, (TypeError, _F32 + _F64_NOTE)),
+    ("f64-device-float64", "f64", 2, lambda: _on(_DEV0, _rows(2, 3, 9, dtype=torch.float64)), None, (TypeError, _F32 + _F64_NOTE)),
+    ("f64-device-elsewhere", "f64", 2, lambda: _on(_DEV1, _rows(2, 3, 9)), None,
+     (ValueError, "scenes are on cuda:1, the maps on cuda:0")),
+    # ---- render_inputs
+    ("inputs-not-a-tensor", "inputs", 2, lambda: None, None, _NOT_TENSOR),
+    ("inputs-last-dim", "inputs", 2, lambda: _rows(2, 3, 8), None, (ValueError, "scenes must be [B,S,9], got (2, 3, 8) for B=2")),
+    ("inputs-shared", "inputs", 2, lambda: _rows(3, 9), None,
+     (ValueError, "render_inputs needs one scene row per photo: scenes must be [B,S,9]")),
+    ("inputs-float64", "inputs", 2, lambda: _rows(2, 3, 9, dtype=torch.float64), None, (TypeError, _F32)),
+    ("inputs-noise-size", "inputs", 2, lambda: _rows(2, 3, 9), lambda: _rows(5), _NOISE_SIZE),
+    ("inputs-noise-float64", "inputs", 2, lambda: _rows(2, 3, 9), lambda: _rows(2, 3, dtype=torch.float64), _NOISE_SIZE),
+    ("inputs-noise-not-a-tensor", "inputs", 2, lambda: _rows(2, 3, 9), lambda: [0.1] * 6, _NOISE_SIZE),
+    ("inputs-host-scenes-device-noise", "inputs", 2, lambda: _rows(2, 3, 9), lambda: _on(_DEV0, _rows(2, 3)), _NOISE_SIDE),
+    ("inputs-device-scenes-host-noise", "inputs", 2, lambda: _on(_DEV0, _rows(2, 3, 9)), lambda: _rows(2, 3), _NOISE_SIDE),
+    ("inputs-device-scenes-elsewhere", "inputs", 2, lambda: _on(_DEV1, _rows(2, 3, 9)), None, _INPUTS_ELSEWHERE),
+    ("inputs-device-noise-elsewhere", "inputs", 2, lambda: _on(_DEV0, _rows(2, 3, 9)), lambda: _on(_DEV1, _rows(2, 3)),
+     _INPUTS_ELSEWHERE),
+    # ---- the fused losses: rendering_loss ("loss") and photo_loss ("photo": 12 maps, "head": its 9-channel input)
+    ("loss-not-a-tensor", "loss", 2, lambda: np.zeros((2, 3, 9), np.float32), None, _NOT_TENSOR),
+    ("photo-not-a-tensor", "photo", 2, lambda: None, None, _NOT_TENSOR),
+    ("loss-float64", "loss", 2, lambda: _rows(2, 3, 9, dtype=torch.float64), None, (TypeError, _F32)),
+    ("loss-device-float64", "loss", 2, lambda: _on(_DEV0, _rows(2, 3, 9, dtype=torch.float64)), None, (TypeError, _F32)),
+    ("photo-float64", "photo", 2, lambda: _rows(2, 3, 9, dtype=torch.float64), None, (TypeError, _F32)),
+    ("loss-last-dim", "loss", 2, lambda: _rows(2, 3, 8), None, (ValueError, "scenes must be [B,S,9], got (2, 3, 8) for B=2")),
+    ("photo-other-batch", "photo", 2, lambda: _rows(1, 3, 9), None, (ValueError, "scenes must be [B,S,9], got (1, 3, 9) for B=2")),
+    ("loss-device-elsewhere", "loss", 2, lambda: _on(_DEV1, _rows(2, 3, 9)), None,
+     (ValueError, "input, target and scenes must be on the same device")),
+    ("photo-device-elsewhere", "photo", 2, lambda: _on(_DEV1, _rows(2, 3, 9)), None,
+     (ValueError, "input, photos and scenes must be on the same device")),
+    ("loss-shared", "loss", 2, lambda: _rows(3, 9), None,
+     (ValueError, "the loss needs one scene table per batch item: scenes must be [B,S,9]")),
+    ("loss-shared-above-the-limit", "loss", 2, lambda: _rows(7, 9), None,
+     (ValueError, "the loss needs one scene table per batch item: scenes must be [B,S,9]")),
+    ("photo-shared", "photo", 2, lambda: _rows(3, 9), None,
+     (ValueError, "the loss needs one scene row per photo: scenes must be [B,S,9]")),
+    ("head-maps-channels", "head", (2, 12, 4, 4), lambda: _rows(2, 3, 9), None, (ValueError, "maps must be [B,9,H,W], got (2, 12, 4, 4)")),
+    # ---- the hand-over itself
+    ("render-by-value-at-the-limit", "render", 2, lambda: _rows(2, 3, 9), None, dict(on_host=True, shared=False, uploads=[], same=True)),
+    ("render-upload-above-the-limit", "render", 1, lambda: _rows(1, 7, 9), None, dict(on_host=False, shared=False, uploads=[(1, 7, 9)])),
+    ("render-shared-by-value", "render", 2, lambda: _rows(6, 9), None, dict(on_host=True, shared=True, uploads=[], same=True)),
+    ("render-shared-above-the-limit", "render", 2, lambda: _rows(7, 9), None, dict(on_host=False, shared=False, uploads=[(2, 7, 9)])),
+    ("render-not-contiguous", "render", 2, lambda: _rows(3, 2, 9).transpose(0, 1), None, dict(on_host=True, shared=False, uploads=[])),
+    ("render-shared-not-contiguous", "render", 2, lambda: _rows(9, 3).t(), None, dict(on_host=True, shared=True, uploads=[])),
+    ("render-device-table", "render", 2, lambda: _on(_DEV0, _rows(2, 30, 9)), None, dict(on_host=False, shared=False, uploads=[], same=True)),
+    ("f64-device-table", "f64", 2, lambda: _on(_DEV0, _rows(2, 3, 9)), None, dict(on_host=False, shared=False, uploads=[], same=True)),
+    ("loss-by-value-at-the-limit", "loss", 2, lambda: _rows(2, 3, 9), None, dict(on_host=True, shared=False, uploads=[], same=True)),
+    ("loss-upload-above-the-limit", "loss", 1, lambda: _rows(1, 7, 9), None, dict(on_host=False, shared=False, uploads=[(1, 7, 9)])),
+    ("loss-not-contiguous", "loss", 2, lambda: _rows(3, 2, 9).transpose(0, 1), None, dict(on_host=True, shared=False, uploads=[])),
+    ("loss-device-table", "loss", 2, lambda: _on(_DEV0, _rows(2, 30, 9)), None, dict(on_host=False, shared=False, uploads=[], same=True)),
+    ("photo-by-value-at-the-limit", "photo", 2, lambda: _rows(2, 3, 9), None, dict(on_host=True, shared=False, uploads=[], same=True)),
+    ("head-upload-above-the-limit", "head", 7, lambda: _rows(7, 1, 9), None, dict(on_host=False, shared=False, uploads=[(7, 1, 9)])),
+    ("inputs-by-value-at-the-limit", "inputs", 2, lambda: _rows(2, 3, 9), None, dict(on_host=True, shared=False, uploads=[], same=True)),
+    ("inputs-by-value-with-noise", "inputs", 2, lambda: _rows(2, 3, 9), lambda: _rows(3, 2).t(),
+     dict(on_host=True, shared=False, uploads=[])),
+    ("inputs-upload-above-the-limit", "inputs", 1, lambda: _rows(1, 7, 9), None, dict(on_host=False, shared=False, uploads=[(1, 7, 9)])),
+    ("inputs-upload-as-a-pair", "inputs", 1, lambda: _rows(1, 7, 9), lambda: _rows(1, 7),
+     dict(on_host=False, shared=False, uploads=[(1, 7, 9), (7,)])),
+    ("inputs-device-tables", "inputs", 2, lambda: _on(_DEV0, _rows(2, 3, 9)), lambda: _on(_DEV0, _rows(2, 3)),
+     dict(on_host=False, shared=False, uploads=[], same=True)),
+]
+
+
+@pytest.mark.parametrize("row", _TABLE_ROWS, ids=[r[0] for r in _TABLE_ROWS])
+def test_scene_table_hand_over_rule(row, monkeypatch):
+    from svbrdf_estimation_amd import _native
+    _, family, B, make_scenes, make_pair, want = row
+    rule, channels = {"render": (_native._RENDER_TABLE, 12), "f64": (_native._F64_TABLE, 12), "inputs": (_native._INPUTS_TABLE, 12),
+                      "loss": (_native._LOSS_TABLE, 12), "photo": (_native._PHOTO_TABLE, 12), "head": (_native._PHOTO_TABLE, 9)}[family]
+    maps = _MapsStandIn(*((12, 4, 4) if B is None else B if isinstance(B, tuple) else (B, channels, 4, 4)))
+    uploads = []
+
+    def upload(table, device):
+        assert device == _DEV0 and not table.is_cuda and table.dtype == torch.float32
+        uploads.append(table.clone())
+        return _on(device, table.contiguous())
+
+    monkeypatch.setattr(_native, "upload_scene_table", upload)
+    monkeypatch.setattr(_native, "_host_rows", _TABLE_LIMIT)
+    monkeypatch.setattr(_native, "_load", lambda: pytest.fail("the hand-over rule needs no library"))
+    scenes, pair = make_scenes(), (make_pair() if make_pair is not None else None)
+    if not isinstance(want, dict):
+        with pytest.raises(want[0]) as e:
+            _native._scene_table(rule, maps, scenes, pair, channels=channels)
+        assert type(e.value) is want[0] and str(e.value) == want[1]
+        assert not uploads
+        return
+    table, b, S, H, W, on_host, shared, pair_out = _native._scene_table(rule, maps, scenes, pair, channels=channels)
+    assert (b, H, W) == (maps.shape[0], 4, 4) and S == scenes.shape[-2]
+    assert (on_host, shared) == (want["on_host"], want["shared"])
+    assert [tuple(u.shape) for u in uploads] == want["uploads"]
+    assert table.is_contiguous() and table.is_cuda != on_host and table.dtype == torch.float32
+    assert table is scenes or not want.get("same")          # a contiguous table that stays where it is is not copied
+    # the rows that reach the launch are the caller's: as given, or -- shared and above the limit -- repeated per map
+    expect = scenes if shared or scenes.dim() == 3 else scenes.unsqueeze(0).expand(b, S, 9)
+    assert tuple(table.shape) == tuple(expect.shape) and torch.equal(torch.Tensor(table), torch.Tensor(expect))
+    if uploads:
+        assert torch.equal(uploads[0], expect) and table.device == _DEV0
+    if pair is None:
+        assert pair_out is None
+    else:
+        assert pair_out.is_contiguous() and pair_out.is_cuda != on_host and pair_out.numel() == b * S
+        assert torch.equal(torch.Tensor(pair_out).reshape(-1), torch.Tensor(pair).reshape(-1))
+        if len(uploads) == 2:
+            assert torch.equal(uploads[1], pair.reshape(-1))
