@@ -270,6 +270,39 @@ SVBRDF_API int svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes(const float *
                                                                    void *workspace, size_t workspace_bytes, int B, int S,
                                                                    int H, int W, void *stream);
 
+/* The photo losses with a PER-PHOTO EXPOSURE and its gradient, still ONE launch: every captured photograph has an unknown
+ * radiometric scale (flash power, shutter, ISO, white balance).  `exposure` [B,S,3] holds a positive gain per photo and
+ * colour channel that multiplies the light colour of its scene row; with w, p' and N as in the weighted entries (w = 1,
+ * p' = photo when `weights` is NULL, and then weight_planes must be 0):
+ *   loss_out[0]   = (1/N) sum w | log(render(scene[b,s] with colour fl32(colour_c e[b,s,c]), input[b]) + eps) - log(p' + eps) |
+ *   grad_input    = d loss / d input (REQUIRED: these entries are forward + adjoint only)
+ *   grad_exposure = d loss / d exposure [B,S,3] = sum_{i,j} w sign(delta) rad_c / (N (rad_c + eps) e_c), or NULL: the
+ *                   loss and grad_input are bit for bit the same without it.
+ *  - EXPOSURE MUST BE FINITE AND > 0.  A component that is NaN, infinite, 0 or negative gives loss_out[0] = NaN and an
+ *    all-NaN grad_exposure, as does anything else that makes the loss NaN (NaN maps, a bad weight); scratch left zeroed.
+ *  - The gain enters as ONE float32 multiply of the colour column in front of the falloff: loss and grad_input EQUAL BIT FOR
+ *    BIT those of svbrdf_[head_]photo_loss[_weighted]_fwd_bwd on a scene table whose columns 6:9 were multiplied by
+ *    `exposure` in float32; an all-ones exposure gives those entries' results on the table as it is.
+ *  - grad_exposure is summed in integers (fixed point 2^-24 per wave of 64 pixels): bitwise reproducible run to run.  A
+ *    zero-weight plane gives exactly (+-)0 in its photo's three entries.
+ *  - NO GRADIENT WITH RESPECT TO LIGHT OR CAMERA POSITIONS, nor to weights, photos or the colour columns themselves.
+ * The scene table is in device memory (no by-value form).  `workspace`: svbrdf_photo_exposure_workspace_bytes(B, S, H, W)
+ * bytes = the 65 words of svbrdf_rendering_loss_workspace_bytes plus B S 3 accumulator words, under the same contract:
+ * zeroed once by the caller, left zeroed by every completed call (a NaN report included), so one buffer zeroed at that
+ * size serves every fused loss.  Error codes before any launch as the weighted entries'; S <= 1278 (the per-workgroup
+ * sums live in LDS).  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect the three by symbol presence. */
+SVBRDF_API size_t svbrdf_photo_exposure_workspace_bytes(int B, int S, int H, int W);
+SVBRDF_API int svbrdf_photo_loss_exposure_fwd_bwd(const float *input, const float *photos, const float *weights,
+                                                  int weight_planes, const float *exposure, const float *scenes,
+                                                  const float *xrow, float eps, float *loss_out, float *grad_input,
+                                                  float *grad_exposure, void *workspace, size_t workspace_bytes, int B,
+                                                  int S, int H, int W, void *stream);
+SVBRDF_API int svbrdf_head_photo_loss_exposure_fwd_bwd(const float *encoded9, const float *photos, const float *weights,
+                                                       int weight_planes, const float *exposure, const float *scenes,
+                                                       const float *xrow, float eps, float *loss_out,
+                                                       float *grad_encoded9, float *grad_exposure, void *workspace,
+                                                       size_t workspace_bytes, int B, int S, int H, int W, void *stream);
+
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd
  * wrapper to apply the upstream gradient of the loss (the chain rule through

@@ -44,6 +44,8 @@ _fp, _int, _float, _size, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, 
 _DIMS = [_int] * 4 + [_fp]                                            # B, S (or R), H, W, stream
 _LOSS = [_fp] * 4 + [_float] + [_fp] * 3 + [_size] + _DIMS            # input, other, scenes, xrow, eps, loss, grad, ws, bytes
 _LOSS_W = [_fp] * 3 + [_int] + [_fp] * 2 + [_float] + [_fp] * 3 + [_size] + _DIMS   # input, photos, weights, planes, scenes, ...
+# input, photos, weights, planes, exposure, scenes, xrow, eps, loss, grad, grad_exposure, ws, bytes
+_LOSS_X = [_fp] * 3 + [_int] + [_fp] * 3 + [_float] + [_fp] * 4 + [_size] + _DIMS
 _LOSS_L1 = [_fp] * 4 + [_float] * 3 + [_fp] * 3 + [_size] + _DIMS     # ... eps, l1_weight, eps_l1 ...
 _INPUTS = [_fp] * 3 + [_u64] * 2 + [_fp] * 2 + _DIMS
 # name -> (restype, argtypes) of every SVBRDF_API function of include/svbrdf_hip.h, applied once in _load();
@@ -73,6 +75,9 @@ SIGNATURES = {
     "svbrdf_photo_loss_weighted_fwd_bwd_host_scenes": (_int, _LOSS_W),
     "svbrdf_head_photo_loss_weighted_fwd_bwd": (_int, _LOSS_W),
     "svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes": (_int, _LOSS_W),
+    "svbrdf_photo_exposure_workspace_bytes": (_size, [_int] * 4),
+    "svbrdf_photo_loss_exposure_fwd_bwd": (_int, _LOSS_X),
+    "svbrdf_head_photo_loss_exposure_fwd_bwd": (_int, _LOSS_X),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
     "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
     "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
@@ -107,7 +112,7 @@ def _load():
             raise NativeLibraryError("cannot load %s: %s" % (_SO, e))
         for name, (restype, argtypes) in SIGNATURES.items():
             if not hasattr(lib, name):
-                if "photo_loss" in name:    # the photo entries joined ABI version 8 without a bump: an older build lacks them
+                if "photo_loss" in name or "photo_exposure" in name:    # joined ABI version 8 without a bump: an older build lacks them
                     raise NativeLibraryError("%s lacks %s (a build of ABI version 8 older than this binding) -- rebuild"
                                              % (_SO, name))
                 raise NativeLibraryError("%s does not export %s -- rebuild" % (_SO, name))
@@ -436,12 +441,15 @@ def render_bwd_ragged(maps, scenes, counts, grad_out):
     return _render_ragged(maps, scenes, counts, True, grad_out)
 
 
-def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W, extra=()):
+def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W, extra=(), more_grads=(),
+                     workspace_bytes="svbrdf_rendering_loss_workspace_bytes"):
     """One launch of the fused-loss entry point `entry`: contiguous device tensors `input` and `other` (target maps or
     photos), the scene table as _scene_table returned it, `floats` = eps (and l1_weight, eps_l1 for the entries that take
     them), `extra` = what the entry takes between `other` and the scene table (the weighted photo entries: weights
-    pointer, plane count).  -> (loss [1] device tensor, grad like `input` or None)"""
-    ws = _workspace(input.device, _load().svbrdf_rendering_loss_workspace_bytes(B, S, H, W))
+    pointer, plane count; the exposure entries: the exposure pointer behind them), `more_grads` = the output pointers it
+    takes behind the gradient (the exposure entries: grad_exposure), `workspace_bytes` = the library function that sizes
+    its scratch.  -> (loss [1] device tensor, grad like `input` or None)"""
+    ws = _workspace(input.device, getattr(_load(), workspace_bytes)(B, S, H, W))
     loss = torch.empty(1, dtype=torch.float32, device=input.device)
     grad = torch.empty_like(input) if want_grad else None
     xr = xrow(input.device, W)
@@ -450,7 +458,7 @@ def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W,
         hook("begin")
     try:
         _call(entry, input.device, input.data_ptr(), other.data_ptr(), *extra, scenes.data_ptr(), xr.data_ptr(), *floats,
-              loss.data_ptr(), grad.data_ptr() if want_grad else None, ws.data_ptr(), ws.numel() * 8, B, S, H, W)
+              loss.data_ptr(), grad.data_ptr() if want_grad else None, *more_grads, ws.data_ptr(), ws.numel() * 8, B, S, H, W)
     except NativeLibraryError:
         # a failed launch may leave partial sums / arrival counts behind: the scratch contract ("every completed
         # call leaves it zeroed") only covers completed calls, so restore it before reporting the error
@@ -491,7 +499,8 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
     return _fused_loss_call(entry, input.contiguous(), target.contiguous(), scenes, floats, want_grad, B, S, H, W)
 
 
-def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weights=None):
+def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weights=None, exposure=None,
+               want_exposure_grad=False):
     """Fused photo loss (svbrdf_photo_loss_fwd_bwd*): mean |log(render(scenes[b,s], input[b]) + eps) - log(photos[b,s] + eps)|
     and d loss/d input in ONE launch.  input [B,12,H,W] and photos [B,S,3,H,W] device fp32; scenes [B,S,9] fp32 on the
     maps' device, or on the HOST (at most host_scenes_max_rows() rows ride in the launch's argument block, a larger table
@@ -499,7 +508,13 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
     the kernel (svbrdf_head_photo_loss_fwd_bwd*) and the gradient has its 9 channels.  ``weights``: per-pixel confidence
     in [0, 1], float32 [B,S,H,W] (one plane per photo) or [B,1,H,W] (one per item, shared by its photos) on the maps'
     device -- the svbrdf_*photo_loss_weighted_fwd_bwd* entries: sum of w |..| over B S 3 H W, a weight of exactly 0
-    excuses the photo value under it (NaN included).  Returns (loss [1] device tensor, grad or None)."""
+    excuses the photo value under it (NaN included).  Returns (loss [1] device tensor, grad or None).
+
+    ``exposure``: a positive float32 gain per photo and colour channel, [B,S,3] on the maps' device, that multiplies the
+    light colour of its scene row -- the svbrdf_*photo_loss_exposure_fwd_bwd entries, still ONE launch, with or without
+    ``weights``.  They are forward + adjoint with the table in device memory: a host table is uploaded, and ``want_grad``
+    only decides whether the map gradient is returned.  Returns (loss, grad or None, grad_exposure [B,S,3] or None --
+    ``want_exposure_grad``).  A gain that is NaN, infinite or <= 0 gives a NaN loss and an all-NaN grad_exposure."""
     _require_device_f32(input, "input")
     _require_device_f32(photos, "photos")
     if photos.device != input.device:
@@ -519,6 +534,23 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
                              % ((B, S, H, W), tuple(weights.shape)))
         weights = weights.contiguous()      # (kept alive by this frame until the launch is enqueued, stream-ordered)
         stem, extra = stem + "_weighted", (weights.data_ptr(), int(weights.shape[1]))
+    if exposure is not None:
+        _require_device_f32(exposure, "exposure")
+        if exposure.device != input.device:
+            raise ValueError("input, photos and exposure must be on the same device")
+        if tuple(exposure.shape) != (B, S, 3):
+            raise ValueError("exposure must be [B,S,3] = %s for these maps and photos, got %s" % ((B, S, 3), tuple(exposure.shape)))
+        exposure = exposure.contiguous()
+        if on_host:
+            scenes = upload_scene_table(scenes, input.device)
+        if weights is None:
+            extra = (None, 0)
+        grad_exposure = torch.empty_like(exposure) if want_exposure_grad else None
+        loss, grad = _fused_loss_call(
+            ("svbrdf_head_photo_loss" if head else "svbrdf_photo_loss") + "_exposure_fwd_bwd", input.contiguous(),
+            photos.contiguous(), scenes, (ctypes.c_float(eps),), True, B, S, H, W, extra + (exposure.data_ptr(),),
+            (grad_exposure.data_ptr() if want_exposure_grad else None,), "svbrdf_photo_exposure_workspace_bytes")
+        return loss, (grad if want_grad else None), grad_exposure
     entry = stem + "_fwd_bwd" + ("_host_scenes" if on_host else "")
     return _fused_loss_call(entry, input.contiguous(), photos.contiguous(), scenes, (ctypes.c_float(eps),), want_grad,
                             B, S, H, W, extra)

@@ -1218,8 +1218,9 @@ __device__ __forceinline__ void head_bwd(const Head &h, const Grad &g, float ge[
 // (until round 8: four round trips -- arrival, ticket, fetch-and-clear of the slots, fetch-and-clear of the ticket word --
 // a fence and a second workgroup barrier; profiles/HISTORY.md part A000, r08_k3_ab.txt).  The integer that is converted to the
 // loss is the same sum of the same fixed-point terms whatever the arrival order: bitwise reproducible.
-__device__ __forceinline__ void loss_arrive(float t, float fixed_scale, double loss_scale, unsigned long long *__restrict__ ws,
-                                            float *__restrict__ loss_out)
+// -> 0, or for the finisher 1 (2: it reported NaN) -- for a kernel that has more to finish (svbrdf_photo_exposure.hip).
+__device__ __forceinline__ int loss_arrive(float t, float fixed_scale, double loss_scale, unsigned long long *__restrict__ ws,
+                                           float *__restrict__ loss_out)
 {
     const unsigned nblocks = gridDim.x * gridDim.y, bid = blockIdx.y * gridDim.x + blockIdx.x;
     const unsigned slot = bid & (kLossSlots - 1);
@@ -1243,7 +1244,7 @@ __device__ __forceinline__ void loss_arrive(float t, float fixed_scale, double l
     }                           // slot's completer adds to that word: every later add there returns it
     // device-scope returning atomic, performed at the memory side: add + arrival count in one
     const unsigned long long old = atomicAdd(&ws[slot], (1ULL << kLossCountShift) | fixed);
-    if ((unsigned)(old >> kLossCountShift) + 1 != slot_blocks) return;
+    if ((unsigned)(old >> kLossCountShift) + 1 != slot_blocks) return 0;
     const unsigned nslots = nblocks < (unsigned)kLossSlots ? nblocks : (unsigned)kLossSlots;
     const unsigned long long sum = (old & kLossSumMask) + fixed;       // < 2^47: 64 of them stay below 2^53
     // One lane is active, but the address is uniform and the value is not known to be: the compiler's atomic optimiser would
@@ -1254,10 +1255,11 @@ __device__ __forceinline__ void loss_arrive(float t, float fixed_scale, double l
     const unsigned long long slot_sum = ((unsigned long long)sum_hi << 32) | sum_lo;
     const unsigned long long tail = atomicAdd(&ws[kLossSlots], (1ULL << kLossDoneShift) | slot_sum);
     __hip_atomic_store(&ws[slot], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // behind the add: off the chain's wait
-    if ((unsigned)((tail >> kLossDoneShift) & kLossDoneMask) + 1 != nslots) return;
+    if ((unsigned)((tail >> kLossDoneShift) & kLossDoneMask) + 1 != nslots) return 0;
     const unsigned long long total = (tail & kLossTotalMask) + slot_sum;
     loss_out[0] = (tail & kLossNonFiniteFlag) ? __builtin_nanf("") : (float)((double)total * loss_scale);
     __hip_atomic_store(&ws[kLossSlots], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return (tail & kLossNonFiniteFlag) ? 2 : 1;
 }
 
 // the gradient planes of one pixel: 12 channels, or the 9 of the encoded head output (chain rule through decode_head)

@@ -45,16 +45,126 @@ __device__ __forceinline__ void add_term(float w, float lg, float &lsum)
     else lsum += fabsf(lg);
 }
 
+// EXPO (the per-photo exposure kernels of svbrdf_photo_exposure.hip; no kernel of this unit sets it): a positive gain per
+// photo and colour channel multiplies the light colour, and d loss/d gain[s][c] = sum over the pixels of q / (N gain),
+// q = w sign(delta) rad / (rad + eps) = -sign(lg) w (1 - ec / b) from registers the loss already holds.  What the scene
+// loop needs for it:
+struct ExpoLoop {
+    int row;                // this WAVE's row of the dynamic LDS (expo_lds), in words: [kExpoSpill] words that the lanes
+                            // which do not hold the wave's sums store theirs to, then [S][3] fixed-point sums of q
+    bool live;              // the lane's pixel exists (the whole wave runs the loop); q is in units of live ? 2^-24 : 0
+    float per_weight;       // WEIGHTED: N 2^24 -- q from w / N, which the adjoint holds anyway; a missing pixel's weight is 0
+};
+constexpr int kExpoSpill = 4;
+// (LDS by index, not by pointer: a pointer through the struct is a 64-bit generic one, two VGPRs each)
+__device__ __forceinline__ int *expo_lds()
+{
+    extern __shared__ __attribute__((aligned(16))) int expo_words[];
+    return expo_words;
+}
+// dA/dr_hat of the lane's pixel is used behind the scene loop only (DEFER_R), and the exposure loops have no register to
+// hold it meanwhile (the three-lobe loop of the weighted kernel spilled 8 VGPRs to scratch around it): it waits here, put
+// by exposure_body in front of both loops.  `take` reads through an index the compiler cannot see through (an empty
+// asm): it would otherwise forward the stored registers to the load and keep them.
+__device__ __forceinline__ float expo_stash(int k, float put, bool take)
+{
+    __shared__ float words[3 * kLossThreads];
+    int i = k * kLossThreads + (int)threadIdx.x;
+    if (!take) {
+        words[i] = put;
+        return put;
+    }
+    asm volatile("" : "+v"(i));
+    return words[i];
+}
+constexpr float kExpoFixedScale = 16777216.0f;      // 2^24: a wave's sum of q (|q| <= 1 for sane maps) fits 32 bits
+// The limit of ONE channel's sum over a row of 16 lanes, in the same units: sane values reach 16 * 2^24 = 2^28, and the four
+// row sums of a channel are added in int32 (expo_collect's two row_bcast steps): 4 * 1.5 * 2^28 < 2^31 cannot wrap.
+constexpr float kExpoRowLimit = 24.0f * kExpoFixedScale;
+
+// sc[6:9] *= gain, ONE float32 multiply of the colour column in front of the falloff: the rendering is bit for bit that of
+// a scene table whose colour columns were multiplied by the gains in float32, and gains of 1 change nothing.  (The gains
+// are checked once per item and wave: exposure_body.)
+__device__ __forceinline__ void expo_scale(const float gain[3], float sc[9])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) sc[6 + k] *= gain[k];
+}
+
+// the three gains of one render: wave-uniform like its scene row, and loaded with it, two passes ahead
+__device__ __forceinline__ void load_gain(const float *__restrict__ p, float e[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) e[k] = p[k];
+}
+
+// v + (v of the lane DPP control CTRL names), as one instruction.  The integer form with a row mask: rows outside the mask
+// add 0.
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v)
+{
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ int dpp_add(int v)
+{
+    return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false);
+}
+
+__device__ __forceinline__ float expo_unit(const ExpoLoop &xl) { return xl.live ? kExpoFixedScale : 0.0f; }
+
+// The three q of render s (in units of 2^-24: the lane's `unit` is folded into them), summed over the wave -- four float
+// steps inside each row of 16 lanes (fixed lanes, fixed order), the row sums converted to integers, then rows 0 -> 1,
+// 2 -> 3 and 1 -> 3 -- and stored in the wave's own row of LDS sums by its last lane (a plain store: a wave meets every
+// render once; the other lanes store to three words of the wave that nobody reads: a select of the address instead of a
+// branch inside the scene loop, which cost 14 VGPRs).  Integer addition from the rows on, so the result does not depend on the order in which waves and workgroups
+// arrive.  Every lane of the wave must be here (DPP does not read a disabled lane): the exposure kernels run a partial
+// wave's missing pixels on a clamped index with a unit of 0.  A channel's row sum that is NaN or beyond kExpoRowLimit (maps no
+// renderer input can produce: rad + eps inside (0, eps / 8) over a whole row) poisons the loss: every gradient is then
+// reported as NaN, whatever the saturating conversion made of it, and below the limit the integer adds cannot wrap.
+// N channels from channel K0 on: the tied loop collects its three q together (interleaved chains), the three-lobe loop
+// each channel's as soon as it is known (one q alive at a time: that loop has no register to spare).
+template <int N, int K0>
+__device__ __forceinline__ void expo_collect(const ExpoLoop &xl, int s, const float q[N], float &lsum)
+{
+    float r[N];
+    int t[N];
+    bool sane = true;
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = dpp_add<0xb1>(q[k]);         // quad_perm [1,0,3,2]
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x4e>(r[k]);         // quad_perm [2,3,0,1]
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x141>(r[k]);        // row_half_mirror
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x140>(r[k]);        // row_mirror: every lane holds its row's sum
+#pragma unroll
+    for (int k = 0; k < N; ++k) sane &= fabsf(r[k]) <= kExpoRowLimit;     // per channel, as the integer sums are; false for NaN
+    if (!sane) lsum = __builtin_nanf("");
+#pragma unroll
+    for (int k = 0; k < N; ++k) t[k] = dpp_add<0x142, 0xa>((int)r[k]);      // row_bcast:15 into rows 1 and 3
+#pragma unroll
+    for (int k = 0; k < N; ++k) t[k] = dpp_add<0x143, 0xc>(t[k]);           // row_bcast:31 into rows 2 and 3
+    const int dst = (threadIdx.x & 63) == 63 ? xl.row + kExpoSpill + 3 * s : xl.row;
+#pragma unroll
+    for (int k = 0; k < N; ++k) expo_lds()[dst + K0 + k] = t[k];
+}
+
 // one (pixel, scene), tied roughness: loss_pixel_scene with the target shading replaced by the photo's three values.
 // WEIGHTED: `w` is the render's checked weight and `inv_count` already carries it (w / N, folded once per render); a
 // weight of exactly 0 selects every term to exactly 0 -- whatever the photo holds, NaN included: 0 * NaN is never
 // formed -- and lg = 0 with M = 0 gives a gradient of exactly (+-)0.
-template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false>
+// EXPO: q[k] = -sign(lg) w (1 - ec / b[k]) `unit` as well, by loss_grad_of_b's clamp (sign(0) = 0: a zero weight gives
+// (+-)0), collected for render `s` in front of the adjoint: the three q are dead before its registers are needed.
+template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false>
 __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
                                                   float s10, float eps, float inv_count, float &lsum, Grad &acc,
-                                                  [[maybe_unused]] float w = 1.0f)
+                                                  [[maybe_unused]] float w = 1.0f,
+                                                  [[maybe_unused]] const ExpoLoop *xl = nullptr, [[maybe_unused]] int s = 0)
 {
     const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
+    [[maybe_unused]] float q[3];
+    [[maybe_unused]] const float unit = !EXPO ? 0.0f : WEIGHTED ? xl->per_weight : expo_unit(*xl);
     float bt[3];
     photo_terms(ph, s10, ec, bt);
     const Dots di = dots(K, g, mi);
@@ -76,18 +186,26 @@ __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g
         const float lg = differ ? log2_(bt[k] * ib[k]) : 0.0f;
         add_term<WEIGHTED>(w, lg, lsum);
         g_rad[k] = loss_grad_of_b(K, lg, inv_count * ib[k]);
+        if (EXPO) {
+            const float share = fma_(-ec, ib[k], 1.0f);     // rad / (rad + eps)
+            q[k] = loss_grad_of_b(K, lg, WEIGHTED ? (share * inv_count) * unit : share * unit);
+        }
     }
+    if (EXPO) expo_collect<3, 0>(*xl, s, q, lsum);
     if (WITH_GRAD) shade_bwd<1, (DEFER & 1) != 0, (DEFER & 2) != 0, (DEFER & 4) != 0>(K, g, mi, di, li, Fi, fi, g_rad, acc);
 }
 
 // independent roughness channels: loss_pixel_scene_by_channel with the photo as the target side
-template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false>
+template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false>
 __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
                                                              float s10, float eps, float inv_count, float &lsum, Grad &acc,
-                                                             [[maybe_unused]] float w = 1.0f)
+                                                             [[maybe_unused]] float w = 1.0f,
+                                                             [[maybe_unused]] const ExpoLoop *xl = nullptr,
+                                                             [[maybe_unused]] int s = 0)
 {
     const Dots di = dots(K, g, mi);
     const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
+    [[maybe_unused]] const float unit = !EXPO ? 0.0f : WEIGHTED ? xl->per_weight : expo_unit(*xl);
     const float omp = 1.0f - g.p;
     float g_LNp = 0.0f, g_VN = 0.0f, g_LN = 0.0f, sN = 0.0f;
 #pragma unroll
@@ -101,6 +219,13 @@ __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, co
         const bool differ = WEIGHTED ? (b != bt && w != 0.0f) : (b != bt);
         const float lg = differ ? log2_(bt * ib) : 0.0f;
         add_term<WEIGHTED>(w, lg, lsum);
+        if (EXPO) {
+            const float share = fma_(-ec, ib, 1.0f);
+            const float qk[1] = {loss_grad_of_b(K, lg, WEIGHTED ? (share * inv_count) * unit : share * unit)};
+            if (k == 0) expo_collect<1, 0>(*xl, s, qk, lsum);
+            else if (k == 1) expo_collect<1, 1>(*xl, s, qk, lsum);
+            else expo_collect<1, 2>(*xl, s, qk, lsum);
+        }
         if (WITH_GRAD) {
             const float gE = loss_grad_of_b(K, lg, inv_count * ib) * g.E[k];
             const float g_f = gE * di.LNp;
@@ -128,22 +253,24 @@ __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, co
     }
 }
 
-template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false>
+template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false>
 __device__ __forceinline__ void photo_pixel_scene_any(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
                                                       float s10, float eps, float inv_count, float &lsum, Grad &acc,
-                                                      [[maybe_unused]] float w_raw = 1.0f)
+                                                      [[maybe_unused]] float w_raw = 1.0f,
+                                                      [[maybe_unused]] const ExpoLoop *xl = nullptr, [[maybe_unused]] int s = 0)
 {
     if (WEIGHTED) {
+        if (EXPO) w_raw = xl->live ? w_raw : 0.0f;
         const float w = checked_weight(w_raw);
         const float icw = inv_count * w;        // the weight folded into 1/N once per render
         if (NL == 3)
-            photo_pixel_scene_by_channel<WITH_GRAD, DEFER & 3, true>(K, g, mi, ph, s10, eps, icw, lsum, acc, w);
+            photo_pixel_scene_by_channel<WITH_GRAD, DEFER & 3, true, EXPO>(K, g, mi, ph, s10, eps, icw, lsum, acc, w, xl, s);
         else
-            photo_pixel_scene<WITH_GRAD, DEFER, true>(K, g, mi, ph, s10, eps, icw, lsum, acc, w);
+            photo_pixel_scene<WITH_GRAD, DEFER, true, EXPO>(K, g, mi, ph, s10, eps, icw, lsum, acc, w, xl, s);
     } else if (NL == 3)
-        photo_pixel_scene_by_channel<WITH_GRAD, DEFER & 3>(K, g, mi, ph, s10, eps, inv_count, lsum, acc);
+        photo_pixel_scene_by_channel<WITH_GRAD, DEFER & 3, false, EXPO>(K, g, mi, ph, s10, eps, inv_count, lsum, acc, 1.0f, xl, s);
     else
-        photo_pixel_scene<WITH_GRAD, DEFER>(K, g, mi, ph, s10, eps, inv_count, lsum, acc);
+        photo_pixel_scene<WITH_GRAD, DEFER, false, EXPO>(K, g, mi, ph, s10, eps, inv_count, lsum, acc, 1.0f, xl, s);
 }
 
 // the three photo values of one (pixel, render): planes 3 s .. 3 s + 2 of the item's [S,3,H,W] photos.  One buffer resource
@@ -189,13 +316,18 @@ __device__ __forceinline__ void load_photo_weight(const float *__restrict__ rend
 #define SVBRDF_PHOTO_LOAD(P, WT)                                                                                     \
     if (WEIGHTED) load_photo_weight(pp, wp, plane, pix, P, WT);                                                      \
     else load_photo(pp, plane, pix, P);
-template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false>
+// EXPO (forward + adjoint only): the colour of every render is scaled by its gains in front of its geometry
+// (expo_scale), and the render's three q go to the workgroup's sums behind its shading (expo_collect).
+template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false>
 __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float y, const float *__restrict__ scp,
                                                   const float *sc_lds, const float *__restrict__ pp, size_t plane,
                                                   size_t pix, int S, float eps, float inv_count, Grad &acc,
                                                   [[maybe_unused]] const float *__restrict__ wp = nullptr,
-                                                  [[maybe_unused]] size_t wstride = 0, [[maybe_unused]] float poison = 0.0f)
+                                                  [[maybe_unused]] size_t wstride = 0, [[maybe_unused]] float poison = 0.0f,
+                                                  [[maybe_unused]] const ExpoLoop *xl = nullptr,
+                                                  [[maybe_unused]] const float *__restrict__ gain = nullptr)
 {
+    static_assert(!EXPO || WITH_GRAD, "the exposure kernels are forward + adjoint");
     constexpr int ST = 9;
     // WEIGHTED: the sum starts from the maps' non-finite guard (+0, or NaN which every FMA below keeps) instead of holding
     // it in a register of its own across the loop; 1/N stays a scalar operand of the one multiply per render that uses it
@@ -210,14 +342,25 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
     [[maybe_unused]] float wa = 1.0f, wb = 1.0f;
     SVBRDF_PHOTO_LOAD(pa, wa)                   // render 0
     if (WITH_GRAD) {
+        [[maybe_unused]] float sg[3];
         load_scene(scp, sc);
+        if (EXPO) {
+            load_gain(gain, sg);
+            expo_scale(sg, sc);
+        }
         Geom ga = geometry<true>(K, sc, x, y), gb;
         load_scene(scp + (S > 1 ? ST : 0), sc);
+        if (EXPO) load_gain(gain + (S > 1 ? 3 : 0), sg);
 #define SVBRDF_PHOTO_PASS(G_CUR, G_NEXT, P_CUR, P_NEXT, W_CUR, W_NEXT, SI)                                                        \
         {                                                                                                          \
             asm volatile("" ::"s"(sc[0]), "s"(sc[8]));                                                             \
             float cur[9];                                                                                          \
             _Pragma("unroll") for (int i = 0; i < 9; ++i) cur[i] = sc[i];                                          \
+            if (EXPO) {                                                                                            \
+                expo_scale(sg, cur);                                                                               \
+                load_gain(gain + ((SI) + 2 < S ? 6 : ((SI) + 1 < S ? 3 : 0)), sg);                                 \
+                gain += ((SI) + 1 < S) ? 3 : 0;                                                                    \
+            }                                                                                                      \
             load_scene(scp + ((SI) + 2 < S ? 2 * ST : ((SI) + 1 < S ? ST : 0)), sc);                               \
             scp += ((SI) + 1 < S) ? ST : 0;                                                                        \
             pp += ((SI) + 1 < S) ? render : 0;          /* photo of render s+1 (a harmless repeat on the last pass) */ \
@@ -225,8 +368,8 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
             SVBRDF_PHOTO_LOAD(P_NEXT, W_NEXT)                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                                     \
             G_NEXT = geometry<true>(K, cur, x, y);                                                                 \
-            photo_pixel_scene_any<NL, WITH_GRAD, DEFER, WEIGHTED>(K, G_CUR, mi, P_CUR, s10, eps, inv_count, lsum,  \
-                                                                  acc, W_CUR);                                     \
+            photo_pixel_scene_any<NL, WITH_GRAD, DEFER, WEIGHTED, EXPO>(K, G_CUR, mi, P_CUR, s10, eps, inv_count,  \
+                                                                        lsum, acc, W_CUR, xl, (SI));               \
             SVBRDF_PHOTO_PIN(P_NEXT, W_NEXT)                                                                       \
         }
         for (int s = 0;;) {
@@ -263,7 +406,7 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
         for (int k = 0; k < 3; ++k) {
             if (DEFER & 4) acc.d[k] *= mi.oms[k] * K.inv_pi;
             else if (DEFER & 1) acc.d[k] *= K.inv_pi;
-            if (DEFER & 2) acc.r[k] *= mi.r4m[k];
+            if (DEFER & 2) acc.r[k] *= EXPO ? expo_stash(k, 0.0f, true) : mi.r4m[k];
         }
     }
     return lsum;
@@ -396,6 +539,10 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
 #endif
 #define SVBRDF_PHOTO_LOSS_ATTRS \
     __launch_bounds__(kLossThreads) __attribute__((amdgpu_waves_per_eu(SVBRDF_PHOTO_LOSS_MIN_WAVES, 8)))
+
+// svbrdf_photo_exposure.hip includes this file for the device code above only: its kernels, launcher and entry points
+// are its own
+#ifndef SVBRDF_PHOTO_SHARED_ONLY
 
 // scene table in device memory (any B*S)
 template <bool WITH_GRAD>
@@ -544,8 +691,11 @@ int photo_impl(const char *who, bool scenes_on_host, bool head, bool weighted, c
     return launch_status(who);
 }
 
+#endif  // SVBRDF_PHOTO_SHARED_ONLY
+
 }  // namespace
 
+#ifndef SVBRDF_PHOTO_SHARED_ONLY
 extern "C" {
 
 // Per-pixel confidence weights (added to ABI version 8 without a bump: see include/svbrdf_hip.h)
@@ -620,3 +770,4 @@ int svbrdf_head_photo_loss_fwd_bwd_host_scenes(const float *encoded9, const floa
 }
 
 }  // extern "C"
+#endif  // SVBRDF_PHOTO_SHARED_ONLY

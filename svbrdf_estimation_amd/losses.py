@@ -288,12 +288,20 @@ class _FusedPhotoLoss(torch.autograd.Function):
     ``head``: ``input`` is the generator's [B,9,H,W] post-tanh output, decoded in the kernel (HeadPhotoLoss)."""
 
     @staticmethod
-    def forward(ctx, input, photos, scenes, eps, head, weights=None):
+    def forward(ctx, input, photos, scenes, eps, head, weights=None, exposure=None):
         need_in = ctx.needs_input_grad[0]
-        ctx.save_for_backward(input, photos)        # (for backward(create_graph=True) only: references, no copies)
+        need_e = exposure is not None and ctx.needs_input_grad[6]
+        # (for backward(create_graph=True) only: references, no copies)
+        ctx.save_for_backward(input, photos, *(() if exposure is None else (exposure,)))
         ctx.second_order = (scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head), weights)
-        loss, grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights)
-        ctx.grads = None if grad is None else (grad,)
+        if exposure is None:
+            loss, grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights)
+            ctx.grads = None if grad is None else (grad,)
+        else:
+            # the exposure kernels: both gradients out of the ONE launch
+            loss, grad, grad_e = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights,
+                                                    exposure=exposure, want_exposure_grad=need_e)
+            ctx.grads = None if grad is None and grad_e is None else (grad, grad_e)
         return loss.view(())
 
     @staticmethod
@@ -301,17 +309,22 @@ class _FusedPhotoLoss(torch.autograd.Function):
         if torch.is_grad_enabled():
             # backward(create_graph=True): the kernel's gradient is a constant to autograd; differentiate the composed
             # definition instead (same scenes), in float64 like the other fused losses do
-            input, photos = ctx.saved_tensors
+            input, photos, *exposure = ctx.saved_tensors
             scenes, eps, head, weights = ctx.second_order
+            need = [ctx.needs_input_grad[0], bool(exposure) and ctx.needs_input_grad[6]]
             with torch.enable_grad():
                 x = input.to(torch.float64)
-                loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes, eps, weights)
-                g, = torch.autograd.grad(loss, [input], grad_loss.to(torch.float64).reshape(()), create_graph=True)
-            return g.to(input.dtype), None, None, None, None, None
-        grad, = _hand_over_gradients(ctx, grad_loss, "Trying to backward through the fused photo loss a second time: its "
+                e = exposure[0].to(torch.float64) if exposure else None
+                loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes, eps, weights, e)
+                wanted = [t for t, n in zip((input, exposure[0] if exposure else None), need) if n]
+                grads = list(torch.autograd.grad(loss, wanted, grad_loss.to(torch.float64).reshape(()), create_graph=True))
+            g_in = grads.pop(0).to(input.dtype) if need[0] else None
+            g_e = grads.pop(0).to(exposure[0].dtype) if need[1] else None
+            return g_in, None, None, None, None, None, g_e
+        grads = _hand_over_gradients(ctx, grad_loss, "Trying to backward through the fused photo loss a second time: its "
                                      "gradient buffer was handed to the first backward.  Specify retain_graph=True for "
                                      "the first one.")
-        return grad, None, None, None, None, None
+        return grads[0], None, None, None, None, None, (grads[1] if len(grads) > 1 else None)
 
 
 class _PhotoLossTensor(_UnitGradientLoss):
@@ -356,12 +369,16 @@ def weighted_log_l1(rendered, photos, eps, weights):
     return (w * (torch.log(rendered + eps) - torch.log(p + eps)).abs()).sum() / rendered.numel()
 
 
-def composed_photo_loss(input, photos, scenes, eps, weights=None):
+def composed_photo_loss(input, photos, scenes, eps, weights=None, exposure=None):
     """The photo loss from differentiable pieces -- S renders per item through K1 / K2 (``renderers._RenderFunction``:
     float32 maps through the float32 kernels, float64 maps through the float64 ones), log / L1 mean by torch.  What float64
     maps take and what ``backward(create_graph=True)`` of the fused loss differentiates.  ``scenes`` [B,S,9] float32.
-    ``weights`` ([B,S,H,W] or [B,1,H,W], or None): the weighted definition, ``weighted_log_l1``."""
+    ``weights`` ([B,S,H,W] or [B,1,H,W], or None): the weighted definition, ``weighted_log_l1``.  ``exposure`` (broadcastable
+    to [B,S,3], or None): the per-photo gain, ``rendered * exposure[..., None, None]`` -- the rendering is linear in the
+    light colour the fused kernels scale instead."""
     rendered = renderers._RenderFunction.apply(input, scenes)
+    if exposure is not None:
+        rendered = rendered * exposure[..., None, None]       # (a float64 exposure promotes, as torch ops do)
     if weights is not None:
         return weighted_log_l1(rendered, photos, eps, weights)
     return nn.functional.l1_loss(torch.log(rendered + eps), torch.log(photos.to(rendered.dtype) + eps))
@@ -395,6 +412,30 @@ def _check_weights(weights, input, photos):
     if weights.dtype != torch.float32:
         raise TypeError("weights must be float32, bool or uint8 (got %s)" % weights.dtype)
     return weights
+
+
+def _check_exposure(exposure, input, photos):
+    """``exposure`` as the photo losses take it -> [B,S,3], expanded by torch ops (autograd sums the gradient back over the
+    broadcast); None passes.  A positive gain per photo and colour channel: [B,S,3], or [B,S,1] / [B,S] (one per photo,
+    grey) or [B,1,1] (one per item).  float32, or float64 (which takes the composed definition); on the input's device;
+    it may require grad."""
+    if exposure is None:
+        return None
+    if not isinstance(exposure, torch.Tensor):
+        raise TypeError("exposure must be a tensor")
+    if not exposure.dtype.is_floating_point:
+        raise TypeError("exposure must be float32 or float64 (got %s)" % exposure.dtype)
+    B, S = photos.shape[0], photos.shape[1]
+    if exposure.dim() == 2:
+        exposure = exposure.unsqueeze(-1)           # [B,S]: one gain per photo
+    if tuple(exposure.shape) not in ((B, S, 3), (B, S, 1), (B, 1, 1)):
+        raise ValueError("exposure must be [B,S,3], [B,S,1], [B,S] or [B,1,1] with the photos' B = %d and S = %d, got %s"
+                         % (B, S, tuple(exposure.shape)))
+    if exposure.device != input.device:
+        raise ValueError("input and exposure must be on the same device")
+    if exposure.dtype not in (torch.float32, torch.float64):
+        raise TypeError("exposure must be float32 or float64 (got %s)" % exposure.dtype)
+    return exposure.expand(B, S, 3)
 
 
 def _normalized(loss, weights, photos, normalize):
@@ -437,28 +478,38 @@ class _PhotoLossModule(nn.Module):
     def uses_fused_kernel(self):
         return RenderingLoss(self.renderer).uses_fused_kernel()
 
-    def _forward_decoded(self, encoded9, photos, scenes, weights):
+    def _forward_decoded(self, encoded9, photos, scenes, weights, exposure=None):
         """the head losses' composed definition: PhotoLoss, which normalises by itself, on the decoded maps"""
-        return PhotoLoss(self.renderer, self.eps, self.normalize)(decode_head(encoded9), photos, scenes, weights)
+        return PhotoLoss(self.renderer, self.eps, self.normalize)(decode_head(encoded9), photos, scenes, weights, exposure)
 
-    def _forward(self, x, photos, scenes, weights, head):
+    def _forward(self, x, photos, scenes, weights, head, exposure=None):
         """The one routing of both modules; ``x``: the 12 maps, or with ``head`` the 9 encoded channels.  A plugin renderer
-        and double on either side take the composed definition, everything else is the fused kernel."""
+        and double on any side take the composed definition, everything else is the fused kernel.  ``exposure=None`` is
+        the path without exposure, untouched.  With an exposure the fused path is the exposure kernel (loss and both
+        gradients in one launch) when the input or the exposure requires grad; a pure evaluation multiplies the table's
+        colour columns by the exposure with one torch op and runs the forward-only kernel of the loss without exposure,
+        which computes the same loss bit for bit (there is no forward-only exposure kernel: not on the hot path)."""
         photos = PhotoLoss._check(x, photos, channels=9 if head else 12)
         weights = _check_weights(weights, x, photos)
+        exposure = _check_exposure(exposure, x, photos)
         B, S = photos.shape[0], photos.shape[1]
         if not self.uses_fused_kernel():
             if head:
-                return self._forward_decoded(x, photos, scenes, weights)
-            loss = self._forward_plugin(x, photos, PhotoLoss._scene_objects(scenes, B, S), weights)
+                return self._forward_decoded(x, photos, scenes, weights, exposure)
+            loss = self._forward_plugin(x, photos, PhotoLoss._scene_objects(scenes, B, S), weights, exposure)
         else:
             table = PhotoLoss._scene_table(scenes, B, S)
-            if _check_fused_photo_inputs(*(("HeadPhotoLoss", "encoded9") if head else ("PhotoLoss", "input")), x, photos):
+            double = _check_fused_photo_inputs(*(("HeadPhotoLoss", "encoded9") if head else ("PhotoLoss", "input")), x, photos)
+            if double or (exposure is not None and exposure.dtype == torch.float64):
                 if head:
-                    return self._forward_decoded(x.to(torch.float64), photos, table, weights)   # promoted in front of the decode
-                loss = composed_photo_loss(x.to(torch.float64), photos, table.to(x.device), self.eps, weights)  # float64 K1 / K2
+                    return self._forward_decoded(x.to(torch.float64), photos, table, weights, exposure)   # promoted in front of the decode
+                loss = composed_photo_loss(x.to(torch.float64), photos, table.to(x.device), self.eps, weights, exposure)  # float64 K1 / K2
             else:
-                loss = _FusedPhotoLoss.apply(x, photos, table, float(self.eps), head, weights)
+                if exposure is not None and not (torch.is_grad_enabled() and (x.requires_grad or exposure.requires_grad)):
+                    table = table.to(x.device)
+                    table = torch.cat((table[..., :6], table[..., 6:] * exposure.detach()), dim=-1)
+                    exposure = None
+                loss = _FusedPhotoLoss.apply(x, photos, table, float(self.eps), head, weights, exposure)
                 if (weights is None or self.normalize == "count") and loss.requires_grad:
                     return loss.as_subclass(_PhotoLossTensor)
         return _normalized(loss, weights, photos, self.normalize)
@@ -488,7 +539,17 @@ class PhotoLoss(_PhotoLossModule):
     weights of all ones give the unweighted loss and gradient bit for bit.  Still one launch, one more load per
     pixel-render.  ``normalize="count"`` (default) divides by the number N = B S 3 H W of terms as above;
     ``normalize="weights"`` returns the weighted mean ``sum w|d| / (3 sum w)`` instead (0 when every weight is 0), which
-    costs a reduction over the weights and a scale of the loss on the device (two small launches, no host sync)."""
+    costs a reduction over the weights and a scale of the loss on the device (two small launches, no host sync).
+
+    ``exposure`` (optional): the unknown radiometric scale of a captured photograph -- flash power, shutter, ISO, white
+    balance -- as a positive gain per photo and colour channel that multiplies the light colour of its scene:
+    ``[B,S,3]``, ``[B,S,1]`` or ``[B,S]`` (one grey gain per photo) or ``[B,1,1]`` (one per item), float32 on the input's
+    device.  It may require grad: with this package's ``LocalRenderer`` the loss, ``d loss/d input`` and
+    ``d loss/d exposure`` come out of ONE launch (csrc/svbrdf_photo_exposure.hip), so the gains can be fitted jointly with
+    the maps (in log space: they must stay positive -- a gain that is NaN, infinite or <= 0 gives a NaN loss).  Loss and
+    map gradient equal, bit for bit, those of a scene table whose colour columns were multiplied by the gains in float32.
+    float64 on any side, a plugin renderer and ``backward(create_graph=True)`` take the composed definition,
+    ``rendered * exposure[..., None, None]``.  There is no gradient towards light or camera positions."""
 
     @staticmethod
     def _check(input, photos, channels=12):
@@ -533,13 +594,15 @@ class PhotoLoss(_PhotoLossModule):
         rows = PhotoLoss._scene_objects(scenes, B, S)
         return torch.stack([torch.stack([environment.scene_to_row(sc) for sc in r]) for r in rows])
 
-    def forward(self, input, photos, scenes, weights=None):
-        return self._forward(input, photos, scenes, weights, head=False)
+    def forward(self, input, photos, scenes, weights=None, exposure=None):
+        return self._forward(input, photos, scenes, weights, head=False, exposure=exposure)
 
-    def _forward_plugin(self, input, photos, scenes, weights=None):
+    def _forward_plugin(self, input, photos, scenes, weights=None, exposure=None):
         """the composed definition with a foreign renderer object: its own render() per scene, log, L1 mean"""
         rendered = torch.stack([torch.cat([self.renderer.render(sc, input[b]) for sc in scenes[b]], dim=0)
                                 for b in range(input.shape[0])], dim=0)
+        if exposure is not None:
+            rendered = rendered * exposure[..., None, None]       # (a float64 exposure promotes, as torch ops do)
         if weights is not None:
             return weighted_log_l1(rendered, photos, self.eps, weights)
         return nn.functional.l1_loss(torch.log(rendered + self.eps), torch.log(photos + self.eps))
@@ -607,5 +670,5 @@ class HeadPhotoLoss(_PhotoLossModule):
     either side and ``backward(create_graph=True)`` take the composed definition above, which is also the specification
     of the fused path.  ``weights`` and ``normalize``: per-pixel confidence, exactly as ``PhotoLoss`` documents them."""
 
-    def forward(self, encoded9, photos, scenes, weights=None):
-        return self._forward(encoded9, photos, scenes, weights, head=True)
+    def forward(self, encoded9, photos, scenes, weights=None, exposure=None):
+        return self._forward(encoded9, photos, scenes, weights, head=True, exposure=exposure)

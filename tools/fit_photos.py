@@ -1,11 +1,17 @@
 """Fit SVBRDF maps to photographs with the fused photo loss (losses.PhotoLoss): the inverse-rendering use of the engine.
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
+                               [--fit-exposure]
 
 Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
 each from ``synthesis.render_inputs`` (the scene table is what that call draws from torch's global generator: the same seed
 gives it again).  A perturbed copy of the maps is then a leaf tensor that Adam fits to the photographs through
 ``PhotoLoss`` -- one kernel launch per step for loss and gradient.  Prints the loss per step and the time per step.
+
+``--fit-exposure``: every photograph is taken with a HIDDEN gain per colour channel in [0.5, 2] (an unknown flash power and
+white balance: the light colour of its scene row times the gain, noise-free, clamped to [0, 1]).  The fit starts from a gain
+of 1 and fits the gains jointly with the maps, the parameter in log space (``exposure=log_e.exp()``), still one launch per
+step for the loss and both gradients; the mean |log e - log e*| is printed beside the maps' error.
 """
 import argparse
 import os
@@ -20,7 +26,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import synth  # noqa: E402
-from svbrdf_estimation_amd import losses, renderers, synthesis  # noqa: E402
+from svbrdf_estimation_amd import _native, losses, renderers, synthesis  # noqa: E402
 
 
 def main():
@@ -33,6 +39,7 @@ def main():
     ap.add_argument("--noise", action="store_true", help="sensor noise on the photographs (dataset.py:215-217)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--print-every", type=int, default=10)
+    ap.add_argument("--fit-exposure", action="store_true", help="photographs with hidden per-photo gains, fitted with the maps")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm device"
     dev = torch.device("cuda:0")
@@ -43,14 +50,23 @@ def main():
     photos = synthesis.render_inputs(truth, S, use_augmentation=True, noise="device" if args.noise else None)
     torch.manual_seed(args.seed)
     table = torch.stack([synthesis.input_scene_table(S, True) for _ in range(B)], dim=0).to(dev)
+    log_e, hidden = None, None
+    if args.fit_exposure:
+        if args.noise:
+            ap.error("--fit-exposure renders its photographs noise-free: not combined with --noise")
+        hidden = 0.5 + 1.5 * torch.from_numpy(synth.uniform01(args.seed + 2000, (B, S, 3))).to(dev)
+        scaled = torch.cat((table[..., :6], table[..., 6:] * hidden), dim=-1)
+        photos = _native.render_fwd(truth, scaled).clamp_(0.0, 1.0)
+        log_e = torch.zeros((B, S, 3), device=dev, requires_grad=True)
     start = truth.clone()
     jitter = torch.from_numpy(synth.uniform01(args.seed + 1000, (B, 9, H, H))).to(dev) - 0.5
     start[:, 3:] = (start[:, 3:] + 0.3 * jitter).clamp_(0.02, 0.98)        # diffuse, roughness, specular off by up to 0.15
     x = start.clone().requires_grad_(True)
     fn = losses.PhotoLoss(renderers.LocalRenderer())
-    opt = torch.optim.Adam([x], lr=args.lr)
-    print("fitting %d x [12,%d,%d] maps to %d photographs each (%s), Adam lr %g" % (
-        B, H, H, S, "sensor noise" if args.noise else "noise-free", args.lr))
+    opt = torch.optim.Adam([x] if log_e is None else [x, log_e], lr=args.lr)
+    print("fitting %d x [12,%d,%d] maps to %d photographs each (%s%s), Adam lr %g" % (
+        B, H, H, S, "sensor noise" if args.noise else "noise-free", ", hidden gains fitted too" if args.fit_exposure else "",
+        args.lr))
     t_last, step_ms = None, []
     for step in range(args.steps):
         if step % args.print_every == 0:
@@ -60,15 +76,16 @@ def main():
                 step_ms.append(1e3 * (now - t_last) / args.print_every)
             t_last = now
         opt.zero_grad(set_to_none=True)
-        loss = fn(x, photos, table)
+        loss = fn(x, photos, table) if log_e is None else fn(x, photos, table, None, log_e.exp())
         loss.backward()
         opt.step()
         with torch.no_grad():
             x[:, 3:].clamp_(0.0, 1.0)
         if step % args.print_every == 0 or step == args.steps - 1:
             err = (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
-            print("step %4d  loss %.6f  mean |d,r,s - truth| %.5f%s" % (
-                step, loss.item(), err, "  %.3f ms/step" % step_ms[-1] if step_ms else ""))
+            gains = "" if log_e is None else "  mean |log e - log e*| %.5f" % (log_e.detach() - hidden.log()).abs().mean().item()
+            print("step %4d  loss %.6f  mean |d,r,s - truth| %.5f%s%s" % (
+                step, loss.item(), err, gains, "  %.3f ms/step" % step_ms[-1] if step_ms else ""))
     if step_ms:
         print("median %.3f ms per step (loss + backward + Adam + clamp, host included)" % float(np.median(step_ms)))
 
