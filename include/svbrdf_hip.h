@@ -285,7 +285,7 @@ SVBRDF_API int svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes(const float *
  *    `exposure` in float32; an all-ones exposure gives those entries' results on the table as it is.
  *  - grad_exposure is summed in integers (fixed point 2^-24 per wave of 64 pixels): bitwise reproducible run to run.  A
  *    zero-weight plane gives exactly (+-)0 in its photo's three entries.
- *  - NO GRADIENT WITH RESPECT TO LIGHT OR CAMERA POSITIONS, nor to weights, photos or the colour columns themselves.
+ *  - NO GRADIENT WITH RESPECT TO LIGHT OR CAMERA POSITIONS here (the scene-gradient entries below have it), nor to weights or photos.
  * The scene table is in device memory (no by-value form).  `workspace`: svbrdf_photo_exposure_workspace_bytes(B, S, H, W)
  * bytes = the 65 words of svbrdf_rendering_loss_workspace_bytes plus B S 3 accumulator words, under the same contract:
  * zeroed once by the caller, left zeroed by every completed call (a NaN report included), so one buffer zeroed at that
@@ -302,6 +302,40 @@ SVBRDF_API int svbrdf_head_photo_loss_exposure_fwd_bwd(const float *encoded9, co
                                                        const float *xrow, float eps, float *loss_out,
                                                        float *grad_encoded9, float *grad_exposure, void *workspace,
                                                        size_t workspace_bytes, int B, int S, int H, int W, void *stream);
+
+/* The photo losses with the gradient towards the SCENE TABLE, still ONE launch: the camera position, the light position
+ * and the light colour of every photo are the last unknowns of a capture.  With w, p' and N as in the weighted entries
+ * (w = 1, p' = photo when `weights` is NULL, and then weight_planes must be 0):
+ *   loss_out[0] = (1/N) sum w | log(render(scene[b,s], input[b]) + eps) - log(p' + eps) |
+ *   grad_input  = d loss / d input (REQUIRED: these entries are forward + adjoint only)
+ *   grad_scenes = d loss / d scenes [B,S,9] (REQUIRED): columns 0:3 camera xyz, 3:6 light xyz, 6:9 light rgb.
+ *  - loss and grad_input EQUAL BIT FOR BIT those of svbrdf_[head_]photo_loss[_weighted]_fwd_bwd on the same table.
+ *  - Positions: the derivative of the composed definition (renderers.py:67-104, then the log-L1 mean) with PyTorch's
+ *    sub-gradient conventions -- clamp(min=m) passes the gradient iff x >= m, sign(0) = 0 -- through (1 - VH)^5, both
+ *    Smith terms, D, 1/(4 VN LN), LN+ and the falloff, and back through the normalisations of wo, wi and h.
+ *  - Colour: sum_{i,j} w sign(delta) rad_c / (N (rad_c + eps) colour_c).  A COLOUR MUST BE FINITE AND > 0: one that is NaN,
+ *    infinite, 0 or negative gives loss_out[0] = NaN.  A gain is applied to the table in front of the call; the chain rule
+ *    takes grad_scenes[..., 6:9] back to it.
+ *  - Whatever makes the loss NaN (NaN maps, a bad weight, a bad colour, a wave of 64 pixels whose sum of N |term| is NaN
+ *    or exceeds 2^19) gives an all-NaN grad_scenes; scratch left zeroed.
+ *  - grad_scenes is summed in float inside a wave of 64 pixels (fixed lanes, fixed order) and in 64-bit integers from there
+ *    on (fixed point, unit 2^-24 / N): bitwise reproducible run to run.
+ * The scene table is in device memory (no by-value form).  `workspace`: svbrdf_photo_scene_grad_workspace_bytes(B, S, H, W)
+ * bytes = the 65 words of svbrdf_rendering_loss_workspace_bytes plus B S 9 accumulator words, under the same contract:
+ * zeroed once by the caller, left zeroed by every completed call (a NaN report included).  Error codes before any launch
+ * as the exposure entries'; S <= 425 (the per-workgroup sums live in LDS).  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect
+ * the three by symbol presence. */
+SVBRDF_API size_t svbrdf_photo_scene_grad_workspace_bytes(int B, int S, int H, int W);
+SVBRDF_API int svbrdf_photo_loss_scene_grad_fwd_bwd(const float *input, const float *photos, const float *weights,
+                                                    int weight_planes, const float *scenes, const float *xrow, float eps,
+                                                    float *loss_out, float *grad_input, float *grad_scenes,
+                                                    void *workspace, size_t workspace_bytes, int B, int S, int H, int W,
+                                                    void *stream);
+SVBRDF_API int svbrdf_head_photo_loss_scene_grad_fwd_bwd(const float *encoded9, const float *photos, const float *weights,
+                                                         int weight_planes, const float *scenes, const float *xrow,
+                                                         float eps, float *loss_out, float *grad_encoded9,
+                                                         float *grad_scenes, void *workspace, size_t workspace_bytes,
+                                                         int B, int S, int H, int W, void *stream);
 
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd

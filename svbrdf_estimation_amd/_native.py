@@ -46,6 +46,8 @@ _LOSS = [_fp] * 4 + [_float] + [_fp] * 3 + [_size] + _DIMS            # input, o
 _LOSS_W = [_fp] * 3 + [_int] + [_fp] * 2 + [_float] + [_fp] * 3 + [_size] + _DIMS   # input, photos, weights, planes, scenes, ...
 # input, photos, weights, planes, exposure, scenes, xrow, eps, loss, grad, grad_exposure, ws, bytes
 _LOSS_X = [_fp] * 3 + [_int] + [_fp] * 3 + [_float] + [_fp] * 4 + [_size] + _DIMS
+# input, photos, weights, planes, scenes, xrow, eps, loss, grad, grad_scenes, ws, bytes
+_LOSS_SG = [_fp] * 3 + [_int] + [_fp] * 2 + [_float] + [_fp] * 4 + [_size] + _DIMS
 _LOSS_L1 = [_fp] * 4 + [_float] * 3 + [_fp] * 3 + [_size] + _DIMS     # ... eps, l1_weight, eps_l1 ...
 _INPUTS = [_fp] * 3 + [_u64] * 2 + [_fp] * 2 + _DIMS
 # name -> (restype, argtypes) of every SVBRDF_API function of include/svbrdf_hip.h, applied once in _load();
@@ -78,6 +80,9 @@ SIGNATURES = {
     "svbrdf_photo_exposure_workspace_bytes": (_size, [_int] * 4),
     "svbrdf_photo_loss_exposure_fwd_bwd": (_int, _LOSS_X),
     "svbrdf_head_photo_loss_exposure_fwd_bwd": (_int, _LOSS_X),
+    "svbrdf_photo_scene_grad_workspace_bytes": (_size, [_int] * 4),
+    "svbrdf_photo_loss_scene_grad_fwd_bwd": (_int, _LOSS_SG),
+    "svbrdf_head_photo_loss_scene_grad_fwd_bwd": (_int, _LOSS_SG),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
     "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
     "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
@@ -112,7 +117,7 @@ def _load():
             raise NativeLibraryError("cannot load %s: %s" % (_SO, e))
         for name, (restype, argtypes) in SIGNATURES.items():
             if not hasattr(lib, name):
-                if "photo_loss" in name or "photo_exposure" in name:    # joined ABI version 8 without a bump: an older build lacks them
+                if "photo_loss" in name or "photo_exposure" in name or "photo_scene_grad" in name:    # joined ABI version 8 without a bump: an older build lacks them
                     raise NativeLibraryError("%s lacks %s (a build of ABI version 8 older than this binding) -- rebuild"
                                              % (_SO, name))
                 raise NativeLibraryError("%s does not export %s -- rebuild" % (_SO, name))
@@ -500,7 +505,7 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
 
 
 def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weights=None, exposure=None,
-               want_exposure_grad=False):
+               want_exposure_grad=False, want_scene_grad=False):
     """Fused photo loss (svbrdf_photo_loss_fwd_bwd*): mean |log(render(scenes[b,s], input[b]) + eps) - log(photos[b,s] + eps)|
     and d loss/d input in ONE launch.  input [B,12,H,W] and photos [B,S,3,H,W] device fp32; scenes [B,S,9] fp32 on the
     maps' device, or on the HOST (at most host_scenes_max_rows() rows ride in the launch's argument block, a larger table
@@ -514,7 +519,15 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
     light colour of its scene row -- the svbrdf_*photo_loss_exposure_fwd_bwd entries, still ONE launch, with or without
     ``weights``.  They are forward + adjoint with the table in device memory: a host table is uploaded, and ``want_grad``
     only decides whether the map gradient is returned.  Returns (loss, grad or None, grad_exposure [B,S,3] or None --
-    ``want_exposure_grad``).  A gain that is NaN, infinite or <= 0 gives a NaN loss and an all-NaN grad_exposure."""
+    ``want_exposure_grad``).  A gain that is NaN, infinite or <= 0 gives a NaN loss and an all-NaN grad_exposure.
+
+    ``want_scene_grad=True`` (without ``exposure``: a gain is applied to the table in front of the call): the
+    svbrdf_*photo_loss_scene_grad_fwd_bwd entries, still ONE launch, with or without ``weights``, forward + adjoint with the
+    table in device memory like the exposure entries.  Returns (loss, grad or None, grad_scenes [B,S,9]): d loss/d scenes,
+    camera xyz | light xyz | light rgb.  Loss and map gradient equal the entries' without it bit for bit.  A colour that is
+    NaN, infinite or <= 0 gives a NaN loss; a NaN loss comes with an all-NaN grad_scenes."""
+    if want_scene_grad and exposure is not None:
+        raise ValueError("want_scene_grad takes no exposure: multiply the table's colour columns by the gains instead")
     _require_device_f32(input, "input")
     _require_device_f32(photos, "photos")
     if photos.device != input.device:
@@ -551,6 +564,15 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
             photos.contiguous(), scenes, (ctypes.c_float(eps),), True, B, S, H, W, extra + (exposure.data_ptr(),),
             (grad_exposure.data_ptr() if want_exposure_grad else None,), "svbrdf_photo_exposure_workspace_bytes")
         return loss, (grad if want_grad else None), grad_exposure
+    if want_scene_grad:
+        if on_host:
+            scenes = upload_scene_table(scenes, input.device)
+        grad_scenes = torch.empty_like(scenes)
+        loss, grad = _fused_loss_call(
+            ("svbrdf_head_photo_loss" if head else "svbrdf_photo_loss") + "_scene_grad_fwd_bwd", input.contiguous(),
+            photos.contiguous(), scenes, (ctypes.c_float(eps),), True, B, S, H, W, extra or (None, 0),
+            (grad_scenes.data_ptr(),), "svbrdf_photo_scene_grad_workspace_bytes")
+        return loss, (grad if want_grad else None), grad_scenes
     entry = stem + "_fwd_bwd" + ("_host_scenes" if on_host else "")
     return _fused_loss_call(entry, input.contiguous(), photos.contiguous(), scenes, (ctypes.c_float(eps),), want_grad,
                             B, S, H, W, extra)

@@ -7,8 +7,8 @@
 // Every captured photograph has an unknown radiometric scale (flash power, shutter, ISO, white balance); without a
 // gradient towards it a wrong flash intensity is absorbed into the albedos.  The gain enters as ONE float32 multiply of the
 // scene row's colour in front of the falloff, so the loss and the map gradient are bit for bit those of the existing
-// kernels on a table whose colour columns were multiplied by e in float32 (all-ones e: the existing results).  There is no
-// gradient towards light or camera positions.
+// kernels on a table whose colour columns were multiplied by e in float32 (all-ones e: the existing results).  The gradient
+// towards light and camera positions is svbrdf_photo_pose.hip's.
 //
 // Four kernels, {maps, head} x {unweighted, weighted}, forward + adjoint, scene table in device memory.  They are
 // svbrdf_photo_loss.hip's flow -- its per-render device functions with EXPO set, included below without its kernels,

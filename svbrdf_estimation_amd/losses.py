@@ -290,11 +290,18 @@ class _FusedPhotoLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, photos, scenes, eps, head, weights=None, exposure=None):
         need_in = ctx.needs_input_grad[0]
+        need_s = ctx.needs_input_grad[2]            # the scene table's gradient: a device table, no exposure (_forward)
         need_e = exposure is not None and ctx.needs_input_grad[6]
         # (for backward(create_graph=True) only: references, no copies)
-        ctx.save_for_backward(input, photos, *(() if exposure is None else (exposure,)))
-        ctx.second_order = (scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head), weights)
-        if exposure is None:
+        ctx.save_for_backward(input, photos, *(() if exposure is None else (exposure,)), *((scenes,) if need_s else ()))
+        ctx.second_order = (None if need_s else scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head),
+                            weights)
+        if need_s:
+            # the scene-gradient kernels: map and table gradient out of the ONE launch
+            loss, grad, grad_s = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights,
+                                                    want_scene_grad=True)
+            ctx.grads = (grad, None, grad_s)
+        elif exposure is None:
             loss, grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights)
             ctx.grads = None if grad is None else (grad,)
         else:
@@ -309,22 +316,27 @@ class _FusedPhotoLoss(torch.autograd.Function):
         if torch.is_grad_enabled():
             # backward(create_graph=True): the kernel's gradient is a constant to autograd; differentiate the composed
             # definition instead (same scenes), in float64 like the other fused losses do
-            input, photos, *exposure = ctx.saved_tensors
             scenes, eps, head, weights = ctx.second_order
-            need = [ctx.needs_input_grad[0], bool(exposure) and ctx.needs_input_grad[6]]
+            input, photos, *rest = ctx.saved_tensors
+            table = rest.pop() if scenes is None else None
+            exposure = rest
+            need = [ctx.needs_input_grad[0], bool(exposure) and ctx.needs_input_grad[6], table is not None]
             with torch.enable_grad():
                 x = input.to(torch.float64)
                 e = exposure[0].to(torch.float64) if exposure else None
-                loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes, eps, weights, e)
-                wanted = [t for t, n in zip((input, exposure[0] if exposure else None), need) if n]
+                loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes if table is None else table, eps,
+                                           weights, e)
+                wanted = [t for t, n in zip((input, exposure[0] if exposure else None, table), need) if n]
                 grads = list(torch.autograd.grad(loss, wanted, grad_loss.to(torch.float64).reshape(()), create_graph=True))
             g_in = grads.pop(0).to(input.dtype) if need[0] else None
             g_e = grads.pop(0).to(exposure[0].dtype) if need[1] else None
-            return g_in, None, None, None, None, None, g_e
+            g_s = grads.pop(0) if need[2] else None
+            return g_in, None, g_s, None, None, None, g_e
         grads = _hand_over_gradients(ctx, grad_loss, "Trying to backward through the fused photo loss a second time: its "
                                      "gradient buffer was handed to the first backward.  Specify retain_graph=True for "
                                      "the first one.")
-        return grads[0], None, None, None, None, None, (grads[1] if len(grads) > 1 else None)
+        return (grads[0], None, (grads[2] if len(grads) > 2 else None), None, None, None,
+                (grads[1] if len(grads) > 1 else None))
 
 
 class _PhotoLossTensor(_UnitGradientLoss):
@@ -375,8 +387,12 @@ def composed_photo_loss(input, photos, scenes, eps, weights=None, exposure=None)
     maps take and what ``backward(create_graph=True)`` of the fused loss differentiates.  ``scenes`` [B,S,9] float32.
     ``weights`` ([B,S,H,W] or [B,1,H,W], or None): the weighted definition, ``weighted_log_l1``.  ``exposure`` (broadcastable
     to [B,S,3], or None): the per-photo gain, ``rendered * exposure[..., None, None]`` -- the rendering is linear in the
-    light colour the fused kernels scale instead."""
-    rendered = renderers._RenderFunction.apply(input, scenes)
+    light colour the fused kernels scale instead.  A table that requires grad takes ``renderers.render_table``, the same
+    render in stock torch ops, differentiable in the table as well; any other table takes K1 / K2 as it always did."""
+    if scenes.requires_grad and torch.is_grad_enabled():
+        rendered = renderers.render_table(input, scenes.to(input.device))
+    else:
+        rendered = renderers._RenderFunction.apply(input, scenes)
     if exposure is not None:
         rendered = rendered * exposure[..., None, None]       # (a float64 exposure promotes, as torch ops do)
     if weights is not None:
@@ -488,7 +504,9 @@ class _PhotoLossModule(nn.Module):
         the path without exposure, untouched.  With an exposure the fused path is the exposure kernel (loss and both
         gradients in one launch) when the input or the exposure requires grad; a pure evaluation multiplies the table's
         colour columns by the exposure with one torch op and runs the forward-only kernel of the loss without exposure,
-        which computes the same loss bit for bit (there is no forward-only exposure kernel: not on the hot path)."""
+        which computes the same loss bit for bit (there is no forward-only exposure kernel: not on the hot path).  A float32
+        ``[B,S,9]`` scene table that requires grad takes the scene-gradient kernel (csrc/svbrdf_photo_pose.hip): loss, map
+        gradient and d loss/d table in one launch; a table that does not takes exactly the paths above."""
         photos = PhotoLoss._check(x, photos, channels=9 if head else 12)
         weights = _check_weights(weights, x, photos)
         exposure = _check_exposure(exposure, x, photos)
@@ -505,7 +523,15 @@ class _PhotoLossModule(nn.Module):
                     return self._forward_decoded(x.to(torch.float64), photos, table, weights, exposure)   # promoted in front of the decode
                 loss = composed_photo_loss(x.to(torch.float64), photos, table.to(x.device), self.eps, weights, exposure)  # float64 K1 / K2
             else:
-                if exposure is not None and not (torch.is_grad_enabled() and (x.requires_grad or exposure.requires_grad)):
+                if table.requires_grad and torch.is_grad_enabled():
+                    # the scene-gradient kernel takes a device table and no exposure: the gains multiply the colour columns
+                    # in front of it (the exposure kernels' one float32 multiply), and autograd chains the table's
+                    # gradient back to them and through the copy of a host table
+                    table = table.to(x.device)
+                    if exposure is not None:
+                        table = torch.cat((table[..., :6], table[..., 6:] * exposure), dim=-1)
+                        exposure = None
+                elif exposure is not None and not (torch.is_grad_enabled() and (x.requires_grad or exposure.requires_grad)):
                     table = table.to(x.device)
                     table = torch.cat((table[..., :6], table[..., 6:] * exposure.detach()), dim=-1)
                     exposure = None
@@ -522,7 +548,8 @@ class PhotoLoss(_PhotoLossModule):
 
     -- fitting maps to captured or synthesised photos, self-supervised training on the input photos themselves.
     ``forward(input [B,12,H,W], photos [B,S,3,H,W] or [B,3,H,W] (S = 1), scenes)`` returns a 0-dim tensor, differentiable
-    w.r.t. ``input`` only.  ``scenes``: the light / view of every photo, a ``[B,S,9]`` float32 tensor (host or device;
+    w.r.t. ``input``, w.r.t. ``exposure`` and w.r.t. ``scenes`` when that is a tensor (both below); never w.r.t. the photos
+    or the weights.  ``scenes``: the light / view of every photo, a ``[B,S,9]`` float32 tensor (host or device;
     camera xyz | light xyz | light rgb) or a nested list ``scenes[b][s]`` of ``environment.Scene``-like objects.
 
     With this package's ``LocalRenderer`` and float32 maps on a ROCm device it is ONE fused HIP kernel (forward and the
@@ -549,7 +576,16 @@ class PhotoLoss(_PhotoLossModule):
     the maps (in log space: they must stay positive -- a gain that is NaN, infinite or <= 0 gives a NaN loss).  Loss and
     map gradient equal, bit for bit, those of a scene table whose colour columns were multiplied by the gains in float32.
     float64 on any side, a plugin renderer and ``backward(create_graph=True)`` take the composed definition,
-    ``rendered * exposure[..., None, None]``.  There is no gradient towards light or camera positions."""
+    ``rendered * exposure[..., None, None]``.
+
+    ``scenes`` as a float32 ``[B,S,9]`` tensor that requires grad: the camera and light positions (and the light colour) of
+    every photo are fitted too.  With this package's ``LocalRenderer`` the loss, ``d loss/d input`` and ``d loss/d scenes``
+    come out of ONE launch (csrc/svbrdf_photo_pose.hip); loss and map gradient equal, bit for bit, those of the same table
+    without the gradient.  The table's gradient follows PyTorch's sub-gradient conventions of the composed definition
+    (``renderers.render_table``, which float64, ``backward(create_graph=True)`` and a table on the host side of a double
+    input take).  With ``exposure=`` as well the gains multiply the colour columns in front of the kernel and get their
+    gradient by the chain rule.  A colour that is NaN, infinite or <= 0 gives a NaN loss and an all-NaN table gradient.
+    Scene OBJECTS and a plugin renderer have no gradient towards light or camera positions."""
 
     @staticmethod
     def _check(input, photos, channels=12):
@@ -662,13 +698,18 @@ class HeadPhotoLoss(_PhotoLossModule):
     """``PhotoLoss(renderer, eps)(decode_head(encoded9), photos, scenes)`` in one kernel: what training or fine-tuning the
     network against photographs needs.  ``forward(encoded9 [B,9,H,W], photos [B,S,3,H,W] or [B,3,H,W] (S = 1), scenes)``
     with ``encoded9`` the generator's output after tanh (any finite value: no clamp of its own) and photos / scenes as
-    ``PhotoLoss.forward`` takes them; a 0-dim tensor, differentiable w.r.t. ``encoded9`` only.
+    ``PhotoLoss.forward`` takes them; a 0-dim tensor, differentiable w.r.t. ``encoded9``, w.r.t.
+    ``exposure`` and w.r.t. a ``[B,S,9]`` ``scenes`` tensor that requires grad, as ``PhotoLoss`` documents both; never w.r.t.
+    the photos or the weights.
 
     With this package's ``LocalRenderer`` and float32 tensors on a ROCm device the head decode, the renderings, the loss
     and the gradient w.r.t. the NINE encoded channels are ONE fused HIP kernel (csrc/svbrdf_photo_loss.hip: 9 planes in,
     9 out, no 12-channel map tensor, none of the head's elementwise launches).  Any other renderer object, float64 on
     either side and ``backward(create_graph=True)`` take the composed definition above, which is also the specification
-    of the fused path.  ``weights`` and ``normalize``: per-pixel confidence, exactly as ``PhotoLoss`` documents them."""
+    of the fused path.  ``weights`` and ``normalize``: per-pixel confidence, exactly as ``PhotoLoss`` documents them.  A
+    float32 ``[B,S,9]`` table that requires grad gets ``d loss/d scenes`` (camera, light, colour) from the same ONE launch
+    (csrc/svbrdf_photo_pose.hip), loss and 9-channel gradient unchanged bit for bit; scene OBJECTS and a plugin renderer
+    have no gradient towards light or camera positions."""
 
     def forward(self, encoded9, photos, scenes, weights=None, exposure=None):
         return self._forward(encoded9, photos, scenes, weights, head=True, exposure=exposure)

@@ -17,6 +17,7 @@ K2 (analytic backward, forward recomputed in registers) of csrc/svbrdf_kernels.h
 Extension (not in the reference): ``render_many(scene_table, svbrdf)`` renders S scenes per
 map in one launch, reading the maps once.
 """
+import math
 import threading
 
 import torch
@@ -100,6 +101,60 @@ def differentiable_render_backward(maps, scenes, grad_out):
     grad = _RenderBackwardF64.apply(maps.to(torch.float64), grad_out.reshape(table.shape[0], table.shape[1], 3, *maps.shape[-2:])
                                     .to(torch.float64), table)
     return grad.to(maps.dtype)
+
+
+def render_table(maps, table):
+    """The render of a whole scene table in STOCK TORCH OPS, differentiable in the maps AND in the table: the reference's
+    renderers.py:67-104, one op per arithmetic step, for ``maps`` [B,12,H,W] and ``table`` [B,S,9] (camera xyz | light xyz |
+    light rgb) -> [B,S,3,H,W] in the promoted dtype of the two.  What the composed photo loss differentiates when the
+    table requires grad (float64 on any side, ``backward(create_graph=True)``), and the specification of the table
+    gradient of the fused kernels (csrc/svbrdf_photo_pose.hip), with autograd's sub-gradient conventions: ``clamp(min=m)``
+    passes the gradient iff ``x >= m``.  Slow on purpose -- some forty small launches; K1 / K2 stay the path of a table
+    that needs no gradient.  The pixel coordinates are the float32 values the kernels use (``_native.make_xrow_host``);
+    pi and the clamp are python floats as in the reference, so float64 tensors take them as doubles."""
+    if maps.dim() != 4 or maps.shape[1] != 12 or maps.shape[-1] != maps.shape[-2]:
+        raise ValueError("maps must be [B,12,H,W] with H == W, got %s" % (tuple(maps.shape),))
+    if table.dim() != 3 or table.shape[0] != maps.shape[0] or table.shape[2] != 9:
+        raise ValueError("table must be [B,S,9], got %s for B=%d" % (tuple(table.shape), maps.shape[0]))
+    dtype = torch.promote_types(maps.dtype, table.dtype)
+    H, W = maps.shape[-2:]
+    xs = (_native.xrow(maps.device, W) if maps.is_cuda else _native.make_xrow_host(W)).to(dtype)
+    gx = xs.view(1, 1, 1, 1, W).expand(1, 1, 1, H, W)
+    pos = torch.cat((gx, -gx.transpose(3, 4), torch.zeros_like(gx)), dim=2)                 # renderers.py:73-76
+
+    def dot(a, b):
+        return (a * b).sum(dim=2, keepdim=True)
+
+    def unit(v):
+        return v / torch.sqrt(dot(v, v))
+
+    def clamp_dot(a, b):
+        return torch.clamp(dot(a, b), min=0.001)
+
+    def smith_g1(alpha_sq, cos_sq):
+        return 2.0 / (1 + torch.sqrt(1 + alpha_sq * (1.0 - cos_sq) / cos_sq))
+
+    rows = table.to(dtype)
+    cam, lgt, col = (rows[:, :, i:i + 3, None, None] for i in (0, 3, 6))                    # [B,S,3,1,1]
+    n, kd, rough, ks0 = torch.split(maps.to(dtype).unsqueeze(1), (3, 3, 3, 3), dim=2)       # [B,1,3,H,W]
+    rough = torch.clamp(rough, min=0.001)
+    wo = unit(cam - pos)
+    to_light = lgt - pos
+    wi = unit(to_light)
+    half = unit((wi + wo) / 2.0)
+    n_h, v_h = clamp_dot(n, half), clamp_dot(wo, half)
+    v_n, l_n = clamp_dot(wo, n), clamp_dot(wi, n)
+    fresnel = ks0 + (1.0 - ks0) * (1.0 - v_h) ** 5
+    a2 = (rough ** 2) ** 2
+    geom = smith_g1(a2, v_n ** 2) * smith_g1(a2, l_n ** 2)
+    nh2 = n_h ** 2
+    den = torch.clamp(nh2 * (a2 + (1 - nh2) / nh2), min=0.001)
+    ggx = a2 / (math.pi * den ** 2)
+    specular = fresnel * geom * ggx / (4.0 * v_n * l_n)
+    diffuse = (1.0 - fresnel) * kd / math.pi
+    cos_l = torch.clamp(dot(wi, n), min=0.0)
+    falloff = 1.0 / torch.sqrt(dot(to_light, to_light)) ** 2
+    return ((diffuse + specular) * (col * falloff)) * cos_l
 
 
 class _HostStaging:

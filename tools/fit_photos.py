@@ -1,7 +1,7 @@
 """Fit SVBRDF maps to photographs with the fused photo loss (losses.PhotoLoss): the inverse-rendering use of the engine.
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
-                               [--fit-exposure]
+                               [--fit-exposure] [--fit-pose [--pose-lr 0.002]]
 
 Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
 each from ``synthesis.render_inputs`` (the scene table is what that call draws from torch's global generator: the same seed
@@ -12,6 +12,11 @@ gives it again).  A perturbed copy of the maps is then a leaf tensor that Adam f
 white balance: the light colour of its scene row times the gain, noise-free, clamped to [0, 1]).  The fit starts from a gain
 of 1 and fits the gains jointly with the maps, the parameter in log space (``exposure=log_e.exp()``), still one launch per
 step for the loss and both gradients; the mean |log e - log e*| is printed beside the maps' error.
+
+``--fit-pose``: the fit is GIVEN camera and light positions that are a few per cent off (a camera from a homography, a flash
+"somewhere next to the lens") and fits the six position columns of the scene table jointly with the maps -- and with the
+gains under ``--fit-exposure`` -- through the table's gradient, which comes out of the same one launch per step; the mean
+|position - truth| is printed beside the maps' error.  The positions take their own learning rate, ``--pose-lr``.
 """
 import argparse
 import os
@@ -40,6 +45,8 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--print-every", type=int, default=10)
     ap.add_argument("--fit-exposure", action="store_true", help="photographs with hidden per-photo gains, fitted with the maps")
+    ap.add_argument("--fit-pose", action="store_true", help="camera and light positions given a few per cent off, fitted with the maps")
+    ap.add_argument("--pose-lr", type=float, default=0.002)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm device"
     dev = torch.device("cuda:0")
@@ -58,15 +65,20 @@ def main():
         scaled = torch.cat((table[..., :6], table[..., 6:] * hidden), dim=-1)
         photos = _native.render_fwd(truth, scaled).clamp_(0.0, 1.0)
         log_e = torch.zeros((B, S, 3), device=dev, requires_grad=True)
+    pos, true_pos, colour = None, table[..., :6], table[..., 6:]
+    if args.fit_pose:
+        off = 1.0 + 0.06 * (torch.from_numpy(synth.uniform01(args.seed + 3000, (B, S, 6))).to(dev) - 0.5)
+        pos = (true_pos * off).requires_grad_(True)                          # every coordinate up to 3 % off
     start = truth.clone()
     jitter = torch.from_numpy(synth.uniform01(args.seed + 1000, (B, 9, H, H))).to(dev) - 0.5
     start[:, 3:] = (start[:, 3:] + 0.3 * jitter).clamp_(0.02, 0.98)        # diffuse, roughness, specular off by up to 0.15
     x = start.clone().requires_grad_(True)
     fn = losses.PhotoLoss(renderers.LocalRenderer())
-    opt = torch.optim.Adam([x] if log_e is None else [x, log_e], lr=args.lr)
-    print("fitting %d x [12,%d,%d] maps to %d photographs each (%s%s), Adam lr %g" % (
+    groups = [{"params": [x] if log_e is None else [x, log_e]}] + ([] if pos is None else [{"params": [pos], "lr": args.pose_lr}])
+    opt = torch.optim.Adam(groups, lr=args.lr)
+    print("fitting %d x [12,%d,%d] maps to %d photographs each (%s%s%s), Adam lr %g" % (
         B, H, H, S, "sensor noise" if args.noise else "noise-free", ", hidden gains fitted too" if args.fit_exposure else "",
-        args.lr))
+        ", positions fitted too (lr %g)" % args.pose_lr if args.fit_pose else "", args.lr))
     t_last, step_ms = None, []
     for step in range(args.steps):
         if step % args.print_every == 0:
@@ -76,7 +88,8 @@ def main():
                 step_ms.append(1e3 * (now - t_last) / args.print_every)
             t_last = now
         opt.zero_grad(set_to_none=True)
-        loss = fn(x, photos, table) if log_e is None else fn(x, photos, table, None, log_e.exp())
+        scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
+        loss = fn(x, photos, scenes) if log_e is None else fn(x, photos, scenes, None, log_e.exp())
         loss.backward()
         opt.step()
         with torch.no_grad():
@@ -84,6 +97,8 @@ def main():
         if step % args.print_every == 0 or step == args.steps - 1:
             err = (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
             gains = "" if log_e is None else "  mean |log e - log e*| %.5f" % (log_e.detach() - hidden.log()).abs().mean().item()
+            if pos is not None:
+                gains += "  mean |position - truth| %.5f" % (pos.detach() - true_pos).abs().mean().item()
             print("step %4d  loss %.6f  mean |d,r,s - truth| %.5f%s%s" % (
                 step, loss.item(), err, gains, "  %.3f ms/step" % step_ms[-1] if step_ms else ""))
     if step_ms:
