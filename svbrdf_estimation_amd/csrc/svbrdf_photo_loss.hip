@@ -111,6 +111,23 @@ __device__ __forceinline__ int dpp_add(int v)
     return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false);
 }
 
+// The four steps of a wave sum that stay inside a row of 16 lanes, N interleaved chains: fixed lanes, fixed order, so
+// the sums are the same bits in every launch; every lane then holds its row's N sums.  What crosses the rows is the
+// caller's (expo_collect: integers, pose_collect: floats).  Every lane of the wave must be here: DPP does not read a
+// disabled lane.
+template <int N>
+__device__ __forceinline__ void dpp_row_sums(const float v[N], float r[N])
+{
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = dpp_add<0xb1>(v[k]);         // quad_perm [1,0,3,2]
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x4e>(r[k]);         // quad_perm [2,3,0,1]
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x141>(r[k]);        // row_half_mirror
+#pragma unroll
+    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x140>(r[k]);        // row_mirror
+}
+
 __device__ __forceinline__ float expo_unit(const ExpoLoop &xl) { return xl.live ? kExpoFixedScale : 0.0f; }
 
 // The three q of render s (in units of 2^-24: the lane's `unit` is folded into them), summed over the wave -- four float
@@ -130,14 +147,7 @@ __device__ __forceinline__ void expo_collect(const ExpoLoop &xl, int s, const fl
     float r[N];
     int t[N];
     bool sane = true;
-#pragma unroll
-    for (int k = 0; k < N; ++k) r[k] = dpp_add<0xb1>(q[k]);         // quad_perm [1,0,3,2]
-#pragma unroll
-    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x4e>(r[k]);         // quad_perm [2,3,0,1]
-#pragma unroll
-    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x141>(r[k]);        // row_half_mirror
-#pragma unroll
-    for (int k = 0; k < N; ++k) r[k] = dpp_add<0x140>(r[k]);        // row_mirror: every lane holds its row's sum
+    dpp_row_sums<N>(q, r);
 #pragma unroll
     for (int k = 0; k < N; ++k) sane &= fabsf(r[k]) <= kExpoRowLimit;     // per channel, as the integer sums are; false for NaN
     if (!sane) lsum = __builtin_nanf("");
@@ -150,18 +160,70 @@ __device__ __forceinline__ void expo_collect(const ExpoLoop &xl, int s, const fl
     for (int k = 0; k < N; ++k) expo_lds()[dst + K0 + k] = t[k];
 }
 
+// POSE (the scene-gradient kernels of svbrdf_photo_pose.hip; no kernel of this unit sets it): the render's scene row, the
+// pixel's coordinates and where the 9 values of pose_bwd go.
+struct PoseRender {
+    const float *sc;
+    float x, y;
+    float *out;
+};
+
+// The adjoint of one render from the bars of its dot products to its scene row, PyTorch's sub-gradient conventions.
+//   g_NH, g_VN: d loss / d (n.h), d (n.wo), clamp masks applied;  gl: d loss / d (n.wi), both clamps of it;
+//   g_p: d loss / d p, p = (1 - VH)^5;  Q[k] = d loss / d b[k] times (b[k] - ec): the radiance's share, which is
+//   d loss / d log colour[k] and d loss / d log falloff.
+// With s = wi + wo, h = s / |s| and VH = wo.h = |s| / 2 (unit wo, wi), the bar of s is g_NH (n - (n.h) h) / |s| + g_VH h / 2,
+// it joins the bars of wo and wi, and each goes through its normalisation: (bar - (bar.w) w) / |r|.  The falloff 1 / |rl|^2
+// adds -2 sum(Q) wi / |rl|.  -> out[0:3] d / d camera, out[3:6] d / d light, out[6:9] = Q (the finisher divides by the colour).
+// The lengths are 1-ULP rsq of the sums geometry() forms: the gradient is well conditioned in them.
+__device__ __forceinline__ void pose_bwd(const VConst &K, const PoseRender &pr, const Geom &g, const MapK &mi,
+                                         const Dots &di, float g_NH, float g_VN, float gl, float g_p, const float Q[3])
+{
+    const float *sc = pr.sc;
+    float *out = pr.out;
+    const float rcx = sc[0] - pr.x, rcy = sc[1] - pr.y, rcz = sc[2];
+    const float rlx = sc[3] - pr.x, rly = sc[4] - pr.y, rlz = sc[5];
+    const float ic = rsq_(dot3(rcx, rcy, rcz, rcx, rcy, rcz));
+    const float il = rsq_(dot3(rlx, rly, rlz, rlx, rly, rlz));
+    const float sx = g.wix + g.wox, sy = g.wiy + g.woy, sz = g.wiz + g.woz;
+    const float ss = dot3(sx, sy, sz, sx, sy, sz);
+    const float ih = rsq_(ss);
+    const float vh = 0.5f * (ss * ih);
+    const float t = 1.0f - vh, t2 = t * t;
+    float g_VH = (-5.0f * (t2 * t2)) * g_p;
+    if (!(vh >= K.tiny)) g_VH = 0.0f;
+    const float a = g_NH * ih;
+    const float c = fma_(-a, di.nh_raw, 0.5f * g_VH);       // bar of s = a n + c h
+    const float eo = g_VN + a, ei = gl + a;                 // bars of wo, wi = e n + c h
+    const float cv = c * vh;                                // h.wo = h.wi = VH
+    const float po = fma_(eo, di.vn_raw, cv);
+    const float pl = fma_(ei, di.ln_raw, cv) + 2.0f * ((Q[0] + Q[1]) + Q[2]);
+    out[0] = fma_(eo, mi.n[0], fma_(c, g.hx, -po * g.wox)) * ic;
+    out[1] = fma_(eo, mi.n[1], fma_(c, g.hy, -po * g.woy)) * ic;
+    out[2] = fma_(eo, mi.n[2], fma_(c, g.hz, -po * g.woz)) * ic;
+    out[3] = fma_(ei, mi.n[0], fma_(c, g.hx, -pl * g.wix)) * il;
+    out[4] = fma_(ei, mi.n[1], fma_(c, g.hy, -pl * g.wiy)) * il;
+    out[5] = fma_(ei, mi.n[2], fma_(c, g.hz, -pl * g.wiz)) * il;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[6 + k] = Q[k];
+}
+
 // one (pixel, scene), tied roughness: loss_pixel_scene with the target shading replaced by the photo's three values.
 // WEIGHTED: `w` is the render's checked weight and `inv_count` already carries it (w / N, folded once per render); a
 // weight of exactly 0 selects every term to exactly 0 -- whatever the photo holds, NaN included: 0 * NaN is never
 // formed -- and lg = 0 with M = 0 gives a gradient of exactly (+-)0.
 // EXPO: q[k] = -sign(lg) w (1 - ec / b[k]) `unit` as well, by loss_grad_of_b's clamp (sign(0) = 0: a zero weight gives
 // (+-)0), collected for render `s` in front of the adjoint: the three q are dead before its registers are needed.
-template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false>
+// POSE: behind the adjoint, the bars pose_bwd needs from the same registers (shade_bwd's own expressions: the compiler
+// forms them once).
+template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false, bool POSE = false>
 __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
                                                   float s10, float eps, float inv_count, float &lsum, Grad &acc,
                                                   [[maybe_unused]] float w = 1.0f,
-                                                  [[maybe_unused]] const ExpoLoop *xl = nullptr, [[maybe_unused]] int s = 0)
+                                                  [[maybe_unused]] const ExpoLoop *xl = nullptr, [[maybe_unused]] int s = 0,
+                                                  [[maybe_unused]] const PoseRender *pr = nullptr)
 {
+    static_assert(!POSE || WITH_GRAD, "the scene-gradient kernels are forward + adjoint");
     const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
     [[maybe_unused]] float q[3];
     [[maybe_unused]] const float unit = !EXPO ? 0.0f : WEIGHTED ? xl->per_weight : expo_unit(*xl);
@@ -193,21 +255,44 @@ __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g
     }
     if (EXPO) expo_collect<3, 0>(*xl, s, q, lsum);
     if (WITH_GRAD) shade_bwd<1, (DEFER & 1) != 0, (DEFER & 2) != 0, (DEFER & 4) != 0>(K, g, mi, di, li, Fi, fi, g_rad, acc);
+    if (POSE) {
+        float Q[3], g_LNp = 0.0f, g_p = 0.0f, Wg = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float gE = g_rad[k] * g.E[k];
+            const float g_f = gE * di.LNp;
+            Q[k] = g_f * fi[k];
+            g_LNp = k == 0 ? gE * fi[k] : fma_(gE, fi[k], g_LNp);
+            g_p = fma_(g_f * (li[0].GD - mi.dpi[k]), mi.oms[k], g_p);
+            const float gGD = g_f * Fi[k];
+            Wg = k == 0 ? gGD : Wg + gGD;
+        }
+        float g_VN = Wg * li[0].KV, g_LN = Wg * li[0].KL;
+        float g_NH = ((Wg * li[0].KN) * 2.0f) * di.NH;
+        if (!(di.nh_raw >= K.tiny)) g_NH = 0.0f;
+        if (!(di.vn_raw >= K.tiny)) g_VN = 0.0f;
+        if (!(di.ln_raw >= K.tiny)) g_LN = 0.0f;
+        if (!(di.ln_raw >= 0.0f)) g_LNp = 0.0f;
+        pose_bwd(K, *pr, g, mi, di, g_NH, g_VN, g_LN + g_LNp, g_p, Q);
+    }
 }
 
-// independent roughness channels: loss_pixel_scene_by_channel with the photo as the target side
-template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false>
+// independent roughness channels: loss_pixel_scene_by_channel with the photo as the target side (POSE: the bar of p and
+// the three Q beside the channels' adjoint)
+template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false, bool POSE = false>
 __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
                                                              float s10, float eps, float inv_count, float &lsum, Grad &acc,
                                                              [[maybe_unused]] float w = 1.0f,
                                                              [[maybe_unused]] const ExpoLoop *xl = nullptr,
-                                                             [[maybe_unused]] int s = 0)
+                                                             [[maybe_unused]] int s = 0,
+                                                             [[maybe_unused]] const PoseRender *pr = nullptr)
 {
     const Dots di = dots(K, g, mi);
     const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
     [[maybe_unused]] const float unit = !EXPO ? 0.0f : WEIGHTED ? xl->per_weight : expo_unit(*xl);
     const float omp = 1.0f - g.p;
     float g_LNp = 0.0f, g_VN = 0.0f, g_LN = 0.0f, sN = 0.0f;
+    [[maybe_unused]] float Q[3], g_p = 0.0f;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float bt = fma_(ph[k], s10, ec);
@@ -238,6 +323,10 @@ __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, co
             g_VN = fma_(gGD, li.KV, g_VN);
             g_LN = fma_(gGD, li.KL, g_LN);
             sN = fma_(gGD, li.KN, sN);
+            if (POSE) {
+                Q[k] = g_f * fi;
+                g_p = fma_(g_F, mi.oms[k], g_p);
+            }
         }
     }
     if (WITH_GRAD) {
@@ -250,6 +339,7 @@ __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, co
         acc.n[0] = fma_(g_NH, g.hx, fma_(g_VN, g.wox, fma_(gl, g.wix, acc.n[0])));
         acc.n[1] = fma_(g_NH, g.hy, fma_(g_VN, g.woy, fma_(gl, g.wiy, acc.n[1])));
         acc.n[2] = fma_(g_NH, g.hz, fma_(g_VN, g.woz, fma_(gl, g.wiz, acc.n[2])));
+        if (POSE) pose_bwd(K, *pr, g, mi, di, g_NH, g_VN, gl, g_p, Q);
     }
 }
 
@@ -439,6 +529,8 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
         __syncthreads();
     }
     if (active) {
+        // (the set-up of a pixel, down to the guards on x and `poison`, stands a second time in wave_pixel_setup below: a
+        // change to the loads or the guards is made in both)
         Maps in;
         Grad acc;
         [[maybe_unused]] Head head;
@@ -532,6 +624,176 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
             loss_arrive(t, fixed_scale, loss_scale, ws, loss_out);
         }
     }
+}
+
+// ---- What the kernels that also sum per-item values share (exposure_body of svbrdf_photo_exposure.hip: 3 S gains,
+// pose_body of svbrdf_photo_pose.hip: 9 S scene values).  No kernel of this unit uses any of it. ----
+
+// Where a lane of such a kernel stands.  A wave that holds at least one pixel runs WHOLE -- the lanes past the item's last
+// pixel shade that last pixel again, deselected from the loss, the sums and the stores -- so that the wave sums never read
+// a disabled lane.  A wave without pixels zeroes its row of sums and skips the pixel: that one-line loop is each body's own
+// (zeroing here, in front of an `if (wave_live)` of the body, cost k_exposure_maps_weighted a fifth spilled SGPR).
+struct WaveIndex {
+    size_t pix;         // the lane's pixel, or the item's last one
+    bool live;          // the lane's pixel exists
+    bool wave_live;     // the wave holds a pixel (wave-uniform)
+    int row;            // the wave's row of the dynamic LDS, in words: spill words that the lanes which do not hold the
+                        // wave's sums store theirs to, then its sums
+};
+[[maybe_unused]] __device__ __forceinline__ WaveIndex wave_index(size_t plane, int row_words)
+{
+    WaveIndex wi;
+    const size_t first = (size_t)blockIdx.x * kLossThreads + (threadIdx.x & ~63u);
+    wi.live = first + (threadIdx.x & 63) < plane;
+    wi.pix = wi.live ? first + (threadIdx.x & 63) : plane - 1;
+    wi.wave_live = __builtin_amdgcn_readfirstlane((int)(first < plane)) != 0;
+    wi.row = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) * row_words;
+    return wi;
+}
+
+// The set-up of a pixel: photo_loss_body<true, false, HEAD, WEIGHTED>'s statements from the plane loads to the guards on x
+// and `poison`, in its source order (the order the scheduler sees), where its comments are.  It stands TWICE: sharing this
+// function with photo_loss_body gave six of the eight head kernels of this unit other machine code (same size, other
+// bytes).  A change to the loads or the guards is made here and there.
+struct PixelSetup {
+    MapK mi;
+    Grad acc;       // zeroed
+    Head head;      // HEAD only
+    bool tied;
+    float x, y, poison;
+};
+template <bool HEAD, bool WEIGHTED>
+__device__ __forceinline__ PixelSetup wave_pixel_setup(const float *__restrict__ input, const float *__restrict__ xrow, int b,
+                                                       size_t plane, size_t pix, int W)
+{
+    PixelSetup ps;
+    Maps in;
+    [[maybe_unused]] float head_chk = 0.0f;
+    ps.poison = 0.0f;
+    if (HEAD) {
+        float e[9];
+        const PlaneBuf pb = plane_buf(input + (size_t)b * 9 * plane, 9, plane, pix);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) e[k] = plane_load(pb, k);
+        ps.head = decode_head(e, in);
+        head_chk = ((e[0] - e[0]) + (e[1] - e[1])) + (e[5] - e[5]);
+        if (WEIGHTED)
+            ps.poison = (((e[2] - e[2]) + (e[3] - e[3])) + ((e[4] - e[4]) + (e[6] - e[6]))) + ((e[7] - e[7]) + (e[8] - e[8]));
+    } else {
+        load_maps_k3(input + (size_t)b * 12 * plane, plane, pix, in);
+    }
+    zero_grad(ps.acc);
+    ps.tied = HEAD || tied_roughness(in);
+    ps.mi = prepare<true>(in);
+    float x[1];
+    if ((W & (W - 1)) == 0) {
+        const unsigned p32 = (unsigned)pix, sh = (unsigned)__builtin_ctz((unsigned)W);
+        x[0] = xrow[p32 & (unsigned)(W - 1)];
+        ps.y = -xrow[p32 >> sh];
+    } else {
+        pixel_coords<1>(xrow, pix, W, x, ps.y);
+    }
+    if (HEAD) {
+        x[0] += head_chk;
+        if (WEIGHTED) ps.poison += head_chk;
+    } else {
+        const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
+        x[0] += chk - chk;
+        if (WEIGHTED) {
+            const float ds = ((in.d[0] + in.d[1]) + (in.d[2] + in.s[0])) + (in.s[1] + in.s[2]);
+            ps.poison = (chk - chk) + (ds - ds);
+        }
+    }
+    ps.x = x[0];
+    return ps;
+}
+
+// The end of such a launch.  `workgroup_sum(i, sane)`: sum i of this workgroup from its waves' rows of LDS, as a 64-bit
+// fixed-point integer; CHECKED: it may clear `sane`, and the loss of the launch -- and with it every gradient -- is then NaN.
+// `write(i, sum, nan)`: the finisher's result i of all B n_sums from the launch's sum.
+//   * behind one barrier, n_sums lanes add the workgroup's sums to the accumulator words of the workspace (behind
+//     loss_arrive's 65) with 64-bit agent-scope RETURNING atomics and wait for their return; then the barrier of the loss
+//     reduction; then lane 0 arrives (loss_arrive).  Whoever finishes the launch therefore knows every accumulator
+//     complete: each workgroup's adds returned before its arrival was counted.
+//   * the finisher's wave 0 (told by readfirstlane of loss_arrive's answer: no LDS word, no third barrier, the other three
+//     waves have left) fetches and zeroes every accumulator with 64-bit agent-scope atomic exchanges -- 8-byte agent
+//     atomics on both sides of the hand-off, no fence; a plain load could be served by this compute unit's L1 or its
+//     die's L2.
+// Three dependent round trips (accumulator adds, slot + tail, exchanges) against two in the kernels of this unit.
+template <bool CHECKED, typename Sum, typename Write>
+__device__ __forceinline__ void photo_sums_finish(float lsum, int b, int n_sums, float fixed_scale, double loss_scale,
+                                                  unsigned long long *__restrict__ ws, float *__restrict__ loss_out,
+                                                  Sum workgroup_sum, Write write)
+{
+    constexpr int kWaves = kLossThreads / 64;
+    __shared__ float wave_part[kWaves];
+    [[maybe_unused]] __shared__ int wild;       // CHECKED: a sum was not sane
+    lsum = wave_sum(lsum);
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = lsum;
+    if (CHECKED && threadIdx.x == 0) wild = 0;
+    __syncthreads();        // the workgroup's sums stand in LDS
+    unsigned long long *__restrict__ accum = ws + (kLossSlots + 1);
+    for (int i = threadIdx.x; i < n_sums; i += kLossThreads) {
+        bool sane = true;
+        const long long sum = workgroup_sum(i, sane);
+        if (CHECKED && !sane) wild = 1;
+        const unsigned long long old = __hip_atomic_fetch_add(&accum[(size_t)b * n_sums + i], (unsigned long long)sum,
+                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // the value is asked for so that the add RETURNS: the wave waits for it here, in front of the barrier
+        asm volatile("" ::"v"((unsigned)old), "v"((unsigned)(old >> 32)));
+    }
+    __syncthreads();        // every add of this workgroup has returned
+    if (threadIdx.x >= 64) return;
+    int finished = 0;
+    if (threadIdx.x == 0) {
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) t += wave_part[w];
+        if (CHECKED && wild) t = __builtin_nanf("");
+        finished = loss_arrive(t, fixed_scale, loss_scale, ws, loss_out);
+    }
+    finished = __builtin_amdgcn_readfirstlane(finished);
+    if (finished == 0) return;
+    // the finisher: every workgroup's adds returned before it arrived, and its arrival before the finisher's own returned
+    const int n_all = (int)gridDim.y * n_sums;
+    for (int i = threadIdx.x; i < n_all; i += 64) {
+        const unsigned long long sum = __hip_atomic_exchange(&accum[i], 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        write(i, (long long)sum, finished == 2);
+    }
+}
+
+// Host side: workspace_bytes of an entry with `per_scene` sums per (item, scene), and the argument checks of its
+// launcher (all before the launch, one order, one set of codes) with plan_loss's grid and fixed-point scale.  `required`
+// holds grad_scenes; grad_exposure may be null and is `optional_out`.  -> p->lds_bytes: the [waves][spill + per_scene S]
+// rows; *units = N 2^24, what one unit of the accumulators is the reciprocal of.
+[[maybe_unused]] size_t sums_workspace_bytes(int per_scene, int B, int S, int H, int W)
+{
+    const size_t sums = (B > 0 && S > 0) ? (size_t)B * (size_t)S * per_scene : 0;
+    return svbrdf_rendering_loss_workspace_bytes(B, S, H, W) + sums * sizeof(unsigned long long);
+}
+[[maybe_unused]] int plan_sums(const char *who, std::initializer_list<const void *> required, const float *weights,
+                               int weight_planes, const float *optional_out, float eps, const float *grad_input,
+                               void *workspace, size_t workspace_bytes, int per_scene, int spill, int B, int S, int H, int W,
+                               LossPlan *p, double *units)
+{
+    constexpr size_t kRowBytes = kLossThreads / 64 * sizeof(float), kLdsMax = 60 * 1024;
+    char text[200], lds_text[80];
+    const auto bad = [&](int code, const char *what) {
+        std::snprintf(text, sizeof(text), "%s: %s", who, what);
+        return fail(code, text);
+    };
+    if (!grad_input) return fail(SVBRDF_ERR_NULL, who);      // forward + adjoint only
+    if (int e = plan_loss(who, false, required, grad_input, workspace, workspace_bytes, "eps", eps, 0.0f, B, S, H, W, p)) return e;
+    if (!aligned(weights, 4) || !aligned(optional_out, 4)) return bad(SVBRDF_ERR_ALIGN, "pointers must be 4-byte aligned");
+    if (weights ? (weight_planes != 1 && weight_planes != S) : weight_planes != 0)
+        return bad(SVBRDF_ERR_DIMS, "weight_planes must be 1 (one plane per item) or S (one per photo) with weights, 0 without");
+    if (workspace_bytes < sums_workspace_bytes(per_scene, B, S, H, W)) return bad(SVBRDF_ERR_WORKSPACE, "workspace too small");
+    p->lds_bytes = kRowBytes * (spill + (size_t)S * per_scene);
+    std::snprintf(lds_text, sizeof(lds_text), "too many scenes per item for the LDS sums (max %d)",
+                  (int)((kLdsMax / kRowBytes - spill) / per_scene));
+    if (p->lds_bytes > kLdsMax) return bad(SVBRDF_ERR_DIMS, lds_text);
+    *units = (double)B * S * 3.0 * (double)H * W * (double)kExpoFixedScale;
+    return 0;
 }
 
 #ifndef SVBRDF_PHOTO_LOSS_MIN_WAVES

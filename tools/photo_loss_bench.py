@@ -1,6 +1,6 @@
 """The fused photo loss against K3 and against the composed form, one process, one box (profiles/r09_photo_loss.txt).
 
-    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...] [--head] [--weights {none,shared,per-photo}] [--pose]
+    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...] [--head] [--weights {none,shared,per-photo}] [--pose] [--exposure]
 
 At the configuration-2 shape (B = 8, 256 x 256, S = 9, scene table by value, six batches rotating beyond the 256 MB
 Infinity Cache, as bench.py does) it prints the event-timed median per launch of
@@ -29,6 +29,11 @@ tests/test_gpu_weighted_photo_loss.py's speed test).  `none` (default) is the un
 (svbrdf_photo_loss_scene_grad_fwd_bwd, per-photo weights, device table), the weighted kernel on the same table and the
 composed torch-op definition with the table as a leaf, forward + backward (tests/pose_photo_checks.py::
 measure_pose_photo_loss, the method of tests/test_gpu_pose_photo_loss.py's speed test).
+
+--exposure: the exposure leg instead -- the photo loss with a per-photo exposure and its gradient
+(svbrdf_photo_loss_exposure_fwd_bwd, per-photo weights, device table), the weighted kernel on the pre-scaled table and the
+composed definition with an exposure leaf (tests/exposure_photo_checks.py::measure_exposure_photo_loss, the method of
+tests/test_gpu_exposure_photo_loss.py's speed test).
 
 --variants: other builds of the library (tools/build_variant.sh, e.g. the photo-loss unit compiled with another of the
 Makefile's scheduler sets), each measured in a child process of its own on this box, interleaved with the shipped build.
@@ -91,7 +96,7 @@ def measure_composed(dev, native, sets=6, n=30, rounds=3):
     return medians["composed_us"]
 
 
-def child(head=False, weights="none", pose=False):
+def child(head=False, weights="none", pose=False, exposure=False):
     import torch
     from svbrdf_estimation_amd import _native
     import photo_checks
@@ -99,6 +104,9 @@ def child(head=False, weights="none", pose=False):
     if pose:
         import pose_photo_checks
         res = pose_photo_checks.measure_pose_photo_loss(dev, _native)
+    elif exposure:
+        import exposure_photo_checks
+        res = exposure_photo_checks.measure_exposure_photo_loss(dev, _native)
     elif weights != "none":
         import weighted_photo_checks
         res = weighted_photo_checks.measure_weighted_photo_loss(dev, _native, weights)
@@ -122,12 +130,14 @@ def main():
                     help="the weighted leg: weighted photo loss, unweighted kernel, unfused weighted composition")
     ap.add_argument("--pose", action="store_true",
                     help="the scene-gradient leg: photo loss with grad_scenes, weighted kernel, composed torch-op definition")
+    ap.add_argument("--exposure", action="store_true",
+                    help="the exposure leg: photo loss with grad_exposure, weighted kernel, composed definition with an exposure leaf")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.head + (args.weights != "none") + args.pose > 1:
-        ap.error("--head, --weights and --pose measure different legs: give one of them")
+    if args.head + (args.weights != "none") + args.pose + args.exposure > 1:
+        ap.error("--head, --weights, --pose and --exposure measure different legs: give one of them")
     if args.child:
-        return child(args.head, args.weights, args.pose)
+        return child(args.head, args.weights, args.pose, args.exposure)
     builds = [("shipped", None)] + [tuple(v.split("=", 1)) for v in args.variants]
     rows = []
     for p in range(args.passes):
@@ -136,7 +146,8 @@ def main():
             if lib:
                 env["SVBRDF_HIP_LIB"] = os.path.abspath(lib)
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--weights", args.weights]
-                                 + (["--head"] if args.head else []) + (["--pose"] if args.pose else []), env=env, text=True, timeout=300,
+                                 + (["--head"] if args.head else []) + (["--pose"] if args.pose else [])
+                                 + (["--exposure"] if args.exposure else []), env=env, text=True, timeout=300,
                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
             line = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")]
             if out.returncode != 0 or not line:
@@ -144,14 +155,16 @@ def main():
                 raise SystemExit("measurement of build %r failed (exit status %s): nothing more is started" % (tag, out.returncode))
             rows.append((tag, p, json.loads(line[0][7:])))
     B, H, S = 8, 256, 9
-    if args.pose:
-        lines = ["# tools/photo_loss_bench.py --pose on %s; B = %d, %d x %d, S = %d, per-photo weights, device table, %d rotating batches" % (
-            rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]), "# medians of event-timed steps (us per step)"]
+    if args.pose or args.exposure:
+        key, what, leaf = ("pose_us", "grad_scenes", "a table") if args.pose else ("exposure_us", "grad_exposure", "an exposure")
+        lines = ["# tools/photo_loss_bench.py --%s on %s; B = %d, %d x %d, S = %d, per-photo weights, device table, %d rotating batches" % (
+            "pose" if args.pose else "exposure", rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
+            "# medians of event-timed steps (us per step)"]
         for tag, p, r in rows:
-            lines.append("%-16s pass %d: photo loss with grad_scenes %7.2f  weighted photo loss on the same table %7.2f (ratio %.3f)  "
-                         "composed torch-op definition with a table leaf fwd + bwd %8.2f (%.1fx)   rounds %s" % (
-                             tag, p, r["pose_us"], r["weighted_us"], r["pose_us"] / r["weighted_us"], r["composition_us"],
-                             r["composition_us"] / r["pose_us"], r["rounds"]))
+            lines.append("%-16s pass %d: photo loss with %s %7.2f  weighted photo loss on the same table %7.2f (ratio %.3f)  "
+                         "composed torch-op definition with %s leaf fwd + bwd %8.2f (%.1fx)   rounds %s" % (
+                             tag, p, what, r[key], r["weighted_us"], r[key] / r["weighted_us"], leaf, r["composition_us"],
+                             r["composition_us"] / r[key], r["rounds"]))
     elif args.weights != "none":
         P = rows[0][2]["planes"]
         lines = ["# tools/photo_loss_bench.py --weights %s on %s; B = %d, %d x %d, S = %d, scene table by value, %d rotating batches" % (
