@@ -337,6 +337,34 @@ SVBRDF_API int svbrdf_head_photo_loss_scene_grad_fwd_bwd(const float *encoded9, 
                                                          float *grad_scenes, void *workspace, size_t workspace_bytes,
                                                          int B, int S, int H, int W, void *stream);
 
+/* One STEP of a fit of the maps to photographs, ONE launch: the (weighted) photo loss at the maps as they are, its gradient
+ * and the Adam update of the maps with it -- what PhotoLoss, backward(), torch.optim.Adam.step() and clamp_ do in several
+ * passes over the same tensors.  `maps`, `exp_avg`, `exp_avg_sq` [B,12,H,W] are updated IN PLACE; with w, p' and N as in
+ * the weighted entries (w = 1, p' = photo when `weights` is NULL, and then weight_planes must be 0) and g = d loss / d maps,
+ * per element, every operation an individually rounded float32 one (no fused multiply-add, IEEE division and square root):
+ *   m' = (beta1 m) + (c1 g)
+ *   v' = (beta2 v) + ((c2 g) g)
+ *   x' = clamp(x - step_size (m' / ((sqrt(v') rsb2) + adam_eps)), lo[ch], hi[ch])
+ * with c1 = 1 - beta1, c2 = 1 - beta2, step_size = lr / (1 - beta1^step), rsb2 = 1 / sqrt(1 - beta2^step), computed on the
+ * host in double from the float arguments and rounded once to float: svbrdf_photo_fit_adam_scalars writes the four, in that
+ * order, to out4 (host only, nothing launched) -- torch.optim.Adam's update without AMSGrad and weight decay.
+ *   loss_out[0] = the loss at the maps BEFORE the update; grad_out = g [B,12,H,W], or NULL: the gradient is never written.
+ *  - loss_out and grad_out EQUAL BIT FOR BIT those of svbrdf_photo_loss[_weighted]_fwd_bwd on the same inputs.
+ *  - `bounds_host`: NULL, or 12 x (lo, hi) floats ON THE HOST, one pair per channel (they ride in the launch's argument block);
+ *    -inf / +inf = no bound on that side, and all-infinite bounds are NULL's results bit for bit.  A NaN x' stays NaN.
+ *  - Non-finite maps behave as the composition does: the loss is NaN, the pixel's 36 values become NaN, every other pixel
+ *    is updated normally, scratch left zeroed.
+ *  - `step` is Adam's t, 1 for the first update.  SVBRDF_ERR_DIMS for step < 1, lr or adam_eps negative or not finite, a
+ *    beta outside [0, 1), a NaN bound or lo > hi; the other codes as the weighted entries'; all before any launch.
+ * The scene table is in device memory (no by-value form).  `workspace`: svbrdf_rendering_loss_workspace_bytes, same
+ * contract.  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect the two by symbol presence. */
+SVBRDF_API int svbrdf_photo_fit_adam_scalars(float lr, float beta1, float beta2, int step, float *out4);
+SVBRDF_API int svbrdf_photo_fit_adam_step(float *maps, float *exp_avg, float *exp_avg_sq, const float *photos,
+                                          const float *weights, int weight_planes, const float *scenes, const float *xrow,
+                                          float eps, const float *bounds_host, float lr, float beta1, float beta2,
+                                          float adam_eps, int step, float *loss_out, float *grad_out, void *workspace,
+                                          size_t workspace_bytes, int B, int S, int H, int W, void *stream);
+
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd
  * wrapper to apply the upstream gradient of the loss (the chain rule through

@@ -48,6 +48,8 @@ _LOSS_W = [_fp] * 3 + [_int] + [_fp] * 2 + [_float] + [_fp] * 3 + [_size] + _DIM
 _LOSS_X = [_fp] * 3 + [_int] + [_fp] * 3 + [_float] + [_fp] * 4 + [_size] + _DIMS
 # input, photos, weights, planes, scenes, xrow, eps, loss, grad, grad_scenes, ws, bytes
 _LOSS_SG = [_fp] * 3 + [_int] + [_fp] * 2 + [_float] + [_fp] * 4 + [_size] + _DIMS
+# maps, exp_avg, exp_avg_sq, photos, weights, planes, scenes, xrow, eps, bounds, lr, beta1, beta2, adam_eps, step, loss, grad, ws, bytes
+_LOSS_FIT = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_int] + [_fp] * 3 + [_size] + _DIMS
 _LOSS_L1 = [_fp] * 4 + [_float] * 3 + [_fp] * 3 + [_size] + _DIMS     # ... eps, l1_weight, eps_l1 ...
 _INPUTS = [_fp] * 3 + [_u64] * 2 + [_fp] * 2 + _DIMS
 # name -> (restype, argtypes) of every SVBRDF_API function of include/svbrdf_hip.h, applied once in _load();
@@ -83,6 +85,8 @@ SIGNATURES = {
     "svbrdf_photo_scene_grad_workspace_bytes": (_size, [_int] * 4),
     "svbrdf_photo_loss_scene_grad_fwd_bwd": (_int, _LOSS_SG),
     "svbrdf_head_photo_loss_scene_grad_fwd_bwd": (_int, _LOSS_SG),
+    "svbrdf_photo_fit_adam_scalars": (_int, [_float] * 3 + [_int, _fp]),
+    "svbrdf_photo_fit_adam_step": (_int, _LOSS_FIT),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
     "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
     "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
@@ -117,7 +121,7 @@ def _load():
             raise NativeLibraryError("cannot load %s: %s" % (_SO, e))
         for name, (restype, argtypes) in SIGNATURES.items():
             if not hasattr(lib, name):
-                if "photo_loss" in name or "photo_exposure" in name or "photo_scene_grad" in name:    # joined ABI version 8 without a bump: an older build lacks them
+                if "photo_loss" in name or "photo_exposure" in name or "photo_scene_grad" in name or "photo_fit" in name:    # joined ABI version 8 without a bump: an older build lacks them
                     raise NativeLibraryError("%s lacks %s (a build of ABI version 8 older than this binding) -- rebuild"
                                              % (_SO, name))
                 raise NativeLibraryError("%s does not export %s -- rebuild" % (_SO, name))
@@ -576,6 +580,53 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
     entry = stem + "_fwd_bwd" + ("_host_scenes" if on_host else "")
     return _fused_loss_call(entry, input.contiguous(), photos.contiguous(), scenes, (ctypes.c_float(eps),), want_grad,
                             B, S, H, W, extra)
+
+
+def photo_fit_adam_scalars(lr, beta1, beta2, step):
+    """(c1, c2, step_size, rsb2) of Adam's step `step` as float32 values (svbrdf_photo_fit_adam_scalars: host only, derived
+    in double from the float32 arguments the step entry takes, each rounded once)"""
+    out = (ctypes.c_float * 4)()
+    _call("svbrdf_photo_fit_adam_scalars", None, ctypes.c_float(lr), ctypes.c_float(beta1), ctypes.c_float(beta2), int(step),
+          ctypes.cast(out, _fp))
+    return tuple(out)
+
+
+def photo_fit_adam_step(maps, exp_avg, exp_avg_sq, photos, scenes, step, lr=1e-2, betas=(0.9, 0.999), adam_eps=1e-8,
+                        bounds=None, eps=0.1, weights=None, want_grad=False):
+    """One step of a photo fit (svbrdf_photo_fit_adam_step): the (weighted) photo loss at `maps`, its gradient and the Adam
+    update of `maps`, `exp_avg`, `exp_avg_sq` -- contiguous float32 [B,12,H,W] device tensors, updated IN PLACE -- in ONE
+    launch.  photos, scenes, eps, weights: as photo_loss (a host table is uploaded: the entry takes a device table).
+    `step`: Adam's t, 1 for the first update.  `bounds`: None, or a ctypes array of 24 floats on the host, (lo, hi) per
+    channel.  -> (loss at the maps before the update, [1] device tensor; the gradient, or None without `want_grad`: it is
+    then never written)."""
+    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (photos, "photos")):
+        _require_device_f32(t, name)
+    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if not t.is_contiguous() or t.shape != maps.shape or t.device != maps.device:
+            raise ValueError("%s is updated in place: a contiguous tensor of the maps' shape on their device" % name)
+    if photos.device != maps.device:
+        raise ValueError("input, photos and scenes must be on the same device")
+    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, maps, scenes)[:6]
+    if on_host:
+        scenes = upload_scene_table(scenes, maps.device)
+    if tuple(photos.shape) != (B, S, 3, H, W):
+        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
+                         % ((B, S, 3, H, W), tuple(photos.shape)))
+    extra = (None, 0)
+    if weights is not None:
+        _require_device_f32(weights, "weights")
+        if weights.device != maps.device:
+            raise ValueError("input, photos and weights must be on the same device")
+        if tuple(weights.shape) not in ((B, S, H, W), (B, 1, H, W)):
+            raise ValueError("weights must be [B,S,H,W] = %s or [B,1,H,W] for these maps and photos, got %s"
+                             % ((B, S, H, W), tuple(weights.shape)))
+        weights = weights.contiguous()
+        extra = (weights.data_ptr(), int(weights.shape[1]))
+    photos = photos.contiguous()
+    floats = (ctypes.c_float(eps), None if bounds is None else ctypes.cast(bounds, _fp), ctypes.c_float(lr),
+              ctypes.c_float(betas[0]), ctypes.c_float(betas[1]), ctypes.c_float(adam_eps), int(step))
+    return _fused_loss_call("svbrdf_photo_fit_adam_step", maps, exp_avg, scenes, floats, want_grad, B, S, H, W,
+                            (exp_avg_sq.data_ptr(), photos.data_ptr()) + extra)
 
 
 def mix_materials(svbrdf0, svbrdf1, alpha):

@@ -1,0 +1,156 @@
+"""Fitting SVBRDF maps to photographs: one Adam step per kernel launch.
+
+The loop a user of ``losses.PhotoLoss`` runs is
+
+    loss = PhotoLoss(x, photos, scenes[, weights]);  loss.backward();  Adam.step();  x[:, 3:].clamp_(0, 1)
+
+Loss and gradient are one launch; ``torch.optim.Adam`` and the clamp then make several more passes over the same
+``[B,12,H,W]`` tensors.  A thread of the photo kernels holds its pixel's complete gradient in registers behind the scene
+loop, and Adam is element-wise: ``PhotoFit.step`` is the whole line above in ONE launch (csrc/svbrdf_photo_fit.hip), the
+gradient never written.
+
+``composed_step`` is the same step in stock torch ops and the specification of the fused one.
+"""
+import ctypes
+import math
+
+import torch
+
+from . import _native, losses, renderers
+
+
+def adam_scalars(lr, beta1, beta2, step, dtype=torch.float32):
+    """(c1, c2, step_size, rsb2) of Adam's step ``step``: c1 = 1 - beta1, c2 = 1 - beta2, step_size = lr / (1 - beta1^t),
+    rsb2 = 1 / sqrt(1 - beta2^t).  float32: the library's derivation (svbrdf_photo_fit_adam_scalars: in double from the
+    float32 arguments, each rounded once to float32).  Any other dtype: Python floats."""
+    if dtype == torch.float32:
+        return _native.photo_fit_adam_scalars(lr, beta1, beta2, step)
+    if step < 1:
+        raise ValueError("step must be >= 1")
+    return 1.0 - beta1, 1.0 - beta2, lr / (1.0 - beta1 ** step), 1.0 / math.sqrt(1.0 - beta2 ** step)
+
+
+def _check_hyper(lr, betas, eps):
+    if not (math.isfinite(lr) and lr >= 0.0):
+        raise ValueError("lr must be finite and >= 0, got %r" % (lr,))
+    if not (math.isfinite(eps) and eps >= 0.0):
+        raise ValueError("eps must be finite and >= 0, got %r" % (eps,))
+    if len(betas) != 2 or not all(0.0 <= b < 1.0 for b in betas):
+        raise ValueError("betas must be two values in [0, 1), got %r" % (betas,))
+
+
+def _check_bounds(bounds):
+    """``bounds`` -> None or a host float32 [12,2] tensor of (lo, hi) per channel; +-inf = no bound on that side"""
+    if bounds is None:
+        return None
+    b = torch.as_tensor(bounds, dtype=torch.float32, device="cpu").contiguous()
+    if tuple(b.shape) != (12, 2):
+        raise ValueError("bounds must be None or [12,2] (lo, hi per channel), got %s" % (tuple(b.shape),))
+    if torch.isnan(b).any() or (b[:, 0] > b[:, 1]).any():
+        raise ValueError("bounds must hold lo <= hi for every channel, and no NaN")
+    return b
+
+
+def composed_step(maps, exp_avg, exp_avg_sq, step, photos, scenes, weights=None, lr=1e-2, betas=(0.9, 0.999), eps=1e-8,
+                  bounds=None, loss_eps=0.1, renderer=None):
+    """One step of the fit in stock torch ops -- THE SPECIFICATION of ``PhotoFit.step``: the gradient g of
+    ``losses.PhotoLoss(renderer, loss_eps)(maps, photos, scenes, weights)``, then per element, each operation rounded in
+    the maps' dtype,
+
+        m' = (beta1 m) + (c1 g)
+        v' = (beta2 v) + ((c2 g) g)
+        den = (sqrt(v') rsb2) + eps
+        x' = x - (step_size (m' / den))
+        x' = clamp(x', lo[ch], hi[ch])          a NaN stays a NaN; +-inf = no bound
+
+    with ``adam_scalars(lr, *betas, step)``.  ``maps``, ``exp_avg``, ``exp_avg_sq`` are updated in place; ``step`` is
+    Adam's t of this update (1 for the first).  Serves float64 maps, CPU tensors and plugin renderers too -- whatever
+    ``PhotoLoss`` serves.  -> the 0-dim loss at the maps before the update."""
+    _check_hyper(lr, betas, eps)
+    bounds = _check_bounds(bounds)
+    fn = losses.PhotoLoss(renderer if renderer is not None else renderers.LocalRenderer(), loss_eps)
+    x = maps.detach().clone().requires_grad_(True)
+    with torch.enable_grad():
+        loss = fn(x, photos, scenes, weights)
+        g, = torch.autograd.grad(loss, x)
+    c1, c2, step_size, rsb2 = adam_scalars(lr, betas[0], betas[1], step, maps.dtype)
+    with torch.no_grad():
+        m = exp_avg.mul_(betas[0]).add_(g * c1)
+        v = exp_avg_sq.mul_(betas[1]).add_((g * c2) * g)
+        den = (v.sqrt() * rsb2) + eps
+        xn = maps - (m / den) * step_size
+        if bounds is not None:
+            lo = bounds[:, 0].to(maps.device, maps.dtype).view(1, 12, 1, 1)
+            hi = bounds[:, 1].to(maps.device, maps.dtype).view(1, 12, 1, 1)
+            xn = torch.where(xn < lo, lo, xn)        # false for NaN: it stays
+            xn = torch.where(xn > hi, hi, xn)
+        maps.copy_(xn)
+    return loss.detach()
+
+
+class PhotoFit:
+    """Adam on a ``[B,12,H,W]`` map tensor under the photo loss, one launch per step.
+
+        fit = PhotoFit(maps, lr=1e-2, bounds=[[-inf, inf]] * 3 + [[0, 1]] * 9)
+        for _ in range(200):
+            loss = fit.step(photos, scenes)          # 0-dim device tensor: the loss BEFORE this update; no host sync
+
+    ``maps`` is updated in place (a leaf that requires grad is updated through ``.data``, like an optimiser does).
+    ``lr``, ``betas``, ``eps`` are ``torch.optim.Adam``'s (no AMSGrad, no weight decay) and may be reassigned between
+    steps; ``bounds``: None, or ``[12,2]`` (lo, hi) per channel applied to the updated maps, +-inf = none on that side;
+    ``loss_eps``: PhotoLoss's eps; ``renderer``: None = this package's ``LocalRenderer``.
+
+    The optimiser state has ``torch.optim.Adam``'s names and meaning, readable and assignable: ``fit.exp_avg``,
+    ``fit.exp_avg_sq`` (tensors like ``maps``) and the number of updates made so far, ``fit.state["step"]`` -- ``state`` is
+    the dict ``Adam.state[p]`` would be (the counter has no attribute of its own: ``step`` is the method).
+
+    float32 maps on a ROCm device with ``LocalRenderer``: ``step`` is ONE fused kernel
+    (svbrdf_photo_fit_adam_step).  Anything else -- float64 maps, CPU tensors, a plugin renderer -- is ``composed_step``,
+    the specification of the fused step."""
+
+    def __init__(self, maps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, bounds=None, loss_eps=0.1, renderer=None):
+        if not isinstance(maps, torch.Tensor) or maps.dim() != 4 or maps.shape[1] != 12 or not maps.dtype.is_floating_point:
+            raise ValueError("maps must be a floating-point [B,12,H,W] tensor")
+        if not maps.is_contiguous():
+            raise ValueError("maps are updated in place: a contiguous tensor")
+        _check_hyper(lr, betas, eps)
+        self.maps = maps
+        self.lr, self.betas, self.eps, self.loss_eps = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(loss_eps)
+        self.renderer = renderer if renderer is not None else renderers.LocalRenderer()
+        self.bounds = bounds
+        self.state = {"step": 0, "exp_avg": torch.zeros_like(maps.detach()), "exp_avg_sq": torch.zeros_like(maps.detach())}
+
+    exp_avg = property(lambda self: self.state["exp_avg"], lambda self, t: self.state.__setitem__("exp_avg", t))
+    exp_avg_sq = property(lambda self: self.state["exp_avg_sq"], lambda self, t: self.state.__setitem__("exp_avg_sq", t))
+
+    @property
+    def bounds(self):
+        return self._bounds
+
+    @bounds.setter
+    def bounds(self, value):
+        self._bounds = _check_bounds(value)
+        # the fused step takes them from the host, 24 floats in the launch's argument block
+        self._bounds_c = None if self._bounds is None else (ctypes.c_float * 24)(*self._bounds.reshape(-1).tolist())
+
+    def uses_fused_kernel(self):
+        return (losses.PhotoLoss(self.renderer).uses_fused_kernel() and self.maps.is_cuda
+                and self.maps.dtype == torch.float32)
+
+    def step(self, photos, scenes, weights=None):
+        """One update from ``photos`` [B,S,3,H,W] (or [B,3,H,W]), ``scenes`` and optional ``weights`` as
+        ``losses.PhotoLoss`` takes them -> the 0-dim loss at the maps before the update."""
+        x = self.maps.detach()
+        t = int(self.state["step"]) + 1
+        if not self.uses_fused_kernel():
+            loss = composed_step(x, self.exp_avg, self.exp_avg_sq, t, photos, scenes, weights, self.lr, self.betas, self.eps,
+                                 self._bounds, self.loss_eps, self.renderer)
+        else:
+            photos = losses.PhotoLoss._check(x, photos)
+            weights = losses._check_weights(weights, x, photos)
+            table = losses.PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
+            loss, _ = _native.photo_fit_adam_step(x, self.exp_avg, self.exp_avg_sq, photos, table.detach(), t, self.lr,
+                                                  self.betas, self.eps, self._bounds_c, self.loss_eps, weights)
+            loss = loss.view(())
+        self.state["step"] = t
+        return loss

@@ -1,7 +1,7 @@
 """Fit SVBRDF maps to photographs with the fused photo loss (losses.PhotoLoss): the inverse-rendering use of the engine.
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
-                               [--fit-exposure] [--fit-pose [--pose-lr 0.002]]
+                               [--fit-exposure] [--fit-pose [--pose-lr 0.002]] [--fused-step]
 
 Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
 each from ``synthesis.render_inputs`` (the scene table is what that call draws from torch's global generator: the same seed
@@ -17,6 +17,10 @@ step for the loss and both gradients; the mean |log e - log e*| is printed besid
 "somewhere next to the lens") and fits the six position columns of the scene table jointly with the maps -- and with the
 gains under ``--fit-exposure`` -- through the table's gradient, which comes out of the same one launch per step; the mean
 |position - truth| is printed beside the maps' error.  The positions take their own learning rate, ``--pose-lr``.
+
+``--fused-step``: the whole step -- loss, gradient, Adam update of the maps and the clamp of diffuse, roughness and specular
+to [0, 1] -- is ONE launch (``fitting.PhotoFit``: the gradient is never written, ``torch.optim.Adam`` is not used).  Only the
+maps have a fused update: refused with ``--fit-exposure`` or ``--fit-pose``, whose joint fits stay on the path above.
 """
 import argparse
 import os
@@ -31,7 +35,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import synth  # noqa: E402
-from svbrdf_estimation_amd import _native, losses, renderers, synthesis  # noqa: E402
+from svbrdf_estimation_amd import _native, fitting, losses, renderers, synthesis  # noqa: E402
 
 
 def main():
@@ -47,7 +51,10 @@ def main():
     ap.add_argument("--fit-exposure", action="store_true", help="photographs with hidden per-photo gains, fitted with the maps")
     ap.add_argument("--fit-pose", action="store_true", help="camera and light positions given a few per cent off, fitted with the maps")
     ap.add_argument("--pose-lr", type=float, default=0.002)
+    ap.add_argument("--fused-step", action="store_true", help="loss, gradient, Adam update and clamp of the maps in one launch")
     args = ap.parse_args()
+    if args.fused_step and (args.fit_exposure or args.fit_pose):
+        ap.error("--fused-step updates the maps only: not combined with --fit-exposure or --fit-pose")
     assert torch.cuda.is_available(), "needs a ROCm device"
     dev = torch.device("cuda:0")
     B, H, S = args.batch, args.size, args.photos
@@ -76,9 +83,14 @@ def main():
     fn = losses.PhotoLoss(renderers.LocalRenderer())
     groups = [{"params": [x] if log_e is None else [x, log_e]}] + ([] if pos is None else [{"params": [pos], "lr": args.pose_lr}])
     opt = torch.optim.Adam(groups, lr=args.lr)
-    print("fitting %d x [12,%d,%d] maps to %d photographs each (%s%s%s), Adam lr %g" % (
+    fit = None
+    if args.fused_step:
+        inf = float("inf")
+        fit = fitting.PhotoFit(x.detach(), lr=args.lr, bounds=[[-inf, inf]] * 3 + [[0.0, 1.0]] * 9)
+    print("fitting %d x [12,%d,%d] maps to %d photographs each (%s%s%s), Adam lr %g%s" % (
         B, H, H, S, "sensor noise" if args.noise else "noise-free", ", hidden gains fitted too" if args.fit_exposure else "",
-        ", positions fitted too (lr %g)" % args.pose_lr if args.fit_pose else "", args.lr))
+        ", positions fitted too (lr %g)" % args.pose_lr if args.fit_pose else "", args.lr,
+        ", the whole step in one launch" if fit is not None else ""))
     t_last, step_ms = None, []
     for step in range(args.steps):
         if step % args.print_every == 0:
@@ -87,13 +99,16 @@ def main():
             if t_last is not None:
                 step_ms.append(1e3 * (now - t_last) / args.print_every)
             t_last = now
-        opt.zero_grad(set_to_none=True)
-        scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
-        loss = fn(x, photos, scenes) if log_e is None else fn(x, photos, scenes, None, log_e.exp())
-        loss.backward()
-        opt.step()
-        with torch.no_grad():
-            x[:, 3:].clamp_(0.0, 1.0)
+        if fit is not None:
+            loss = fit.step(photos, table)
+        else:
+            opt.zero_grad(set_to_none=True)
+            scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
+            loss = fn(x, photos, scenes) if log_e is None else fn(x, photos, scenes, None, log_e.exp())
+            loss.backward()
+            opt.step()
+            with torch.no_grad():
+                x[:, 3:].clamp_(0.0, 1.0)
         if step % args.print_every == 0 or step == args.steps - 1:
             err = (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
             gains = "" if log_e is None else "  mean |log e - log e*| %.5f" % (log_e.detach() - hidden.log()).abs().mean().item()

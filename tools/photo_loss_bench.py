@@ -1,6 +1,6 @@
 """The fused photo loss against K3 and against the composed form, one process, one box (profiles/r09_photo_loss.txt).
 
-    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...] [--head] [--weights {none,shared,per-photo}] [--pose] [--exposure]
+    python tools/photo_loss_bench.py [--out FILE] [--variants TAG=LIB ...] [--head] [--weights {none,shared,per-photo}] [--pose] [--exposure] [--fit]
 
 At the configuration-2 shape (B = 8, 256 x 256, S = 9, scene table by value, six batches rotating beyond the 256 MB
 Infinity Cache, as bench.py does) it prints the event-timed median per launch of
@@ -34,6 +34,11 @@ measure_pose_photo_loss, the method of tests/test_gpu_pose_photo_loss.py's speed
 (svbrdf_photo_loss_exposure_fwd_bwd, per-photo weights, device table), the weighted kernel on the pre-scaled table and the
 composed definition with an exposure leaf (tests/exposure_photo_checks.py::measure_exposure_photo_loss, the method of
 tests/test_gpu_exposure_photo_loss.py's speed test).
+
+--fit: the fit-step leg instead -- the fused step (svbrdf_photo_fit_adam_step through fitting.PhotoFit: loss, gradient, Adam
+update and clamp of the maps in ONE launch, per-photo weights, device table), the weighted loss kernel's launch on the same
+data, and the composed step -- PhotoLoss forward + backward, torch.optim.Adam.step(), clamp_ -- with the stock default and
+with fused=True (tests/photo_fit_checks.py::measure_photo_fit, the method of tests/test_gpu_photo_fit.py's speed test).
 
 --variants: other builds of the library (tools/build_variant.sh, e.g. the photo-loss unit compiled with another of the
 Makefile's scheduler sets), each measured in a child process of its own on this box, interleaved with the shipped build.
@@ -96,12 +101,15 @@ def measure_composed(dev, native, sets=6, n=30, rounds=3):
     return medians["composed_us"]
 
 
-def child(head=False, weights="none", pose=False, exposure=False):
+def child(head=False, weights="none", pose=False, exposure=False, fit=False):
     import torch
     from svbrdf_estimation_amd import _native
     import photo_checks
     dev = torch.device("cuda:0")
-    if pose:
+    if fit:
+        import photo_fit_checks
+        res = photo_fit_checks.measure_photo_fit(dev, _native)
+    elif pose:
         import pose_photo_checks
         res = pose_photo_checks.measure_pose_photo_loss(dev, _native)
     elif exposure:
@@ -132,12 +140,14 @@ def main():
                     help="the scene-gradient leg: photo loss with grad_scenes, weighted kernel, composed torch-op definition")
     ap.add_argument("--exposure", action="store_true",
                     help="the exposure leg: photo loss with grad_exposure, weighted kernel, composed definition with an exposure leaf")
+    ap.add_argument("--fit", action="store_true",
+                    help="the fit-step leg: fused loss + Adam step, weighted kernel, PhotoLoss + torch.optim.Adam + clamp_")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    if args.head + (args.weights != "none") + args.pose + args.exposure > 1:
-        ap.error("--head, --weights, --pose and --exposure measure different legs: give one of them")
+    if args.head + (args.weights != "none") + args.pose + args.exposure + args.fit > 1:
+        ap.error("--head, --weights, --pose, --exposure and --fit measure different legs: give one of them")
     if args.child:
-        return child(args.head, args.weights, args.pose, args.exposure)
+        return child(args.head, args.weights, args.pose, args.exposure, args.fit)
     builds = [("shipped", None)] + [tuple(v.split("=", 1)) for v in args.variants]
     rows = []
     for p in range(args.passes):
@@ -147,7 +157,7 @@ def main():
                 env["SVBRDF_HIP_LIB"] = os.path.abspath(lib)
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--weights", args.weights]
                                  + (["--head"] if args.head else []) + (["--pose"] if args.pose else [])
-                                 + (["--exposure"] if args.exposure else []), env=env, text=True, timeout=300,
+                                 + (["--exposure"] if args.exposure else []) + (["--fit"] if args.fit else []), env=env, text=True, timeout=300,
                                  stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
             line = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")]
             if out.returncode != 0 or not line:
@@ -155,7 +165,17 @@ def main():
                 raise SystemExit("measurement of build %r failed (exit status %s): nothing more is started" % (tag, out.returncode))
             rows.append((tag, p, json.loads(line[0][7:])))
     B, H, S = 8, 256, 9
-    if args.pose or args.exposure:
+    if args.fit:
+        lines = ["# tools/photo_loss_bench.py --fit on %s; B = %d, %d x %d, S = %d, per-photo weights, device table, %d rotating batches" % (
+            rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
+            "# medians of event-timed steps (us per step); algorithmic bytes of the fused step (72 + 3 S + P) * 4 * H * W * B = %.1f MB, "
+            "of the weighted loss (24 + 3 S + P): byte ratio %.3f" % ((72 + 3 * S + S) * 4 * H * H * B / 1e6, rows[0][2]["byte_ratio"])]
+        for tag, p, r in rows:
+            lines.append("%-16s pass %d: fused step %7.2f  weighted loss launch %7.2f (ratio %.3f)  composed step PhotoLoss fwd + bwd, "
+                         "Adam, clamp_: stock %8.2f, fused=True %8.2f  fused step / faster composed %.3f   fused step = %.3f of 8 TB/s"
+                         "   rounds %s" % (tag, p, r["fit_us"], r["weighted_us"], r["fit_over_weighted"], r["composed_us"],
+                                           r["composed_fused_us"], r["fit_over_composed"], r["fit_frac_of_8TBps"], r["rounds"]))
+    elif args.pose or args.exposure:
         key, what, leaf = ("pose_us", "grad_scenes", "a table") if args.pose else ("exposure_us", "grad_exposure", "an exposure")
         lines = ["# tools/photo_loss_bench.py --%s on %s; B = %d, %d x %d, S = %d, per-photo weights, device table, %d rotating batches" % (
             "pose" if args.pose else "exposure", rows[0][2]["device"], B, H, H, S, rows[0][2]["sets"]),
