@@ -365,6 +365,29 @@ SVBRDF_API int svbrdf_photo_fit_adam_step(float *maps, float *exp_avg, float *ex
                                           float adam_eps, int step, float *loss_out, float *grad_out, void *workspace,
                                           size_t workspace_bytes, int B, int S, int H, int W, void *stream);
 
+/* SEVERAL steps of the same fit in ONE launch.  The call leaves `maps`, `exp_avg`, `exp_avg_sq` and losses_out[k]
+ * EQUAL BIT FOR BIT to n_steps successive calls of svbrdf_photo_fit_adam_step with step = first_step + k and the same
+ * other arguments, in one kernel launch.  losses_out[k], k < n_steps, is the loss BEFORE update k (a NaN compares as
+ * "both NaN").
+ * The fit is pixel-local, so the thread that owns a pixel runs the steps on it with maps and state kept on chip: they are
+ * read from memory once and written once, and no workgroup waits for another.
+ *  - 1 <= n_steps <= SVBRDF_PHOTO_FIT_MAX_STEPS and first_step >= 1, else SVBRDF_ERR_DIMS; the other checks are the single
+ *    step's, in its order; all before any launch.
+ *  - `workspace`: svbrdf_photo_fit_steps_workspace_bytes(n_steps, B, S, H, W) bytes = n_steps times
+ *    svbrdf_rendering_loss_workspace_bytes (every step sums its loss in 65 words of its own), same contract: zeroed once by
+ *    the caller, left zeroed by every completed call.  Too small for n_steps: SVBRDF_ERR_WORKSPACE.
+ *  - Non-finite maps behave as n single steps do: every losses_out[k] is NaN, the pixel's 36 values become NaN, every other
+ *    pixel is updated normally.
+ * No gradient output (of which step?) and no learning-rate schedule inside a launch.  ADDED TO ABI VERSION 8 WITHOUT A BUMP:
+ * detect the two by symbol presence. */
+#define SVBRDF_PHOTO_FIT_MAX_STEPS 64
+SVBRDF_API size_t svbrdf_photo_fit_steps_workspace_bytes(int n_steps, int B, int S, int H, int W);
+SVBRDF_API int svbrdf_photo_fit_adam_steps(float *maps, float *exp_avg, float *exp_avg_sq, const float *photos,
+                                           const float *weights, int weight_planes, const float *scenes, const float *xrow,
+                                           float eps, const float *bounds_host, float lr, float beta1, float beta2,
+                                           float adam_eps, int first_step, int n_steps, float *losses_out, void *workspace,
+                                           size_t workspace_bytes, int B, int S, int H, int W, void *stream);
+
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd
  * wrapper to apply the upstream gradient of the loss (the chain rule through

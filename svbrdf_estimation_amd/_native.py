@@ -50,6 +50,8 @@ _LOSS_X = [_fp] * 3 + [_int] + [_fp] * 3 + [_float] + [_fp] * 4 + [_size] + _DIM
 _LOSS_SG = [_fp] * 3 + [_int] + [_fp] * 2 + [_float] + [_fp] * 4 + [_size] + _DIMS
 # maps, exp_avg, exp_avg_sq, photos, weights, planes, scenes, xrow, eps, bounds, lr, beta1, beta2, adam_eps, step, loss, grad, ws, bytes
 _LOSS_FIT = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_int] + [_fp] * 3 + [_size] + _DIMS
+# ... adam_eps, first_step, n_steps, losses, ws, bytes: the step's list with (first_step, n_steps) for `step` and no gradient
+_LOSS_FIT_STEPS = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_int] * 2 + [_fp] * 2 + [_size] + _DIMS
 _LOSS_L1 = [_fp] * 4 + [_float] * 3 + [_fp] * 3 + [_size] + _DIMS     # ... eps, l1_weight, eps_l1 ...
 _INPUTS = [_fp] * 3 + [_u64] * 2 + [_fp] * 2 + _DIMS
 # name -> (restype, argtypes) of every SVBRDF_API function of include/svbrdf_hip.h, applied once in _load();
@@ -87,6 +89,8 @@ SIGNATURES = {
     "svbrdf_head_photo_loss_scene_grad_fwd_bwd": (_int, _LOSS_SG),
     "svbrdf_photo_fit_adam_scalars": (_int, [_float] * 3 + [_int, _fp]),
     "svbrdf_photo_fit_adam_step": (_int, _LOSS_FIT),
+    "svbrdf_photo_fit_steps_workspace_bytes": (_size, [_int] * 5),
+    "svbrdf_photo_fit_adam_steps": (_int, _LOSS_FIT_STEPS),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
     "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
     "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
@@ -627,6 +631,63 @@ def photo_fit_adam_step(maps, exp_avg, exp_avg_sq, photos, scenes, step, lr=1e-2
               ctypes.c_float(betas[0]), ctypes.c_float(betas[1]), ctypes.c_float(adam_eps), int(step))
     return _fused_loss_call("svbrdf_photo_fit_adam_step", maps, exp_avg, scenes, floats, want_grad, B, S, H, W,
                             (exp_avg_sq.data_ptr(), photos.data_ptr()) + extra)
+
+
+PHOTO_FIT_MAX_STEPS = 64        # SVBRDF_PHOTO_FIT_MAX_STEPS of include/svbrdf_hip.h
+
+
+def photo_fit_adam_steps(maps, exp_avg, exp_avg_sq, photos, scenes, first_step, n_steps, lr=1e-2, betas=(0.9, 0.999),
+                         adam_eps=1e-8, bounds=None, eps=0.1, weights=None):
+    """`n_steps` consecutive steps of a photo fit in ONE launch (svbrdf_photo_fit_adam_steps), 1 <= n_steps <=
+    PHOTO_FIT_MAX_STEPS: bit for bit what `n_steps` calls of photo_fit_adam_step with step = first_step, first_step + 1,
+    ... leave in `maps`, `exp_avg`, `exp_avg_sq`, the other arguments as there.  -> float32 [n_steps] device tensor: the loss
+    before each update.  No gradient is returned."""
+    if not 1 <= int(n_steps) <= PHOTO_FIT_MAX_STEPS:
+        raise ValueError("n_steps must lie in [1, %d], got %r" % (PHOTO_FIT_MAX_STEPS, n_steps))
+    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (photos, "photos")):
+        _require_device_f32(t, name)
+    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if not t.is_contiguous() or t.shape != maps.shape or t.device != maps.device:
+            raise ValueError("%s is updated in place: a contiguous tensor of the maps' shape on their device" % name)
+    if photos.device != maps.device:
+        raise ValueError("input, photos and scenes must be on the same device")
+    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, maps, scenes)[:6]
+    if on_host:
+        scenes = upload_scene_table(scenes, maps.device)
+    if tuple(photos.shape) != (B, S, 3, H, W):
+        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
+                         % ((B, S, 3, H, W), tuple(photos.shape)))
+    extra = (None, 0)
+    if weights is not None:
+        _require_device_f32(weights, "weights")
+        if weights.device != maps.device:
+            raise ValueError("input, photos and weights must be on the same device")
+        if tuple(weights.shape) not in ((B, S, H, W), (B, 1, H, W)):
+            raise ValueError("weights must be [B,S,H,W] = %s or [B,1,H,W] for these maps and photos, got %s"
+                             % ((B, S, H, W), tuple(weights.shape)))
+        weights = weights.contiguous()
+        extra = (weights.data_ptr(), int(weights.shape[1]))
+    photos = photos.contiguous()
+    n_steps = int(n_steps)
+    ws = _workspace(maps.device, _load().svbrdf_photo_fit_steps_workspace_bytes(n_steps, B, S, H, W))
+    losses = torch.empty(n_steps, dtype=torch.float32, device=maps.device)
+    xr = xrow(maps.device, W)
+    hook = _launch_hook
+    if hook is not None:
+        hook("begin")
+    try:
+        _call("svbrdf_photo_fit_adam_steps", maps.device, maps.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+              photos.data_ptr(), *extra, scenes.data_ptr(), xr.data_ptr(), ctypes.c_float(eps),
+              None if bounds is None else ctypes.cast(bounds, _fp), ctypes.c_float(lr), ctypes.c_float(betas[0]),
+              ctypes.c_float(betas[1]), ctypes.c_float(adam_eps), int(first_step), n_steps, losses.data_ptr(), ws.data_ptr(),
+              ws.numel() * 8, B, S, H, W)
+    except NativeLibraryError:
+        ws.zero_()      # (as _fused_loss_call: only a completed call leaves the scratch zeroed)
+        raise
+    finally:
+        if hook is not None:
+            hook("end")
+    return losses
 
 
 def mix_materials(svbrdf0, svbrdf1, alpha):

@@ -9,6 +9,9 @@ Loss and gradient are one launch; ``torch.optim.Adam`` and the clamp then make s
 loop, and Adam is element-wise: ``PhotoFit.step`` is the whole line above in ONE launch (csrc/svbrdf_photo_fit.hip), the
 gradient never written.
 
+``PhotoFit.steps(n, ...)`` runs n consecutive steps on the same photographs in ceil(n / 64) launches, maps and state kept
+on chip between the steps, bit for bit the n single steps.
+
 ``composed_step`` is the same step in stock torch ops and the specification of the fused one.
 """
 import ctypes
@@ -154,3 +157,34 @@ class PhotoFit:
             loss = loss.view(())
         self.state["step"] = t
         return loss
+
+    def steps(self, n, photos, scenes, weights=None):
+        """``n`` consecutive updates from the same ``photos``, ``scenes`` and ``weights`` -> a ``[n]`` device tensor of the
+        losses at the maps before each update; no host synchronisation.  Maps, state and losses are those of ``n`` calls
+        of ``step`` -- on the fused path bit for bit, in ceil(n / 64) launches (svbrdf_photo_fit_adam_steps: the thread
+        that owns a pixel runs the steps on it with maps and state kept on chip; csrc/svbrdf_photo_fit.hip).  ``lr``,
+        ``betas``, ``eps`` and ``bounds`` are read once per call; ``state["step"]`` advances by ``n``.  Anything but float32
+        maps on a ROCm device with ``LocalRenderer`` is ``n`` times ``composed_step``."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("n must be >= 1, got %r" % (n,))
+        x = self.maps.detach()
+        lr, betas, eps, bounds, bounds_c = self.lr, self.betas, self.eps, self._bounds, self._bounds_c
+        t = int(self.state["step"]) + 1
+        if not self.uses_fused_kernel():
+            seen = []
+            for k in range(n):
+                seen.append(composed_step(x, self.exp_avg, self.exp_avg_sq, t + k, photos, scenes, weights, lr, betas, eps,
+                                          bounds, self.loss_eps, self.renderer))
+                self.state["step"] = t + k
+            return torch.stack(seen)
+        photos = losses.PhotoLoss._check(x, photos)
+        weights = losses._check_weights(weights, x, photos)
+        table = losses.PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1]).detach()
+        out = []
+        for first in range(0, n, _native.PHOTO_FIT_MAX_STEPS):
+            k = min(_native.PHOTO_FIT_MAX_STEPS, n - first)
+            out.append(_native.photo_fit_adam_steps(x, self.exp_avg, self.exp_avg_sq, photos, table, t + first, k, lr, betas,
+                                                    eps, bounds_c, self.loss_eps, weights))
+            self.state["step"] = t + first + k - 1
+        return out[0] if len(out) == 1 else torch.cat(out)

@@ -1,7 +1,7 @@
 """Fit SVBRDF maps to photographs with the fused photo loss (losses.PhotoLoss): the inverse-rendering use of the engine.
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
-                               [--fit-exposure] [--fit-pose [--pose-lr 0.002]] [--fused-step]
+                               [--fit-exposure] [--fit-pose [--pose-lr 0.002]] [--fused-step [--steps-per-launch K]]
 
 Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
 each from ``synthesis.render_inputs`` (the scene table is what that call draws from torch's global generator: the same seed
@@ -21,6 +21,12 @@ gains under ``--fit-exposure`` -- through the table's gradient, which comes out 
 ``--fused-step``: the whole step -- loss, gradient, Adam update of the maps and the clamp of diffuse, roughness and specular
 to [0, 1] -- is ONE launch (``fitting.PhotoFit``: the gradient is never written, ``torch.optim.Adam`` is not used).  Only the
 maps have a fused update: refused with ``--fit-exposure`` or ``--fit-pose``, whose joint fits stay on the path above.
+
+``--steps-per-launch K`` (only with ``--fused-step``): K consecutive steps per launch (``fitting.PhotoFit.steps``: the thread
+that owns a pixel runs them with maps and state kept on chip, read from memory once and written once per launch; ceil(K / 64)
+launches).  Maps and losses are bit for bit those of K single-step launches.  The losses of every ``--print-every``-th step
+are printed from the returned tensor -- the maps' error only where a launch ends, the maps in between never reach memory --
+and the time per step is the time of a launch divided by its steps.
 """
 import argparse
 import os
@@ -52,7 +58,12 @@ def main():
     ap.add_argument("--fit-pose", action="store_true", help="camera and light positions given a few per cent off, fitted with the maps")
     ap.add_argument("--pose-lr", type=float, default=0.002)
     ap.add_argument("--fused-step", action="store_true", help="loss, gradient, Adam update and clamp of the maps in one launch")
+    ap.add_argument("--steps-per-launch", type=int, default=None, help="with --fused-step: this many consecutive steps per launch")
     args = ap.parse_args()
+    if args.steps_per_launch is not None and not args.fused_step:
+        ap.error("--steps-per-launch needs --fused-step: only the fused step runs several steps in a launch")
+    if args.steps_per_launch is not None and args.steps_per_launch < 1:
+        ap.error("--steps-per-launch must be >= 1")
     if args.fused_step and (args.fit_exposure or args.fit_pose):
         ap.error("--fused-step updates the maps only: not combined with --fit-exposure or --fit-pose")
     assert torch.cuda.is_available(), "needs a ROCm device"
@@ -91,6 +102,8 @@ def main():
         B, H, H, S, "sensor noise" if args.noise else "noise-free", ", hidden gains fitted too" if args.fit_exposure else "",
         ", positions fitted too (lr %g)" % args.pose_lr if args.fit_pose else "", args.lr,
         ", the whole step in one launch" if fit is not None else ""))
+    if args.steps_per_launch is not None:
+        return run_in_launches(args, fit, photos, table, x, truth)
     t_last, step_ms = None, []
     for step in range(args.steps):
         if step % args.print_every == 0:
@@ -118,6 +131,31 @@ def main():
                 step, loss.item(), err, gains, "  %.3f ms/step" % step_ms[-1] if step_ms else ""))
     if step_ms:
         print("median %.3f ms per step (loss + backward + Adam + clamp, host included)" % float(np.median(step_ms)))
+
+
+def run_in_launches(args, fit, photos, table, x, truth):
+    """--steps-per-launch: the fit in launches of K steps, the losses read from the tensors the launches return"""
+    K, launch_ms = args.steps_per_launch, []
+    print("%d steps per launch" % K)
+    for first in range(0, args.steps, K):
+        n = min(K, args.steps - first)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        losses_dev = fit.steps(n, photos, table)
+        torch.cuda.synchronize()
+        ms = 1e3 * (time.perf_counter() - t0) / n
+        if first:                               # (the first launch loads the code object)
+            launch_ms.append(ms)
+        seen = losses_dev.cpu().tolist()
+        for k, loss in enumerate(seen):
+            step = first + k
+            if step % args.print_every == 0 or step == args.steps - 1:
+                err = ""
+                if k == n - 1:
+                    err = "  mean |d,r,s - truth| %.5f behind it" % (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
+                print("step %4d  loss %.6f%s  %.3f ms/step" % (step, loss, err, ms))
+    if launch_ms:
+        print("median %.3f ms per step (%d steps per launch, host included)" % (float(np.median(launch_ms)), K))
 
 
 if __name__ == "__main__":
