@@ -907,7 +907,7 @@ __global__ __launch_bounds__(kThreads) void k_render_bwd_inl([[maybe_unused]] co
 //   per pixel: read 12 input + 12 target planes once, loop the S scenes in registers
 //   (geometry shared by input and target), accumulate |dlog| and the 12 map gradients,
 //   write 12 gradient planes once  -> 144 B/pixel of HBM traffic, independent of S.
-//   Loss: per-thread fp32 sum -> wave shuffle -> LDS -> one value per workgroup, added as a
+//   Loss: per-thread fp32 sum -> wave sum (wave_sum_k3) -> LDS -> one value per workgroup, added as a
 //   fixed-point integer to one of kLossSlots 64-bit accumulators (integer addition is
 //   associative, so the result is bitwise reproducible whatever the arrival order).  Each
 //   accumulator word also counts its arrivals in its top 16 bits, so ONE returning atomic
@@ -919,11 +919,55 @@ __global__ __launch_bounds__(kThreads) void k_render_bwd_inl([[maybe_unused]] co
 //   (A single shared accumulator + ticket serialises 2 atomics per workgroup on one address
 //   and cost ~45 us at 2048 workgroups -- measured; profiles/r01_k3_sweep.txt.)
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v)
+[[maybe_unused]] __device__ __forceinline__ float wave_sum(float v)      // (the photo units' own sums, and K3's with SVBRDF_K3_DPP_SUM=0)
 {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
+}
+
+// The same sum for K3's own launch tail, without the LDS pipe: __shfl_xor is a ds_bpermute_b32, and six of them in a row are
+// six dependent LDS round trips in front of the workgroup's arrival.  Same tree, hence the same bits: lane i adds the
+// value of lane i ^ 32, then ^ 16, ^ 8, ^ 4, ^ 2, ^ 1 (addition is commutative, only the grouping matters).
+//  * ^ 32 and ^ 16: gfx950's lane swaps.  v_permlane32_swap exchanges the upper half of its first operand with the lower
+//    half of its second, v_permlane16_swap the odd rows of 16 lanes of the first with the even rows of the second; given
+//    the same value twice, the two results hold lane i's and lane i ^ 32's (^ 16's) value between them in every lane.
+//  * ^ 8 ... ^ 1: DPP row rotations.  After the ^ 8 step (row_ror:8 is exactly ^ 8 inside a row of 16) every value repeats
+//    with period 8 along its row, so the lane four further (row_ror:4) holds what lane i ^ 4 holds; likewise period 4 and
+//    row_ror:2, period 2 and row_ror:1.
+// Every lane of the wave must be here (neither instruction reads a disabled lane): rendering_loss_body calls it outside
+// its `active` branch, and a workgroup is always kLossThreads lanes.
+#ifndef SVBRDF_K3_DPP_SUM
+#define SVBRDF_K3_DPP_SUM 1         // 0 = the ds_bpermute butterfly (wave_sum)
+#endif
+template <int CTRL>
+__device__ __forceinline__ float dpp_ror_add(float v)
+{
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float wave_sum_k3(float v)
+{
+#if SVBRDF_K3_DPP_SUM
+    {
+        const unsigned u = __builtin_bit_cast(unsigned, v);
+        const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+        const unsigned a = r[0], b = r[1];      // (elements copied out first: a bit cast of r[k] itself reads r[0] twice)
+        v = __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
+    }
+    {
+        const unsigned u = __builtin_bit_cast(unsigned, v);
+        const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+        const unsigned a = r[0], b = r[1];
+        v = __builtin_bit_cast(float, a) + __builtin_bit_cast(float, b);
+    }
+    v = dpp_ror_add<0x128>(v);      // row_ror:8
+    v = dpp_ror_add<0x124>(v);      // row_ror:4
+    v = dpp_ror_add<0x122>(v);      // row_ror:2
+    v = dpp_ror_add<0x121>(v);      // row_ror:1
+    return v;
+#else
+    return wave_sum(v);
+#endif
 }
 
 constexpr int kLossSlots = 64;                    // sharded accumulators (power of two)
@@ -1079,10 +1123,17 @@ __device__ __forceinline__ void loss_pixel_scene_any(const VConst &K, const Geom
 #ifndef SVBRDF_K3_EARLY_COORDS
 #define SVBRDF_K3_EARLY_COORDS 1    // pixel coordinates loaded in front of the plane loads (rendering_loss_body)
 #endif
-template <int NL, bool WITH_GRAD, int DEFER = 0>
+#ifndef SVBRDF_K3_ENTRY_FETCH
+#define SVBRDF_K3_ENTRY_FETCH 1     // the launch's scalars fetched together at wave entry (rendering_loss_body)
+#endif
+#ifndef SVBRDF_K3_EARLY_SCENE
+#define SVBRDF_K3_EARLY_SCENE 1     // render 0's scene row requested in front of the plane loads (rendering_loss_body)
+#endif
+// EARLY_SC: the row of render 0 is already in `sc_early` (requested by the caller)
+template <int NL, bool WITH_GRAD, int DEFER = 0, bool EARLY_SC = false>
 __device__ __forceinline__ float loss_scene_loop(const MapK &mi, const MapK &mt_in, float x, float y,
                                                  const float *__restrict__ scp, const float *sc_lds, int S,
-                                                 float eps, float inv_count, Grad &acc)
+                                                 float eps, float inv_count, Grad &acc, const float *sc_early = nullptr)
 {
     constexpr int ST = 9;               // floats per scene row
     float lsum = 0.0f;
@@ -1094,7 +1145,16 @@ __device__ __forceinline__ float loss_scene_loop(const MapK &mi, const MapK &mt_
     const long long tm0 = clock64(), wc0 = wall_clock64();
 #endif
     if (WITH_GRAD) {
-        load_scene(scp, sc);
+        if (EARLY_SC) {
+            load_scene(sc_early, sc);
+            // opaque from here on: the two scene loops then start from values of their own, as they did from loads of
+            // their own, and render 0's geometry stays inside each (common to both, it is otherwise lifted above the
+            // branch between them, and the register allocation of everything behind it changes: spills)
+            asm volatile("" : "+s"(sc[0]), "+s"(sc[1]), "+s"(sc[2]), "+s"(sc[3]), "+s"(sc[4]), "+s"(sc[5]), "+s"(sc[6]),
+                              "+s"(sc[7]), "+s"(sc[8]));
+        } else {
+            load_scene(scp, sc);
+        }
         Geom ga = geometry<true>(K, sc, x, y), gb;               // render 0
         load_scene(scp + (S > 1 ? ST : 0), sc);                  // scalars of render 1
         // One pass = shade render s with geometry G_CUR while the geometry of render s+1 goes into G_NEXT.  The loop
@@ -1304,6 +1364,20 @@ __device__ __forceinline__ void rendering_loss_body(const float *__restrict__ in
 #if SVBRDF_TIMING
     const long long t_entry = wall_clock64();
 #endif
+#if SVBRDF_K3_ENTRY_FETCH
+    if (WITH_GRAD && EARLY_COORDS) {
+        // The launch's scalars sit behind the by-value table in the kernel-argument block, and left to the compiler each
+        // is fetched where it is first used: S, the grid width, ws, the plane pointers -- four dependent scalar round trips
+        // (s_load, s_waitcnt lgkmcnt(0)) between wave entry and the first plane load, in every wave, and one more (the grid
+        // height) in front of the arrival atomic.  Required in SGPRs here, all of them are requested at once and awaited
+        // once (tests/test_isa_wave_ends.py).  Width and height of the grid together: asked for alone, the width was put
+        // into the unused fourth register of the S/H/W load and had to wait for that load first.  (By-value-table kernels
+        // only, like the early coordinate loads; not tried on the device-table variants.)
+        asm volatile("" ::"s"(input), "s"(target), "s"(xrow), "s"(grad_input), "s"(ws), "s"(loss_out), "s"(S), "s"(H), "s"(W),
+                     "s"(eps), "s"(inv_count), "s"(loss_scale), "s"(fixed_scale), "s"(gridDim.x), "s"(gridDim.y));
+        __builtin_amdgcn_sched_barrier(0);      // (or the scheduler lifts the first use of S, and a wait of its own, over it)
+    }
+#endif
 #if SVBRDF_K3_STAGGER
     if (WITH_GRAD && EARLY_COORDS && S >= 6) {     // (by-value-table kernels only, like the early coordinate loads)
         // The first resident round of a launch -- 1024 workgroups, 4096 waves -- issues 25 MB of plane loads within 0.4 us,
@@ -1347,6 +1421,17 @@ __device__ __forceinline__ void rendering_loss_body(const float *__restrict__ in
             const unsigned p32 = (unsigned)pix, sh = (unsigned)__builtin_ctz((unsigned)W);
             x_early = xrow[p32 & (unsigned)(W - 1)];
             y_early = xrow[p32 >> sh];
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        // The scene row of render 0 likewise: fetched where the scene loop first uses it, it is one more scalar round trip
+        // AFTER the planes have arrived, in front of the un-pipelined first geometry.  Requested here it lands under the
+        // plane loads.  It costs nine SGPRs across the prologue and nothing else (render 0's geometry computed this
+        // early kept 13 more VGPRs live and made the kernel spill, HISTORY.md A.1).  Render 1's row requested here too
+        // measured no further gain at config 2 and cost the config-5 shape 0.1-0.2 % (profiles/r20_k3_ab_pairs.txt).
+        [[maybe_unused]] float sc_early[9];
+        constexpr bool early_scene = SVBRDF_K3_EARLY_SCENE && EARLY_COORDS && WITH_GRAD;
+        if (early_scene) {
+            load_scene(scenes + (size_t)b * S * 9, sc_early);
             __builtin_amdgcn_sched_barrier(0);
         }
         if (HEAD) {     // input is the [B,9,H,W] post-tanh generator output
@@ -1431,9 +1516,9 @@ __device__ __forceinline__ void rendering_loss_body(const float *__restrict__ in
         }
         const float *__restrict__ scp = scenes + (size_t)b * S * 9;
         if (__all(tied))     // wave-uniform: every lane's input AND target roughness channels are tied
-            lsum = loss_scene_loop<1, WITH_GRAD, kDefer>(mi, mt, x[0], y, scp, sc_lds, S, eps, inv_count, acc);
+            lsum = loss_scene_loop<1, WITH_GRAD, kDefer, early_scene>(mi, mt, x[0], y, scp, sc_lds, S, eps, inv_count, acc, sc_early);
         else
-            lsum = loss_scene_loop<3, WITH_GRAD, kDefer & 3>(mi, mt, x[0], y, scp, sc_lds, S, eps, inv_count, acc);
+            lsum = loss_scene_loop<3, WITH_GRAD, kDefer & 3, early_scene>(mi, mt, x[0], y, scp, sc_lds, S, eps, inv_count, acc, sc_early);
         if (WITH_L1) lsum = fma_(l1sum, l1.sum_scale, lsum);
 #if SVBRDF_TIMING
         if (WITH_GRAD && !HEAD) {       // timing build: entry / exit stamps of the wave beside the loop's (loss_scene_loop)
@@ -1449,7 +1534,7 @@ __device__ __forceinline__ void rendering_loss_body(const float *__restrict__ in
     }
     {
         __shared__ float wave_part[kLossThreads / 64];
-        lsum = wave_sum(lsum);
+        lsum = wave_sum_k3(lsum);
         if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = lsum;
         __syncthreads();
         if (threadIdx.x == 0) {     // the other waves retire here
