@@ -388,6 +388,30 @@ SVBRDF_API int svbrdf_photo_fit_adam_steps(float *maps, float *exp_avg, float *e
                                            float adam_eps, int first_step, int n_steps, float *losses_out, void *workspace,
                                            size_t workspace_bytes, int B, int S, int H, int W, void *stream);
 
+/* One step of the fit WITH the gradient towards the scene table, still ONE launch: svbrdf_photo_fit_adam_step's argument
+ * list with `grad_scenes` [B,S,9] added (REQUIRED) -- the light position, the camera position and the gain of a captured
+ * photograph are refined together with the maps, and everything that is H W-sized stays inside the launch.
+ *  - loss_out, grad_out (if given) and grad_scenes EQUAL BIT FOR BIT svbrdf_photo_loss_scene_grad_fwd_bwd's loss_out,
+ *    grad_input and grad_scenes on the same inputs, its NaN rules included: a colour that is NaN, infinite or <= 0, a bad
+ *    weight, or a wave sum beyond the limit gives a NaN loss and an all-NaN grad_scenes.
+ *  - maps', exp_avg', exp_avg_sq' EQUAL BIT FOR BIT svbrdf_photo_fit_adam_step's on that gradient: the three lines above
+ *    with the scalars of svbrdf_photo_fit_adam_scalars.  The gradients are those at the maps BEFORE the update.
+ *  - The map update is applied whatever the loss turns out to be (the thread that owns a pixel cannot know the launch's
+ *    loss), as svbrdf_photo_fit_adam_step applies it beside a NaN pixel.
+ *  - `workspace`: svbrdf_photo_scene_grad_workspace_bytes(B, S, H, W) bytes, same contract: left zeroed.
+ *  - Error codes, all before any launch and with no device buffer touched: the scene-gradient entry's checks in its order
+ *    (its LDS limit on S included, and here S <= 383: six more words per thread wait in LDS across the scene loop), then
+ *    the fit entry's of step, lr, the betas, adam_eps and the bounds.
+ * Not offered: several steps in one launch (grad_scenes sums over all pixels of an item: applying it between two steps
+ * needs a grid barrier), a head variant, and the Adam update of the table itself (a few hundred floats whose
+ * parameterisation is the caller's).  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect it by symbol presence. */
+SVBRDF_API int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg, float *exp_avg_sq, const float *photos,
+                                                     const float *weights, int weight_planes, const float *scenes,
+                                                     const float *xrow, float eps, const float *bounds_host, float lr,
+                                                     float beta1, float beta2, float adam_eps, int step, float *loss_out,
+                                                     float *grad_out, float *grad_scenes, void *workspace,
+                                                     size_t workspace_bytes, int B, int S, int H, int W, void *stream);
+
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd
  * wrapper to apply the upstream gradient of the loss (the chain rule through

@@ -50,6 +50,8 @@ _LOSS_X = [_fp] * 3 + [_int] + [_fp] * 3 + [_float] + [_fp] * 4 + [_size] + _DIM
 _LOSS_SG = [_fp] * 3 + [_int] + [_fp] * 2 + [_float] + [_fp] * 4 + [_size] + _DIMS
 # maps, exp_avg, exp_avg_sq, photos, weights, planes, scenes, xrow, eps, bounds, lr, beta1, beta2, adam_eps, step, loss, grad, ws, bytes
 _LOSS_FIT = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_int] + [_fp] * 3 + [_size] + _DIMS
+# ... step, loss, grad, grad_scenes, ws, bytes: the step's list with grad_scenes behind the gradient
+_LOSS_FIT_SG = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_int] + [_fp] * 4 + [_size] + _DIMS
 # ... adam_eps, first_step, n_steps, losses, ws, bytes: the step's list with (first_step, n_steps) for `step` and no gradient
 _LOSS_FIT_STEPS = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_int] * 2 + [_fp] * 2 + [_size] + _DIMS
 _LOSS_L1 = [_fp] * 4 + [_float] * 3 + [_fp] * 3 + [_size] + _DIMS     # ... eps, l1_weight, eps_l1 ...
@@ -89,6 +91,7 @@ SIGNATURES = {
     "svbrdf_head_photo_loss_scene_grad_fwd_bwd": (_int, _LOSS_SG),
     "svbrdf_photo_fit_adam_scalars": (_int, [_float] * 3 + [_int, _fp]),
     "svbrdf_photo_fit_adam_step": (_int, _LOSS_FIT),
+    "svbrdf_photo_fit_adam_step_scene_grad": (_int, _LOSS_FIT_SG),
     "svbrdf_photo_fit_steps_workspace_bytes": (_size, [_int] * 5),
     "svbrdf_photo_fit_adam_steps": (_int, _LOSS_FIT_STEPS),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
@@ -596,13 +599,18 @@ def photo_fit_adam_scalars(lr, beta1, beta2, step):
 
 
 def photo_fit_adam_step(maps, exp_avg, exp_avg_sq, photos, scenes, step, lr=1e-2, betas=(0.9, 0.999), adam_eps=1e-8,
-                        bounds=None, eps=0.1, weights=None, want_grad=False):
+                        bounds=None, eps=0.1, weights=None, want_grad=False, want_scene_grad=False):
     """One step of a photo fit (svbrdf_photo_fit_adam_step): the (weighted) photo loss at `maps`, its gradient and the Adam
     update of `maps`, `exp_avg`, `exp_avg_sq` -- contiguous float32 [B,12,H,W] device tensors, updated IN PLACE -- in ONE
     launch.  photos, scenes, eps, weights: as photo_loss (a host table is uploaded: the entry takes a device table).
     `step`: Adam's t, 1 for the first update.  `bounds`: None, or a ctypes array of 24 floats on the host, (lo, hi) per
     channel.  -> (loss at the maps before the update, [1] device tensor; the gradient, or None without `want_grad`: it is
-    then never written)."""
+    then never written).
+
+    ``want_scene_grad=True``: svbrdf_photo_fit_adam_step_scene_grad, the same step and still ONE launch
+    -> (loss, grad or None, grad_scenes [B,S,9]): d loss / d scenes at the maps before the update, camera xyz | light xyz |
+    light rgb, as photo_loss(want_scene_grad=True) returns it bit for bit.  A NaN loss comes with an all-NaN grad_scenes;
+    the maps are updated whatever the loss is."""
     for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (photos, "photos")):
         _require_device_f32(t, name)
     for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
@@ -629,6 +637,12 @@ def photo_fit_adam_step(maps, exp_avg, exp_avg_sq, photos, scenes, step, lr=1e-2
     photos = photos.contiguous()
     floats = (ctypes.c_float(eps), None if bounds is None else ctypes.cast(bounds, _fp), ctypes.c_float(lr),
               ctypes.c_float(betas[0]), ctypes.c_float(betas[1]), ctypes.c_float(adam_eps), int(step))
+    if want_scene_grad:
+        grad_scenes = torch.empty_like(scenes)
+        loss, grad = _fused_loss_call("svbrdf_photo_fit_adam_step_scene_grad", maps, exp_avg, scenes, floats, want_grad, B, S,
+                                      H, W, (exp_avg_sq.data_ptr(), photos.data_ptr()) + extra, (grad_scenes.data_ptr(),),
+                                      "svbrdf_photo_scene_grad_workspace_bytes")
+        return loss, grad, grad_scenes
     return _fused_loss_call("svbrdf_photo_fit_adam_step", maps, exp_avg, scenes, floats, want_grad, B, S, H, W,
                             (exp_avg_sq.data_ptr(), photos.data_ptr()) + extra)
 

@@ -136,6 +136,10 @@ __device__ __forceinline__ void fit_body(float *maps, float *exp_avg, float *exp
     }
 }
 
+// svbrdf_photo_fit_pose.hip includes this file for AdamArgs, fit_stash, adam_channel and adam_scalars only: its kernels and
+// entry point are its own
+#ifndef SVBRDF_PHOTO_FIT_SHARED_ONLY
+
 #define SVBRDF_FIT_KERNEL(NAME, WEIGHTED)                                                                             \
     __global__ SVBRDF_PHOTO_LOSS_ATTRS void NAME(float *maps, float *exp_avg, float *exp_avg_sq,                      \
                                                  const float *__restrict__ photos, const float *__restrict__ weights, \
@@ -153,6 +157,8 @@ __device__ __forceinline__ void fit_body(float *maps, float *exp_avg, float *exp
 SVBRDF_FIT_KERNEL(k_fit_maps, false)
 SVBRDF_FIT_KERNEL(k_fit_maps_weighted, true)
 #undef SVBRDF_FIT_KERNEL
+
+#endif  // SVBRDF_PHOTO_FIT_SHARED_ONLY
 
 // The four scalars of a step, in double from the float arguments the step entry takes, each rounded once to float.
 // -> false: the arguments are not an Adam step's.
@@ -174,6 +180,8 @@ bool adam_scalars(float lr, float beta1, float beta2, int step, float out[4])
 // launch.  Maps and state are read from memory once, in front of the first step, and stored once, behind the last.  The
 // photographs and weights of the workgroup's 256 pixels are read again in every step ((3 S + P) KB, from L2 after the
 // first).  Results EQUAL BIT FOR BIT n launches of k_fit_maps*: the same statements on the same values. ----
+
+#ifndef SVBRDF_PHOTO_FIT_SHARED_ONLY
 
 // the two scalars of a step that depend on t, one pair per step of the launch, by value in the argument block
 struct RunScalars {
@@ -362,8 +370,11 @@ SVBRDF_FIT_RUN_KERNEL(k_fit_run, false)
 SVBRDF_FIT_RUN_KERNEL(k_fit_run_weighted, true)
 #undef SVBRDF_FIT_RUN_KERNEL
 
+#endif  // SVBRDF_PHOTO_FIT_SHARED_ONLY
+
 }  // namespace
 
+#ifndef SVBRDF_PHOTO_FIT_SHARED_ONLY
 extern "C" {
 
 int svbrdf_photo_fit_adam_scalars(float lr, float beta1, float beta2, int step, float *out4)
@@ -463,3 +474,4 @@ int svbrdf_photo_fit_adam_steps(float *maps, float *exp_avg, float *exp_avg_sq, 
 }
 
 }  // extern "C"
+#endif  // SVBRDF_PHOTO_FIT_SHARED_ONLY

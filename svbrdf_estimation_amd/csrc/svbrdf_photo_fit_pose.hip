@@ -1,0 +1,203 @@
+// svbrdf_photo_fit_pose.hip -- translation unit of libsvbrdf_hip.so: one step of a fit of SVBRDF maps to photographs
+// WITH the gradient towards the scene table -- the photo loss, its gradient towards the maps, the Adam update of the maps,
+// and d loss / d (camera, light position, light colour) of every photo -- in the one launch (added to ABI version 8
+// without a bump).
+//
+// A flash photograph never comes with an exact light position or a known gain.  svbrdf_photo_pose.hip returns the
+// gradient towards them and leaves the maps to torch.optim.Adam and clamp_, several passes over the [B,12,H,W] tensors;
+// svbrdf_photo_fit.hip updates the maps in the launch and holds the table frozen.  This unit is both: the thread of the
+// pose loop holds its pixel's complete map gradient in registers behind the loop exactly like the fit kernel's thread.
+//
+// Two kernels, unweighted and weighted, forward + adjoint, scene table in device memory.  Nothing is computed here that
+// the two units do not compute: they are included below without their kernels, launchers and entry points, and what is
+// written out here is the flow alone.
+//   * per workgroup pose_body<false, WEIGHTED>'s: a wave that holds a pixel runs whole (wave_index), the per-wave rows of
+//     float sums in dynamic LDS, pose_scene_loop<1|3, WEIGHTED> chosen per wave, the colour check, photo_sums_finish<true>
+//     with the pose body's two lambdas.  loss_out, grad_out and grad_scenes are therefore bit for bit those of
+//     svbrdf_photo_loss_scene_grad_fwd_bwd -- the NaN rules included;
+//   * where the pose body stores the gradient of a live lane, the thread stores it if grad_out was given and then runs
+//     fit_body's epilogue: the 24 state loads back to back, adam_channel per channel, 36 stores with the gradient stores'
+//     cache policy.  Diffuse and roughness as stored wait in LDS across the loop (fit_stash) beside expo_stash's three
+//     words.  maps', exp_avg' and exp_avg_sq' are bit for bit svbrdf_photo_fit_adam_step's on the same gradient;
+//   * the one place where the two flows disagree: a lane of a whole wave that has no pixel shades the item's LAST pixel
+//     with 1/N = 0.  The epilogue runs for live lanes only -- several lanes would otherwise apply the momentum update to
+//     that last pixel.
+// The map update is applied whatever the loss turns out to be: the thread cannot know the launch's loss.
+//
+// NOT here, and why:
+//   * several steps in one launch.  The table's gradient is a sum over all pixels of an item; a second step would need it
+//     reduced and applied between the steps -- a grid barrier, which this project does not build (svbrdf_photo_fit.hip,
+//     the section on several steps);
+//   * a head (9-channel) variant: PhotoFit fits maps;
+//   * the Adam update of the [B,S,9] table and of the gains: a few hundred floats whose parameterisation is the user's
+//     (tools/fit_photos.py fits log e, with a learning rate of its own).  A stock torch.optim on them is one or two tiny
+//     launches; this kernel's job is everything that is H W-sized.
+#define SVBRDF_PHOTO_POSE_SHARED_ONLY
+#include "svbrdf_photo_pose.hip"
+#define SVBRDF_PHOTO_FIT_SHARED_ONLY
+#include "svbrdf_photo_fit.hip"
+
+namespace {
+
+template <bool WEIGHTED>
+__device__ __forceinline__ void joint_body(float *maps, float *exp_avg, float *exp_avg_sq, const float *__restrict__ photos,
+                                           const float *__restrict__ weights, int weight_planes,
+                                           const float *__restrict__ scenes, const float *__restrict__ xrow, float eps,
+                                           float inv_count, double loss_scale, float fixed_scale, double grad_scale,
+                                           float per_count, const AdamArgs &adam, float *grad_out,
+                                           float *__restrict__ grad_scenes, unsigned long long *__restrict__ ws,
+                                           float *__restrict__ loss_out, int S, int H, int W)
+{
+    float *sums = pose_lds();
+    const size_t plane = (size_t)H * W;
+    const int b = blockIdx.y;
+    const int n_sums = 9 * S;
+    const WaveIndex wi = wave_index(plane, kPoseSpill + n_sums);
+    float lsum = 0.0f;
+    if (!wi.wave_live) {
+        for (int i = threadIdx.x & 63; i < n_sums; i += 64) sums[wi.row + kPoseSpill + i] = 0.0f;     // a wave without pixels
+    } else {
+        {
+            // diffuse and roughness as stored, to LDS (fit_body; a lane without a pixel stashes the last pixel's, unread)
+            const PlaneBuf xb = plane_buf(maps + (size_t)b * 12 * plane, 12, plane, wi.pix);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) fit_stash(k, plane_load(xb, 3 + k), false);
+        }
+        PixelSetup ps = wave_pixel_setup<false, WEIGHTED>(maps, xrow, b, plane, wi.pix, W);
+        const float *__restrict__ scp = scenes + (size_t)b * n_sums;
+        const float *__restrict__ pp = photos + (size_t)b * S * 3 * plane;
+        const float *__restrict__ wp = WEIGHTED ? weights + (size_t)b * weight_planes * plane : nullptr;
+        const size_t wstride = weight_planes == 1 ? 0 : plane;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) expo_stash(k, ps.mi.r4m[k], false);
+        if (__builtin_amdgcn_readfirstlane((int)__all(ps.tied)))      // wave-uniform, and known to be
+            lsum = pose_scene_loop<1, WEIGHTED>(ps.mi, ps.x, ps.y, scp, pp, plane, wi.pix, S, eps, inv_count, ps.acc, wp,
+                                                wstride, ps.poison, wi.row, wi.live);
+        else
+            lsum = pose_scene_loop<3, WEIGHTED>(ps.mi, ps.x, ps.y, scp, pp, plane, wi.pix, S, eps, inv_count, ps.acc, wp,
+                                                wstride, ps.poison, wi.row, wi.live);
+        // the item's light colours, a lane each (pose_body)
+        for (int i = threadIdx.x & 63; i < 3 * S; i += 64) {
+            const float c = scp[(i / 3) * 9 + 6 + i % 3];
+            if (!(c > 0.0f && c < __builtin_inff())) lsum = __builtin_nanf("");
+        }
+        if (wi.live) {
+            if (grad_out) store_grads_k3(grad_out + (size_t)b * 12 * plane, plane, wi.pix, ps.acc);
+            // fit_body's epilogue, for the lanes that own a pixel ONLY
+            const PlaneBuf xb = plane_buf(maps + (size_t)b * 12 * plane, 12, plane, wi.pix);
+            const PlaneBuf mb = plane_buf(exp_avg + (size_t)b * 12 * plane, 12, plane, wi.pix);
+            const PlaneBuf vb = plane_buf(exp_avg_sq + (size_t)b * 12 * plane, 12, plane, wi.pix);
+            float m[12], v[12], x[12], g[12];
+            __builtin_amdgcn_sched_barrier(0);      // the three resources stand: the 24 state loads back to back
+#pragma unroll
+            for (int k = 0; k < 12; ++k) m[k] = plane_load(mb, k);
+#pragma unroll
+            for (int k = 0; k < 12; ++k) v[k] = plane_load(vb, k);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                x[0 + k] = ps.mi.n[k];
+                x[3 + k] = fit_stash(k, 0.0f, true);
+                x[6 + k] = fit_stash(3 + k, 0.0f, true);
+                x[9 + k] = ps.mi.s[k];
+                g[0 + k] = ps.acc.n[k];
+                g[3 + k] = ps.acc.d[k];
+                g[6 + k] = ps.acc.r[k];
+                g[9 + k] = ps.acc.s[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 12; ++k) {
+                const float xn = adam_channel(adam, k, x[k], g[k], m[k], v[k]);
+                plane_store(xb, k, xn);
+                plane_store(mb, k, m[k]);
+                plane_store(vb, k, v[k]);
+            }
+        } else {
+            lsum -= lsum;       // +0; a NaN stays
+        }
+    }
+    photo_sums_finish<true>(
+        lsum, b, n_sums, fixed_scale, loss_scale, ws, loss_out,
+        [&](int i, bool &sane) {        // the waves' floats, each checked against kPoseWaveLimit, to fixed point (pose_body)
+            long long sum = 0;
+#pragma unroll
+            for (int w = 0; w < kPoseWaves; ++w) {
+                const float v = sums[w * (kPoseSpill + n_sums) + kPoseSpill + i] * per_count;
+                const bool ok = fabsf(v) <= kPoseWaveLimit;         // false for NaN
+                sane = sane && ok;
+                sum += ok ? (long long)v : 0LL;
+            }
+            return sum;
+        },
+        [&](int i, long long sum, bool nan) {
+            float gr = (float)((double)sum * grad_scale);
+            if (i % 9 >= 6) gr *= rcp_(scenes[i]);       // the colour columns hold sum(Q): d / d colour = Q / colour
+            grad_scenes[i] = nan ? __builtin_nanf("") : gr;
+        });
+}
+
+#define SVBRDF_JOINT_KERNEL(NAME, WEIGHTED)                                                                           \
+    __global__ SVBRDF_PHOTO_LOSS_ATTRS void NAME(float *maps, float *exp_avg, float *exp_avg_sq,                      \
+                                                 const float *__restrict__ photos, const float *__restrict__ weights, \
+                                                 int weight_planes, const float *__restrict__ scenes,                 \
+                                                 const float *__restrict__ xrow, float eps, float inv_count,          \
+                                                 double loss_scale, float fixed_scale, double grad_scale,             \
+                                                 float per_count, const AdamArgs adam, float *grad_out,               \
+                                                 float *__restrict__ grad_scenes, unsigned long long *__restrict__ ws, \
+                                                 float *__restrict__ loss_out, int S, int H, int W)                   \
+    {                                                                                                                 \
+        joint_body<WEIGHTED>(maps, exp_avg, exp_avg_sq, photos, weights, weight_planes, scenes, xrow, eps, inv_count, \
+                             loss_scale, fixed_scale, grad_scale, per_count, adam, grad_out, grad_scenes, ws,         \
+                             loss_out, S, H, W);                                                                      \
+    }
+// (names that hold none of the substrings the other photo and fit kernels are counted by)
+SVBRDF_JOINT_KERNEL(k_joint_fit, false)
+SVBRDF_JOINT_KERNEL(k_joint_fit_weighted, true)
+#undef SVBRDF_JOINT_KERNEL
+
+}  // namespace
+
+extern "C" {
+
+int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg, float *exp_avg_sq, const float *photos,
+                                          const float *weights, int weight_planes, const float *scenes, const float *xrow,
+                                          float eps, const float *bounds_host, float lr, float beta1, float beta2,
+                                          float adam_eps, int step, float *loss_out, float *grad_out, float *grad_scenes,
+                                          void *workspace, size_t workspace_bytes, int B, int S, int H, int W, void *stream)
+{
+    const char *who = "photo_fit_adam_step_scene_grad";
+    char text[200];
+    const auto bad = [&](int code, const char *what) {
+        std::snprintf(text, sizeof(text), "%s: %s", who, what);
+        return fail(code, text);
+    };
+    LossPlan p;
+    double units;       // N 2^24
+    // the scene-gradient entry's checks in its order (grad_out may be null and the kernels are forward + adjoint whatever
+    // it is: the plan is the one with a gradient), then the fit entry's
+    if (int e = plan_sums(who, {maps, exp_avg, exp_avg_sq, photos, grad_scenes, scenes, xrow, loss_out}, weights,
+                          weight_planes, nullptr, eps, grad_out ? grad_out : maps, workspace, workspace_bytes, 9, kPoseSpill,
+                          B, S, H, W, &p, &units)) return e;
+    // fit_stash's six words per thread stand beside the rows of sums: the workgroup's LDS stays inside what plan_sums
+    // allows the scene-gradient kernels (60 KB of rows), S <= 383
+    if (p.lds_bytes + 6 * kLossThreads * sizeof(float) > 60 * 1024)
+        return bad(SVBRDF_ERR_DIMS, "too many scenes per item for the LDS sums (max 383)");
+    AdamArgs a;
+    float sc[4];
+    if (!adam_scalars(lr, beta1, beta2, step, sc))
+        return bad(SVBRDF_ERR_DIMS, "step >= 1, a finite lr >= 0 and betas in [0, 1) are required");
+    if (!(adam_eps >= 0.0f) || !std::isfinite(adam_eps)) return bad(SVBRDF_ERR_DIMS, "adam_eps must be finite and >= 0");
+    a.beta1 = beta1; a.c1 = sc[0]; a.beta2 = beta2; a.c2 = sc[1]; a.step_size = sc[2]; a.rsb2 = sc[3]; a.adam_eps = adam_eps;
+    for (int k = 0; k < 12; ++k) {
+        a.lo[k] = bounds_host ? bounds_host[2 * k] : -__builtin_inff();
+        a.hi[k] = bounds_host ? bounds_host[2 * k + 1] : __builtin_inff();
+        if (!(a.lo[k] <= a.hi[k])) return bad(SVBRDF_ERR_DIMS, "bounds must hold lo <= hi for every channel, and no NaN");
+    }
+    hipLaunchKernelGGL(weights ? k_joint_fit_weighted : k_joint_fit, p.grid, dim3(kLossThreads), p.lds_bytes,
+                       static_cast<hipStream_t>(stream), maps, exp_avg, exp_avg_sq, photos, weights, weight_planes, scenes,
+                       xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, 1.0 / units, (float)units, a, grad_out,
+                       grad_scenes, p.ws, loss_out, S, H, W);
+    return launch_status(who);
+}
+
+}  // extern "C"

@@ -14,6 +14,10 @@
 // SVBRDF_TU = 4 as svbrdf_aux_f64.hip does: none of its kernels, none of its entry points.  A unit of its own so that K3's
 // machine code cannot move (tests/test_counter_replay_guard.py hashes it) and so that this kernel takes its own scheduler
 // option set (csrc/Makefile: SCHED_PHOTO).  Numerics contract as K3: -ffp-contract=off, the coords -> NH path exact.
+// (svbrdf_photo_fit_pose.hip includes svbrdf_photo_pose.hip and svbrdf_photo_fit.hip, and each of the two includes this
+// file: it arrives once)
+#ifndef SVBRDF_PHOTO_LOSS_HIP_INCLUDED
+#define SVBRDF_PHOTO_LOSS_HIP_INCLUDED
 #define SVBRDF_TU 4
 #include "svbrdf_kernels.hip"
 
@@ -1033,3 +1037,5 @@ int svbrdf_head_photo_loss_fwd_bwd_host_scenes(const float *encoded9, const floa
 
 }  // extern "C"
 #endif  // SVBRDF_PHOTO_SHARED_ONLY
+
+#endif  // SVBRDF_PHOTO_LOSS_HIP_INCLUDED

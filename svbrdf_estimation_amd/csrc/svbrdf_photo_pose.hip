@@ -187,6 +187,10 @@ __device__ __forceinline__ void pose_body(const float *__restrict__ input, const
         });
 }
 
+// svbrdf_photo_fit_pose.hip includes this file for the device code above only: its kernels, launcher and entry point are
+// its own
+#ifndef SVBRDF_PHOTO_POSE_SHARED_ONLY
+
 #define SVBRDF_POSE_KERNEL(NAME, HEAD, WEIGHTED)                                                                      \
     __global__ SVBRDF_PHOTO_LOSS_ATTRS void NAME(const float *__restrict__ input, const float *__restrict__ photos,   \
                                                  const float *__restrict__ weights, int weight_planes,                \
@@ -222,8 +226,11 @@ int pose_impl(const char *who, bool head, const float *input, const float *photo
     return launch_status(who);
 }
 
+#endif  // SVBRDF_PHOTO_POSE_SHARED_ONLY
+
 }  // namespace
 
+#ifndef SVBRDF_PHOTO_POSE_SHARED_ONLY
 extern "C" {
 
 size_t svbrdf_photo_scene_grad_workspace_bytes(int B, int S, int H, int W)
@@ -250,3 +257,4 @@ int svbrdf_head_photo_loss_scene_grad_fwd_bwd(const float *encoded9, const float
 }
 
 }  // extern "C"
+#endif  // SVBRDF_PHOTO_POSE_SHARED_ONLY

@@ -12,6 +12,11 @@ gradient never written.
 ``PhotoFit.steps(n, ...)`` runs n consecutive steps on the same photographs in ceil(n / 64) launches, maps and state kept
 on chip between the steps, bit for bit the n single steps.
 
+``PhotoFit.step`` also refines what a real capture leaves unknown: with a scene table that requires grad and / or an
+``exposure=`` that does, the same ONE launch returns ``d loss / d (camera, light position, light colour)`` as well
+(csrc/svbrdf_photo_fit_pose.hip) and the loss it returns carries it to autograd -- towards the table and the gains only,
+never towards the maps, which the launch has already updated.
+
 ``composed_step`` is the same step in stock torch ops and the specification of the fused one.
 """
 import ctypes
@@ -54,8 +59,33 @@ def _check_bounds(bounds):
     return b
 
 
+def _wants_grad(scenes, exposure):
+    """a step's loss is differentiable: grad mode is on and the scene table (a tensor) or the exposure requires grad"""
+    return torch.is_grad_enabled() and ((isinstance(scenes, torch.Tensor) and scenes.requires_grad)
+                                        or (exposure is not None and exposure.requires_grad))
+
+
+class _StepLoss(torch.autograd.Function):
+    """The loss of a step that has ALREADY updated the maps, differentiable towards ``inputs`` (the scene table, the
+    exposure) and towards nothing else.  ``forward`` makes the step -- ``run()`` -> (0-dim loss, d loss / d input for
+    every input, or None) -- so maps and state are updated when it returns, and keeps the gradients; ``backward`` returns
+    ``grad_loss * gradient``.  The gradients are those at the maps BEFORE the update: what ``loss.backward();
+    opt_maps.step(); opt_pose.step()`` gives in the composed loop.  Once differentiable: a double backward raises."""
+
+    @staticmethod
+    def forward(ctx, run, *inputs):
+        loss, grads = run()
+        ctx.save_for_backward(*grads)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        return (None,) + tuple(None if g is None else (grad_loss * g).to(g.dtype) for g in ctx.saved_tensors)
+
+
 def composed_step(maps, exp_avg, exp_avg_sq, step, photos, scenes, weights=None, lr=1e-2, betas=(0.9, 0.999), eps=1e-8,
-                  bounds=None, loss_eps=0.1, renderer=None):
+                  bounds=None, loss_eps=0.1, renderer=None, exposure=None):
     """One step of the fit in stock torch ops -- THE SPECIFICATION of ``PhotoFit.step``: the gradient g of
     ``losses.PhotoLoss(renderer, loss_eps)(maps, photos, scenes, weights)``, then per element, each operation rounded in
     the maps' dtype,
@@ -68,14 +98,33 @@ def composed_step(maps, exp_avg, exp_avg_sq, step, photos, scenes, weights=None,
 
     with ``adam_scalars(lr, *betas, step)``.  ``maps``, ``exp_avg``, ``exp_avg_sq`` are updated in place; ``step`` is
     Adam's t of this update (1 for the first).  Serves float64 maps, CPU tensors and plugin renderers too -- whatever
-    ``PhotoLoss`` serves.  -> the 0-dim loss at the maps before the update."""
+    ``PhotoLoss`` serves.  ``exposure``: PhotoLoss's per-photo gains.  -> the 0-dim loss at the maps before the update.
+
+    With grad mode on and a ``scenes`` tensor or an ``exposure`` that requires grad, the returned loss carries its graph
+    towards them -- ``d loss / d scenes`` and ``d loss / d exposure`` at the maps before the update, as ``PhotoLoss``
+    defines them -- and not towards the maps; otherwise it is detached."""
     _check_hyper(lr, betas, eps)
     bounds = _check_bounds(bounds)
     fn = losses.PhotoLoss(renderer if renderer is not None else renderers.LocalRenderer(), loss_eps)
+    wanted = []
+    if _wants_grad(scenes, exposure):
+        wanted = [t for t in (scenes, exposure) if isinstance(t, torch.Tensor) and t.requires_grad]
+    update = lambda: _composed_update(fn, maps, exp_avg, exp_avg_sq, step, photos, scenes, weights, exposure, lr, betas, eps,
+                                      bounds, wanted)
+    return _StepLoss.apply(update, *wanted) if wanted else update()[0]
+
+
+def _composed_update(fn, maps, exp_avg, exp_avg_sq, step, photos, scenes, weights, exposure, lr, betas, eps, bounds, wanted):
+    """composed_step's body -> (the detached loss, d loss / d t for every t of ``wanted``, None where no gradient reaches
+    t).  With nothing wanted the table and the gains are constants, whatever requires grad."""
     x = maps.detach().clone().requires_grad_(True)
+    if not wanted:
+        scenes = scenes.detach() if isinstance(scenes, torch.Tensor) else scenes
+        exposure = None if exposure is None else exposure.detach()
     with torch.enable_grad():
-        loss = fn(x, photos, scenes, weights)
-        g, = torch.autograd.grad(loss, x)
+        loss = fn(x, photos, scenes, weights, exposure)
+        # (a plugin renderer works with scene objects: no gradient reaches the table, as in PhotoLoss)
+        g, *grads = torch.autograd.grad(loss, [x] + wanted, allow_unused=True)
     c1, c2, step_size, rsb2 = adam_scalars(lr, betas[0], betas[1], step, maps.dtype)
     with torch.no_grad():
         m = exp_avg.mul_(betas[0]).add_(g * c1)
@@ -88,7 +137,7 @@ def composed_step(maps, exp_avg, exp_avg_sq, step, photos, scenes, weights=None,
             xn = torch.where(xn < lo, lo, xn)        # false for NaN: it stays
             xn = torch.where(xn > hi, hi, xn)
         maps.copy_(xn)
-    return loss.detach()
+    return loss.detach(), tuple(None if t is None else t.detach() for t in grads)
 
 
 class PhotoFit:
@@ -108,8 +157,9 @@ class PhotoFit:
     the dict ``Adam.state[p]`` would be (the counter has no attribute of its own: ``step`` is the method).
 
     float32 maps on a ROCm device with ``LocalRenderer``: ``step`` is ONE fused kernel
-    (svbrdf_photo_fit_adam_step).  Anything else -- float64 maps, CPU tensors, a plugin renderer -- is ``composed_step``,
-    the specification of the fused step."""
+    (svbrdf_photo_fit_adam_step; svbrdf_photo_fit_adam_step_scene_grad when the scene table or the exposure wants a
+    gradient, see ``step``).  Anything else -- float64 maps, CPU tensors, a plugin renderer -- is ``composed_step``, the
+    specification of the fused step."""
 
     def __init__(self, maps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, bounds=None, loss_eps=0.1, renderer=None):
         if not isinstance(maps, torch.Tensor) or maps.dim() != 4 or maps.shape[1] != 12 or not maps.dtype.is_floating_point:
@@ -140,47 +190,90 @@ class PhotoFit:
         return (losses.PhotoLoss(self.renderer).uses_fused_kernel() and self.maps.is_cuda
                 and self.maps.dtype == torch.float32)
 
-    def step(self, photos, scenes, weights=None):
-        """One update from ``photos`` [B,S,3,H,W] (or [B,3,H,W]), ``scenes`` and optional ``weights`` as
-        ``losses.PhotoLoss`` takes them -> the 0-dim loss at the maps before the update."""
+    def step(self, photos, scenes, weights=None, exposure=None):
+        """One update from ``photos`` [B,S,3,H,W] (or [B,3,H,W]), ``scenes``, optional ``weights`` and optional ``exposure``
+        (a positive gain per photo and colour channel) as ``losses.PhotoLoss`` takes them -> the 0-dim loss at the maps
+        before the update.
+
+        The light, the camera and the gains are refined WITH the maps: with grad mode on and ``scenes`` a float32
+        ``[B,S,9]`` tensor that requires grad (PhotoLoss's signal) and / or an ``exposure`` that requires grad, the returned
+        loss is attached to autograd towards ``scenes`` and ``exposure`` -- never towards the maps, which are already
+        updated when ``step`` returns -- and ``loss.backward()`` deposits ``d loss / d scenes`` (camera xyz | light xyz |
+        light rgb) at the maps BEFORE the update, once differentiable.  Still ONE launch on the fused path
+        (svbrdf_photo_fit_adam_step_scene_grad); the gains multiply the table's colour columns with torch ops in front of
+        it, and autograd chains the colour gradient back to them, through ``log_e.exp()`` too.  The update of the table and
+        of the gains is the caller's: a stock ``torch.optim`` over a few hundred floats.
+
+        With nothing that requires grad, or under ``torch.no_grad()``, it is the step without a table gradient: one launch
+        of svbrdf_photo_fit_adam_step, a loss that does not require grad, a given ``exposure`` multiplied in as a
+        constant."""
         x = self.maps.detach()
         t = int(self.state["step"]) + 1
-        if not self.uses_fused_kernel():
+        if not self.uses_fused_kernel() or (isinstance(exposure, torch.Tensor) and exposure.dtype == torch.float64):
             loss = composed_step(x, self.exp_avg, self.exp_avg_sq, t, photos, scenes, weights, self.lr, self.betas, self.eps,
-                                 self._bounds, self.loss_eps, self.renderer)
+                                 self._bounds, self.loss_eps, self.renderer, exposure)
         else:
             photos = losses.PhotoLoss._check(x, photos)
             weights = losses._check_weights(weights, x, photos)
+            exposure = losses._check_exposure(exposure, x, photos)
             table = losses.PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
-            loss, _ = _native.photo_fit_adam_step(x, self.exp_avg, self.exp_avg_sq, photos, table.detach(), t, self.lr,
-                                                  self.betas, self.eps, self._bounds_c, self.loss_eps, weights)
-            loss = loss.view(())
+            want = _wants_grad(table, exposure)
+            if not want:
+                table = table.detach()
+                exposure = None if exposure is None else exposure.detach()
+            if want or exposure is not None:
+                # the kernels take a device table and no exposure: the gains multiply the colour columns in front of them
+                # (_PhotoLossModule._forward), and autograd chains the table's gradient back through both
+                table = table.to(x.device)
+                if exposure is not None:
+                    table = torch.cat((table[..., :6], table[..., 6:] * exposure), dim=-1)
+            args = (x, self.exp_avg, self.exp_avg_sq, photos)
+            rest = (t, self.lr, self.betas, self.eps, self._bounds_c, self.loss_eps, weights)
+
+            def joint():
+                loss, _, grad_scenes = _native.photo_fit_adam_step(*args, table.detach(), *rest, want_scene_grad=True)
+                return loss.view(()), (grad_scenes,)
+
+            if want:
+                loss = _StepLoss.apply(joint, table)
+            else:
+                loss = _native.photo_fit_adam_step(*args, table, *rest)[0].view(())
         self.state["step"] = t
         return loss
 
-    def steps(self, n, photos, scenes, weights=None):
+    def steps(self, n, photos, scenes, weights=None, exposure=None):
         """``n`` consecutive updates from the same ``photos``, ``scenes`` and ``weights`` -> a ``[n]`` device tensor of the
         losses at the maps before each update; no host synchronisation.  Maps, state and losses are those of ``n`` calls
         of ``step`` -- on the fused path bit for bit, in ceil(n / 64) launches (svbrdf_photo_fit_adam_steps: the thread
         that owns a pixel runs the steps on it with maps and state kept on chip; csrc/svbrdf_photo_fit.hip).  ``lr``,
         ``betas``, ``eps`` and ``bounds`` are read once per call; ``state["step"]`` advances by ``n``.  Anything but float32
-        maps on a ROCm device with ``LocalRenderer`` is ``n`` times ``composed_step``."""
+        maps on a ROCm device with ``LocalRenderer`` is ``n`` times ``composed_step``.
+
+        Maps only: the table and the ``exposure`` gains are CONSTANTS of the n steps, whatever requires grad, and the losses
+        returned are never differentiable.  The table's gradient is a sum over all pixels of an item; applying it between
+        two steps of one launch would need a grid barrier (csrc/svbrdf_photo_fit_pose.hip).  To refine the table, call
+        ``step`` in a loop."""
         n = int(n)
         if n < 1:
             raise ValueError("n must be >= 1, got %r" % (n,))
         x = self.maps.detach()
         lr, betas, eps, bounds, bounds_c = self.lr, self.betas, self.eps, self._bounds, self._bounds_c
         t = int(self.state["step"]) + 1
-        if not self.uses_fused_kernel():
+        if not self.uses_fused_kernel() or (isinstance(exposure, torch.Tensor) and exposure.dtype == torch.float64):
             seen = []
-            for k in range(n):
-                seen.append(composed_step(x, self.exp_avg, self.exp_avg_sq, t + k, photos, scenes, weights, lr, betas, eps,
-                                          bounds, self.loss_eps, self.renderer))
-                self.state["step"] = t + k
+            with torch.no_grad():
+                for k in range(n):
+                    seen.append(composed_step(x, self.exp_avg, self.exp_avg_sq, t + k, photos, scenes, weights, lr, betas,
+                                              eps, bounds, self.loss_eps, self.renderer, exposure))
+                    self.state["step"] = t + k
             return torch.stack(seen)
         photos = losses.PhotoLoss._check(x, photos)
         weights = losses._check_weights(weights, x, photos)
+        exposure = losses._check_exposure(exposure, x, photos)
         table = losses.PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1]).detach()
+        if exposure is not None:
+            table = table.to(x.device)
+            table = torch.cat((table[..., :6], table[..., 6:] * exposure.detach()), dim=-1)
         out = []
         for first in range(0, n, _native.PHOTO_FIT_MAX_STEPS):
             k = min(_native.PHOTO_FIT_MAX_STEPS, n - first)

@@ -19,14 +19,18 @@ gains under ``--fit-exposure`` -- through the table's gradient, which comes out 
 |position - truth| is printed beside the maps' error.  The positions take their own learning rate, ``--pose-lr``.
 
 ``--fused-step``: the whole step -- loss, gradient, Adam update of the maps and the clamp of diffuse, roughness and specular
-to [0, 1] -- is ONE launch (``fitting.PhotoFit``: the gradient is never written, ``torch.optim.Adam`` is not used).  Only the
-maps have a fused update: refused with ``--fit-exposure`` or ``--fit-pose``, whose joint fits stay on the path above.
+to [0, 1] -- is ONE launch (``fitting.PhotoFit``: the gradient is never written, ``torch.optim.Adam`` is not used for the
+maps).  With ``--fit-pose`` and / or ``--fit-exposure`` the same one launch also returns the gradient towards the scene
+table (``fit.step(photos, cat(pos, colour), None, exposure=log_e.exp())``): ``loss.backward()`` hands it to the positions and,
+through the colour columns, to ``log e``, and a small Adam over those few hundred floats follows (``--pose-lr`` as above).
 
 ``--steps-per-launch K`` (only with ``--fused-step``): K consecutive steps per launch (``fitting.PhotoFit.steps``: the thread
 that owns a pixel runs them with maps and state kept on chip, read from memory once and written once per launch; ceil(K / 64)
 launches).  Maps and losses are bit for bit those of K single-step launches.  The losses of every ``--print-every``-th step
 are printed from the returned tensor -- the maps' error only where a launch ends, the maps in between never reach memory --
-and the time per step is the time of a launch divided by its steps.
+and the time per step is the time of a launch divided by its steps.  Maps only: refused with ``--fit-pose`` or
+``--fit-exposure`` -- the table's gradient sums over all pixels, and applying it between two steps of one launch would need a
+grid barrier.
 """
 import argparse
 import os
@@ -64,8 +68,9 @@ def main():
         ap.error("--steps-per-launch needs --fused-step: only the fused step runs several steps in a launch")
     if args.steps_per_launch is not None and args.steps_per_launch < 1:
         ap.error("--steps-per-launch must be >= 1")
-    if args.fused_step and (args.fit_exposure or args.fit_pose):
-        ap.error("--fused-step updates the maps only: not combined with --fit-exposure or --fit-pose")
+    if args.steps_per_launch is not None and (args.fit_exposure or args.fit_pose):
+        ap.error("--steps-per-launch updates the maps only: positions and gains would have to be updated between the steps of "
+                 "a launch, from a gradient summed over all pixels (a grid barrier) -- use --fused-step without it")
     assert torch.cuda.is_available(), "needs a ROCm device"
     dev = torch.device("cuda:0")
     B, H, S = args.batch, args.size, args.photos
@@ -98,6 +103,9 @@ def main():
     if args.fused_step:
         inf = float("inf")
         fit = fitting.PhotoFit(x.detach(), lr=args.lr, bounds=[[-inf, inf]] * 3 + [[0.0, 1.0]] * 9)
+        # the maps are the fused step's; what is left for torch.optim is the few hundred floats of gains and positions
+        groups = ([] if log_e is None else [{"params": [log_e]}]) + ([] if pos is None else [{"params": [pos], "lr": args.pose_lr}])
+        opt = torch.optim.Adam(groups, lr=args.lr) if groups else None
     print("fitting %d x [12,%d,%d] maps to %d photographs each (%s%s%s), Adam lr %g%s" % (
         B, H, H, S, "sensor noise" if args.noise else "noise-free", ", hidden gains fitted too" if args.fit_exposure else "",
         ", positions fitted too (lr %g)" % args.pose_lr if args.fit_pose else "", args.lr,
@@ -112,8 +120,14 @@ def main():
             if t_last is not None:
                 step_ms.append(1e3 * (now - t_last) / args.print_every)
             t_last = now
-        if fit is not None:
+        if fit is not None and opt is None:
             loss = fit.step(photos, table)
+        elif fit is not None:
+            opt.zero_grad(set_to_none=True)
+            scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
+            loss = fit.step(photos, scenes, None, exposure=None if log_e is None else log_e.exp())
+            loss.backward()
+            opt.step()
         else:
             opt.zero_grad(set_to_none=True)
             scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
