@@ -458,23 +458,26 @@ def render_bwd_ragged(maps, scenes, counts, grad_out):
 
 
 def _fused_loss_call(entry, input, other, scenes, floats, want_grad, B, S, H, W, extra=(), more_grads=(),
-                     workspace_bytes="svbrdf_rendering_loss_workspace_bytes"):
+                     workspace_bytes="svbrdf_rendering_loss_workspace_bytes", n_losses=1, workspace_lead=()):
     """One launch of the fused-loss entry point `entry`: contiguous device tensors `input` and `other` (target maps or
     photos), the scene table as _scene_table returned it, `floats` = eps (and l1_weight, eps_l1 for the entries that take
     them), `extra` = what the entry takes between `other` and the scene table (the weighted photo entries: weights
     pointer, plane count; the exposure entries: the exposure pointer behind them), `more_grads` = the output pointers it
     takes behind the gradient (the exposure entries: grad_exposure), `workspace_bytes` = the library function that sizes
-    its scratch.  -> (loss [1] device tensor, grad like `input` or None)"""
-    ws = _workspace(input.device, getattr(_load(), workspace_bytes)(B, S, H, W))
-    loss = torch.empty(1, dtype=torch.float32, device=input.device)
+    its scratch, `workspace_lead` = what that function takes in front of B, S, H, W (the steps entry: n_steps), `n_losses` =
+    the length of the loss tensor (the steps entry: one per step).  `want_grad` None: the entry takes no gradient pointer.
+    -> (loss [n_losses] device tensor, grad like `input` or None)"""
+    ws = _workspace(input.device, getattr(_load(), workspace_bytes)(*workspace_lead, B, S, H, W))
+    loss = torch.empty(n_losses, dtype=torch.float32, device=input.device)
     grad = torch.empty_like(input) if want_grad else None
+    grad_ptr = () if want_grad is None else (grad.data_ptr() if want_grad else None,)
     xr = xrow(input.device, W)
     hook = _launch_hook
     if hook is not None:
         hook("begin")
     try:
         _call(entry, input.device, input.data_ptr(), other.data_ptr(), *extra, scenes.data_ptr(), xr.data_ptr(), *floats,
-              loss.data_ptr(), grad.data_ptr() if want_grad else None, *more_grads, ws.data_ptr(), ws.numel() * 8, B, S, H, W)
+              loss.data_ptr(), *grad_ptr, *more_grads, ws.data_ptr(), ws.numel() * 8, B, S, H, W)
     except NativeLibraryError:
         # a failed launch may leave partial sums / arrival counts behind: the scratch contract ("every completed
         # call leaves it zeroed") only covers completed calls, so restore it before reporting the error
@@ -515,6 +518,18 @@ def rendering_loss(input, target, scenes, eps=0.1, want_grad=True, l1_weight=0.0
     return _fused_loss_call(entry, input.contiguous(), target.contiguous(), scenes, floats, want_grad, B, S, H, W)
 
 
+def _checked_weights(weights, device, B, S, H, W):
+    """per-pixel weights of a photo entry, float32 [B,S,H,W] or [B,1,H,W] on `device` -> contiguous (the caller keeps the
+    result alive until the launch is enqueued, stream-ordered)"""
+    _require_device_f32(weights, "weights")
+    if weights.device != device:
+        raise ValueError("input, photos and weights must be on the same device")
+    if tuple(weights.shape) not in ((B, S, H, W), (B, 1, H, W)):
+        raise ValueError("weights must be [B,S,H,W] = %s or [B,1,H,W] for these maps and photos, got %s"
+                         % ((B, S, H, W), tuple(weights.shape)))
+    return weights.contiguous()
+
+
 def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weights=None, exposure=None,
                want_exposure_grad=False, want_scene_grad=False):
     """Fused photo loss (svbrdf_photo_loss_fwd_bwd*): mean |log(render(scenes[b,s], input[b]) + eps) - log(photos[b,s] + eps)|
@@ -550,13 +565,7 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
     stem = "svbrdf_head_photo_loss" if head else "svbrdf_photo_loss"
     extra = ()
     if weights is not None:
-        _require_device_f32(weights, "weights")
-        if weights.device != input.device:
-            raise ValueError("input, photos and weights must be on the same device")
-        if tuple(weights.shape) not in ((B, S, H, W), (B, 1, H, W)):
-            raise ValueError("weights must be [B,S,H,W] = %s or [B,1,H,W] for these maps and photos, got %s"
-                             % ((B, S, H, W), tuple(weights.shape)))
-        weights = weights.contiguous()      # (kept alive by this frame until the launch is enqueued, stream-ordered)
+        weights = _checked_weights(weights, input.device, B, S, H, W)
         stem, extra = stem + "_weighted", (weights.data_ptr(), int(weights.shape[1]))
     if exposure is not None:
         _require_device_f32(exposure, "exposure")
@@ -598,6 +607,37 @@ def photo_fit_adam_scalars(lr, beta1, beta2, step):
     return tuple(out)
 
 
+def _fit_operands(maps, exp_avg, exp_avg_sq, photos, scenes, weights):
+    """The operands of a fit entry, checked: maps and state contiguous float32 [B,12,H,W] device tensors (updated in place);
+    photos, scenes, weights as photo_loss takes them; a host table is uploaded (the entries take a device table).
+    -> (the device table, (B, S, H, W), `extra`: what the entries take between exp_avg and the table, `keep`: the tensors
+    behind extra's pointers, for the caller's frame to hold until the launch is enqueued)"""
+    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (photos, "photos")):
+        _require_device_f32(t, name)
+    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        if not t.is_contiguous() or t.shape != maps.shape or t.device != maps.device:
+            raise ValueError("%s is updated in place: a contiguous tensor of the maps' shape on their device" % name)
+    if photos.device != maps.device:
+        raise ValueError("input, photos and scenes must be on the same device")
+    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, maps, scenes)[:6]
+    if on_host:
+        scenes = upload_scene_table(scenes, maps.device)
+    if tuple(photos.shape) != (B, S, 3, H, W):
+        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
+                         % ((B, S, 3, H, W), tuple(photos.shape)))
+    if weights is not None:
+        weights = _checked_weights(weights, maps.device, B, S, H, W)
+    photos = photos.contiguous()
+    planes = (None, 0) if weights is None else (weights.data_ptr(), int(weights.shape[1]))
+    return scenes, (B, S, H, W), (exp_avg_sq.data_ptr(), photos.data_ptr()) + planes, (photos, weights)
+
+
+def _adam_floats(eps, bounds, lr, betas, adam_eps, step):
+    """what the fit entries take between xrow and the loss pointer, up to Adam's t"""
+    return (ctypes.c_float(eps), None if bounds is None else ctypes.cast(bounds, _fp), ctypes.c_float(lr),
+            ctypes.c_float(betas[0]), ctypes.c_float(betas[1]), ctypes.c_float(adam_eps), int(step))
+
+
 def photo_fit_adam_step(maps, exp_avg, exp_avg_sq, photos, scenes, step, lr=1e-2, betas=(0.9, 0.999), adam_eps=1e-8,
                         bounds=None, eps=0.1, weights=None, want_grad=False, want_scene_grad=False):
     """One step of a photo fit (svbrdf_photo_fit_adam_step): the (weighted) photo loss at `maps`, its gradient and the Adam
@@ -611,40 +651,14 @@ def photo_fit_adam_step(maps, exp_avg, exp_avg_sq, photos, scenes, step, lr=1e-2
     -> (loss, grad or None, grad_scenes [B,S,9]): d loss / d scenes at the maps before the update, camera xyz | light xyz |
     light rgb, as photo_loss(want_scene_grad=True) returns it bit for bit.  A NaN loss comes with an all-NaN grad_scenes;
     the maps are updated whatever the loss is."""
-    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (photos, "photos")):
-        _require_device_f32(t, name)
-    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        if not t.is_contiguous() or t.shape != maps.shape or t.device != maps.device:
-            raise ValueError("%s is updated in place: a contiguous tensor of the maps' shape on their device" % name)
-    if photos.device != maps.device:
-        raise ValueError("input, photos and scenes must be on the same device")
-    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, maps, scenes)[:6]
-    if on_host:
-        scenes = upload_scene_table(scenes, maps.device)
-    if tuple(photos.shape) != (B, S, 3, H, W):
-        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
-                         % ((B, S, 3, H, W), tuple(photos.shape)))
-    extra = (None, 0)
-    if weights is not None:
-        _require_device_f32(weights, "weights")
-        if weights.device != maps.device:
-            raise ValueError("input, photos and weights must be on the same device")
-        if tuple(weights.shape) not in ((B, S, H, W), (B, 1, H, W)):
-            raise ValueError("weights must be [B,S,H,W] = %s or [B,1,H,W] for these maps and photos, got %s"
-                             % ((B, S, H, W), tuple(weights.shape)))
-        weights = weights.contiguous()
-        extra = (weights.data_ptr(), int(weights.shape[1]))
-    photos = photos.contiguous()
-    floats = (ctypes.c_float(eps), None if bounds is None else ctypes.cast(bounds, _fp), ctypes.c_float(lr),
-              ctypes.c_float(betas[0]), ctypes.c_float(betas[1]), ctypes.c_float(adam_eps), int(step))
+    scenes, dims, extra, keep = _fit_operands(maps, exp_avg, exp_avg_sq, photos, scenes, weights)
+    floats = _adam_floats(eps, bounds, lr, betas, adam_eps, step)
     if want_scene_grad:
         grad_scenes = torch.empty_like(scenes)
-        loss, grad = _fused_loss_call("svbrdf_photo_fit_adam_step_scene_grad", maps, exp_avg, scenes, floats, want_grad, B, S,
-                                      H, W, (exp_avg_sq.data_ptr(), photos.data_ptr()) + extra, (grad_scenes.data_ptr(),),
-                                      "svbrdf_photo_scene_grad_workspace_bytes")
+        loss, grad = _fused_loss_call("svbrdf_photo_fit_adam_step_scene_grad", maps, exp_avg, scenes, floats, want_grad, *dims,
+                                      extra, (grad_scenes.data_ptr(),), "svbrdf_photo_scene_grad_workspace_bytes")
         return loss, grad, grad_scenes
-    return _fused_loss_call("svbrdf_photo_fit_adam_step", maps, exp_avg, scenes, floats, want_grad, B, S, H, W,
-                            (exp_avg_sq.data_ptr(), photos.data_ptr()) + extra)
+    return _fused_loss_call("svbrdf_photo_fit_adam_step", maps, exp_avg, scenes, floats, want_grad, *dims, extra)
 
 
 PHOTO_FIT_MAX_STEPS = 64        # SVBRDF_PHOTO_FIT_MAX_STEPS of include/svbrdf_hip.h
@@ -658,50 +672,12 @@ def photo_fit_adam_steps(maps, exp_avg, exp_avg_sq, photos, scenes, first_step, 
     before each update.  No gradient is returned."""
     if not 1 <= int(n_steps) <= PHOTO_FIT_MAX_STEPS:
         raise ValueError("n_steps must lie in [1, %d], got %r" % (PHOTO_FIT_MAX_STEPS, n_steps))
-    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (photos, "photos")):
-        _require_device_f32(t, name)
-    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        if not t.is_contiguous() or t.shape != maps.shape or t.device != maps.device:
-            raise ValueError("%s is updated in place: a contiguous tensor of the maps' shape on their device" % name)
-    if photos.device != maps.device:
-        raise ValueError("input, photos and scenes must be on the same device")
-    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, maps, scenes)[:6]
-    if on_host:
-        scenes = upload_scene_table(scenes, maps.device)
-    if tuple(photos.shape) != (B, S, 3, H, W):
-        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
-                         % ((B, S, 3, H, W), tuple(photos.shape)))
-    extra = (None, 0)
-    if weights is not None:
-        _require_device_f32(weights, "weights")
-        if weights.device != maps.device:
-            raise ValueError("input, photos and weights must be on the same device")
-        if tuple(weights.shape) not in ((B, S, H, W), (B, 1, H, W)):
-            raise ValueError("weights must be [B,S,H,W] = %s or [B,1,H,W] for these maps and photos, got %s"
-                             % ((B, S, H, W), tuple(weights.shape)))
-        weights = weights.contiguous()
-        extra = (weights.data_ptr(), int(weights.shape[1]))
-    photos = photos.contiguous()
     n_steps = int(n_steps)
-    ws = _workspace(maps.device, _load().svbrdf_photo_fit_steps_workspace_bytes(n_steps, B, S, H, W))
-    losses = torch.empty(n_steps, dtype=torch.float32, device=maps.device)
-    xr = xrow(maps.device, W)
-    hook = _launch_hook
-    if hook is not None:
-        hook("begin")
-    try:
-        _call("svbrdf_photo_fit_adam_steps", maps.device, maps.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
-              photos.data_ptr(), *extra, scenes.data_ptr(), xr.data_ptr(), ctypes.c_float(eps),
-              None if bounds is None else ctypes.cast(bounds, _fp), ctypes.c_float(lr), ctypes.c_float(betas[0]),
-              ctypes.c_float(betas[1]), ctypes.c_float(adam_eps), int(first_step), n_steps, losses.data_ptr(), ws.data_ptr(),
-              ws.numel() * 8, B, S, H, W)
-    except NativeLibraryError:
-        ws.zero_()      # (as _fused_loss_call: only a completed call leaves the scratch zeroed)
-        raise
-    finally:
-        if hook is not None:
-            hook("end")
-    return losses
+    scenes, dims, extra, keep = _fit_operands(maps, exp_avg, exp_avg_sq, photos, scenes, weights)
+    floats = _adam_floats(eps, bounds, lr, betas, adam_eps, first_step) + (n_steps,)
+    return _fused_loss_call("svbrdf_photo_fit_adam_steps", maps, exp_avg, scenes, floats, None, *dims, extra,
+                            workspace_bytes="svbrdf_photo_fit_steps_workspace_bytes", n_losses=n_steps,
+                            workspace_lead=(n_steps,))[0]
 
 
 def mix_materials(svbrdf0, svbrdf1, alpha):

@@ -20,11 +20,14 @@
 // depend on how the compiler schedules it.  What differs:
 //   * the diffuse and roughness planes of the pixel as stored (the set-up keeps only what it derives from them; normal and
 //     specular survive in MapK as loaded) wait in LDS across the scene loop: the loop has no six registers to spare;
-//   * behind the loop, when the shading temporaries are dead: the 24 state loads back to back, the five lines above per
-//     channel -- every operation an individually rounded float32 one (this unit is built with -ffp-contract=off and the
-//     lines hold no fma), IEEE division and square root -- and 36 stores with the gradient stores' cache policy;
+//   * behind the loop, when the shading temporaries are dead (adam_epilogue, the one copy: the joint step of
+//     svbrdf_photo_fit_pose.hip calls it too): the 24 state loads back to back, the five lines above per channel -- every
+//     operation an individually rounded float32 one (this unit is built with -ffp-contract=off and the lines hold no
+//     fma), IEEE division and square root -- and 36 stores with the gradient stores' cache policy;
 //   * the clamp is two compares and selects: a NaN stays a NaN (v_max / v_min would return the bound), +-inf bounds never
 //     select.
+// The three fit entries -- this unit's two and the joint unit's -- check their weights and turn (bounds, lr, betas, adam_eps,
+// step) into AdamArgs through one helper each (fit_weights_check, adam_args) and report through fit_bad.
 #define SVBRDF_PHOTO_SHARED_ONLY
 #include "svbrdf_photo_loss.hip"
 
@@ -60,6 +63,42 @@ __device__ __forceinline__ float adam_channel(const AdamArgs &a, int ch, float x
     return xn;
 }
 
+// The single step's update of the pixel `pix` of item b, behind the scene loop: the 24 state loads back to back, the pixel's
+// 12 values (normal and specular from `mi` as loaded, diffuse and roughness from fit_stash) and its gradient `acc`,
+// adam_channel per channel, 36 stores.  The one copy: fit_body and joint_body (svbrdf_photo_fit_pose.hip) call it.
+__device__ __forceinline__ void adam_epilogue(float *maps, float *exp_avg, float *exp_avg_sq, int b, size_t plane, size_t pix,
+                                              const PixelSetup &ps, const AdamArgs &adam)
+{
+    const PlaneBuf xb = plane_buf(maps + (size_t)b * 12 * plane, 12, plane, pix);
+    const PlaneBuf mb = plane_buf(exp_avg + (size_t)b * 12 * plane, 12, plane, pix);
+    const PlaneBuf vb = plane_buf(exp_avg_sq + (size_t)b * 12 * plane, 12, plane, pix);
+    float m[12], v[12], x[12], g[12];
+    __builtin_amdgcn_sched_barrier(0);      // the three resources stand: the 24 state loads back to back
+#pragma unroll
+    for (int k = 0; k < 12; ++k) m[k] = plane_load(mb, k);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) v[k] = plane_load(vb, k);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        x[0 + k] = ps.mi.n[k];
+        x[3 + k] = fit_stash(k, 0.0f, true);
+        x[6 + k] = fit_stash(3 + k, 0.0f, true);
+        x[9 + k] = ps.mi.s[k];
+        g[0 + k] = ps.acc.n[k];
+        g[3 + k] = ps.acc.d[k];
+        g[6 + k] = ps.acc.r[k];
+        g[9 + k] = ps.acc.s[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const float xn = adam_channel(adam, k, x[k], g[k], m[k], v[k]);
+        plane_store(xb, k, xn);
+        plane_store(mb, k, m[k]);
+        plane_store(vb, k, v[k]);
+    }
+}
+
 // One thread = one pixel, all S renders of it and its 36 values of maps and state; workgroup = 256 pixels of one item, as
 // photo_loss_body<true, false, false, WEIGHTED>.
 template <bool WEIGHTED>
@@ -93,34 +132,7 @@ __device__ __forceinline__ void fit_body(float *maps, float *exp_avg, float *exp
             lsum = photo_scene_loop<3, true, 3, WEIGHTED>(ps.mi, ps.x, ps.y, scp, nullptr, pp, plane, pix, S, eps, inv_count,
                                                           ps.acc, wp, wstride, ps.poison);
         if (grad_out) store_grads_k3(grad_out + (size_t)b * 12 * plane, plane, pix, ps.acc);
-        const PlaneBuf xb = plane_buf(maps + (size_t)b * 12 * plane, 12, plane, pix);
-        const PlaneBuf mb = plane_buf(exp_avg + (size_t)b * 12 * plane, 12, plane, pix);
-        const PlaneBuf vb = plane_buf(exp_avg_sq + (size_t)b * 12 * plane, 12, plane, pix);
-        float m[12], v[12], x[12], g[12];
-        __builtin_amdgcn_sched_barrier(0);      // the three resources stand: the 24 state loads back to back
-#pragma unroll
-        for (int k = 0; k < 12; ++k) m[k] = plane_load(mb, k);
-#pragma unroll
-        for (int k = 0; k < 12; ++k) v[k] = plane_load(vb, k);
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            x[0 + k] = ps.mi.n[k];
-            x[3 + k] = fit_stash(k, 0.0f, true);
-            x[6 + k] = fit_stash(3 + k, 0.0f, true);
-            x[9 + k] = ps.mi.s[k];
-            g[0 + k] = ps.acc.n[k];
-            g[3 + k] = ps.acc.d[k];
-            g[6 + k] = ps.acc.r[k];
-            g[9 + k] = ps.acc.s[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 12; ++k) {
-            const float xn = adam_channel(adam, k, x[k], g[k], m[k], v[k]);
-            plane_store(xb, k, xn);
-            plane_store(mb, k, m[k]);
-            plane_store(vb, k, v[k]);
-        }
+        adam_epilogue(maps, exp_avg, exp_avg_sq, b, plane, pix, ps, adam);
     }
     {
         __shared__ float wave_part[kLossThreads / 64];
@@ -136,8 +148,8 @@ __device__ __forceinline__ void fit_body(float *maps, float *exp_avg, float *exp
     }
 }
 
-// svbrdf_photo_fit_pose.hip includes this file for AdamArgs, fit_stash, adam_channel and adam_scalars only: its kernels and
-// entry point are its own
+// svbrdf_photo_fit_pose.hip includes this file for AdamArgs, fit_stash, adam_epilogue and the host helpers behind the
+// kernels (adam_scalars, fit_bad, adam_args) only: its kernels and entry point are its own
 #ifndef SVBRDF_PHOTO_FIT_SHARED_ONLY
 
 #define SVBRDF_FIT_KERNEL(NAME, WEIGHTED)                                                                             \
@@ -173,6 +185,44 @@ bool adam_scalars(float lr, float beta1, float beta2, int step, float out[4])
     out[3] = (float)(1.0 / std::sqrt(1.0 - std::pow(b2, (double)step)));
     return true;
 }
+
+// What the three fit entries check and fill alike, each in its own order -> 0, or the error reported as "<who>: <what>"
+int fit_bad(const char *who, int code, const char *what)
+{
+    char text[200];
+    std::snprintf(text, sizeof(text), "%s: %s", who, what);
+    return fail(code, text);
+}
+
+// (the joint entry's weights are checked by plan_sums)
+[[maybe_unused]] int fit_weights_check(const char *who, const float *weights, int weight_planes, int S)
+{
+    if (!aligned(weights, 4)) return fit_bad(who, SVBRDF_ERR_ALIGN, "pointers must be 4-byte aligned");
+    if (weights ? (weight_planes != 1 && weight_planes != S) : weight_planes != 0)
+        return fit_bad(who, SVBRDF_ERR_DIMS,
+                       "weight_planes must be 1 (one plane per item) or S (one per photo) with weights, 0 without");
+    return 0;
+}
+
+// The update's arguments of Adam's step `step`: the scalars (`scalars_rule`: the entry's wording of what they require),
+// adam_eps, the seven scalars, then the 12 bounds -- +-inf without bounds_host
+int adam_args(const char *who, const char *scalars_rule, const float *bounds_host, float lr, float beta1, float beta2,
+              float adam_eps, int step, AdamArgs *a)
+{
+    float sc[4];
+    if (!adam_scalars(lr, beta1, beta2, step, sc)) return fit_bad(who, SVBRDF_ERR_DIMS, scalars_rule);
+    if (!(adam_eps >= 0.0f) || !std::isfinite(adam_eps))
+        return fit_bad(who, SVBRDF_ERR_DIMS, "adam_eps must be finite and >= 0");
+    a->beta1 = beta1; a->c1 = sc[0]; a->beta2 = beta2; a->c2 = sc[1]; a->step_size = sc[2]; a->rsb2 = sc[3]; a->adam_eps = adam_eps;
+    for (int k = 0; k < 12; ++k) {
+        a->lo[k] = bounds_host ? bounds_host[2 * k] : -__builtin_inff();
+        a->hi[k] = bounds_host ? bounds_host[2 * k + 1] : __builtin_inff();
+        if (!(a->lo[k] <= a->hi[k]))
+            return fit_bad(who, SVBRDF_ERR_DIMS, "bounds must hold lo <= hi for every channel, and no NaN");
+    }
+    return 0;
+}
+constexpr const char *kStepRule = "step >= 1, a finite lr >= 0 and betas in [0, 1) are required";
 
 // ---- Several steps in one launch (svbrdf_photo_fit_adam_steps).  The fit is pixel-local -- a pixel's loss term reads its
 // own 12 map values, Adam is element-wise, the loss sum is reported and never fed back -- so the thread that owns a pixel
@@ -392,29 +442,13 @@ int svbrdf_photo_fit_adam_step(float *maps, float *exp_avg, float *exp_avg_sq, c
                                int W, void *stream)
 {
     const char *who = "photo_fit_adam_step";
-    char text[200];
-    const auto bad = [&](int code, const char *what) {
-        std::snprintf(text, sizeof(text), "%s: %s", who, what);
-        return fail(code, text);
-    };
     LossPlan p;
     // (grad_out may be null and the kernels are forward + adjoint whatever it is: the plan is the one with a gradient)
     if (int e = plan_loss(who, false, {maps, exp_avg, exp_avg_sq, photos, scenes, xrow, loss_out}, grad_out ? grad_out : maps,
                           workspace, workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    if (!aligned(weights, 4)) return bad(SVBRDF_ERR_ALIGN, "pointers must be 4-byte aligned");
-    if (weights ? (weight_planes != 1 && weight_planes != S) : weight_planes != 0)
-        return bad(SVBRDF_ERR_DIMS, "weight_planes must be 1 (one plane per item) or S (one per photo) with weights, 0 without");
+    if (int e = fit_weights_check(who, weights, weight_planes, S)) return e;
     AdamArgs a;
-    float sc[4];
-    if (!adam_scalars(lr, beta1, beta2, step, sc))
-        return bad(SVBRDF_ERR_DIMS, "step >= 1, a finite lr >= 0 and betas in [0, 1) are required");
-    if (!(adam_eps >= 0.0f) || !std::isfinite(adam_eps)) return bad(SVBRDF_ERR_DIMS, "adam_eps must be finite and >= 0");
-    a.beta1 = beta1; a.c1 = sc[0]; a.beta2 = beta2; a.c2 = sc[1]; a.step_size = sc[2]; a.rsb2 = sc[3]; a.adam_eps = adam_eps;
-    for (int k = 0; k < 12; ++k) {
-        a.lo[k] = bounds_host ? bounds_host[2 * k] : -__builtin_inff();
-        a.hi[k] = bounds_host ? bounds_host[2 * k + 1] : __builtin_inff();
-        if (!(a.lo[k] <= a.hi[k])) return bad(SVBRDF_ERR_DIMS, "bounds must hold lo <= hi for every channel, and no NaN");
-    }
+    if (int e = adam_args(who, kStepRule, bounds_host, lr, beta1, beta2, adam_eps, step, &a)) return e;
     hipLaunchKernelGGL(weights ? k_fit_maps_weighted : k_fit_maps, p.grid, dim3(kLossThreads), 0,
                        static_cast<hipStream_t>(stream), maps, exp_avg, exp_avg_sq, photos, weights, weight_planes, scenes,
                        xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, a, grad_out, p.ws, loss_out, S, H, W);
@@ -434,39 +468,30 @@ int svbrdf_photo_fit_adam_steps(float *maps, float *exp_avg, float *exp_avg_sq, 
                                 int W, void *stream)
 {
     const char *who = "photo_fit_adam_steps";
-    char text[200];
-    const auto bad = [&](int code, const char *what) {
-        std::snprintf(text, sizeof(text), "%s: %s", who, what);
-        return fail(code, text);
-    };
+    const char *rule = "first_step >= 1, a finite lr >= 0 and betas in [0, 1) are required";
     LossPlan p;
     // the single step's checks in its order (a workspace below ONE step's 65 words fails here already)
     if (int e = plan_loss(who, false, {maps, exp_avg, exp_avg_sq, photos, scenes, xrow, losses_out}, maps, workspace,
                           workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    if (!aligned(weights, 4)) return bad(SVBRDF_ERR_ALIGN, "pointers must be 4-byte aligned");
-    if (weights ? (weight_planes != 1 && weight_planes != S) : weight_planes != 0)
-        return bad(SVBRDF_ERR_DIMS, "weight_planes must be 1 (one plane per item) or S (one per photo) with weights, 0 without");
+    if (int e = fit_weights_check(who, weights, weight_planes, S)) return e;
     if (n_steps < 1 || n_steps > SVBRDF_PHOTO_FIT_MAX_STEPS)
-        return bad(SVBRDF_ERR_DIMS, "n_steps must lie in [1, SVBRDF_PHOTO_FIT_MAX_STEPS]");
+        return fit_bad(who, SVBRDF_ERR_DIMS, "n_steps must lie in [1, SVBRDF_PHOTO_FIT_MAX_STEPS]");
     AdamArgs a;
     RunScalars run;
     float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int k = 0; k < SVBRDF_PHOTO_FIT_MAX_STEPS; ++k) {
         // (first_step + k cannot wrap where it is used: k < n_steps <= 64, and a first_step that close to INT_MAX is no fit's)
         if (k < n_steps && (first_step > 0x7fffffff - k || !adam_scalars(lr, beta1, beta2, first_step + k, sc)))
-            return bad(SVBRDF_ERR_DIMS, "first_step >= 1, a finite lr >= 0 and betas in [0, 1) are required");
+            return fit_bad(who, SVBRDF_ERR_DIMS, rule);
         run.step_size[k] = sc[2];       // (behind n_steps: the last step's, never read)
         run.rsb2[k] = sc[3];
     }
-    if (!(adam_eps >= 0.0f) || !std::isfinite(adam_eps)) return bad(SVBRDF_ERR_DIMS, "adam_eps must be finite and >= 0");
-    a.beta1 = beta1; a.c1 = sc[0]; a.beta2 = beta2; a.c2 = sc[1]; a.step_size = 0.0f; a.rsb2 = 0.0f; a.adam_eps = adam_eps;
-    for (int k = 0; k < 12; ++k) {
-        a.lo[k] = bounds_host ? bounds_host[2 * k] : -__builtin_inff();
-        a.hi[k] = bounds_host ? bounds_host[2 * k + 1] : __builtin_inff();
-        if (!(a.lo[k] <= a.hi[k])) return bad(SVBRDF_ERR_DIMS, "bounds must hold lo <= hi for every channel, and no NaN");
-    }
+    // everything that does not depend on t (the scalars of first_step passed above); the kernel takes the two that do from `run`
+    if (int e = adam_args(who, rule, bounds_host, lr, beta1, beta2, adam_eps, first_step, &a)) return e;
+    a.step_size = 0.0f;
+    a.rsb2 = 0.0f;
     if (workspace_bytes < svbrdf_photo_fit_steps_workspace_bytes(n_steps, B, S, H, W))
-        return bad(SVBRDF_ERR_WORKSPACE, "workspace too small for n_steps (svbrdf_photo_fit_steps_workspace_bytes)");
+        return fit_bad(who, SVBRDF_ERR_WORKSPACE, "workspace too small for n_steps (svbrdf_photo_fit_steps_workspace_bytes)");
     hipLaunchKernelGGL(weights ? k_fit_run_weighted : k_fit_run, p.grid, dim3(kLossThreads), 0,
                        static_cast<hipStream_t>(stream), maps, exp_avg, exp_avg_sq, photos, weights, weight_planes, scenes,
                        xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, a, run, n_steps, p.ws, losses_out, S, H, W);

@@ -15,10 +15,11 @@
 //     float sums in dynamic LDS, pose_scene_loop<1|3, WEIGHTED> chosen per wave, the colour check, photo_sums_finish<true>
 //     with the pose body's two lambdas.  loss_out, grad_out and grad_scenes are therefore bit for bit those of
 //     svbrdf_photo_loss_scene_grad_fwd_bwd -- the NaN rules included;
-//   * where the pose body stores the gradient of a live lane, the thread stores it if grad_out was given and then runs
-//     fit_body's epilogue: the 24 state loads back to back, adam_channel per channel, 36 stores with the gradient stores'
-//     cache policy.  Diffuse and roughness as stored wait in LDS across the loop (fit_stash) beside expo_stash's three
-//     words.  maps', exp_avg' and exp_avg_sq' are bit for bit svbrdf_photo_fit_adam_step's on the same gradient;
+//   * where the pose body stores the gradient of a live lane, the thread stores it if grad_out was given and then calls
+//     the fit unit's adam_epilogue, the function fit_body calls: the 24 state loads back to back, adam_channel per channel,
+//     36 stores with the gradient stores' cache policy.  Diffuse and roughness as stored wait in LDS across the loop
+//     (fit_stash) beside expo_stash's three words.  maps', exp_avg' and exp_avg_sq' are bit for bit
+//     svbrdf_photo_fit_adam_step's on the same gradient;
 //   * the one place where the two flows disagree: a lane of a whole wave that has no pixel shades the item's LAST pixel
 //     with 1/N = 0.  The epilogue runs for live lanes only -- several lanes would otherwise apply the momentum update to
 //     that last pixel.
@@ -83,35 +84,8 @@ __device__ __forceinline__ void joint_body(float *maps, float *exp_avg, float *e
         }
         if (wi.live) {
             if (grad_out) store_grads_k3(grad_out + (size_t)b * 12 * plane, plane, wi.pix, ps.acc);
-            // fit_body's epilogue, for the lanes that own a pixel ONLY
-            const PlaneBuf xb = plane_buf(maps + (size_t)b * 12 * plane, 12, plane, wi.pix);
-            const PlaneBuf mb = plane_buf(exp_avg + (size_t)b * 12 * plane, 12, plane, wi.pix);
-            const PlaneBuf vb = plane_buf(exp_avg_sq + (size_t)b * 12 * plane, 12, plane, wi.pix);
-            float m[12], v[12], x[12], g[12];
-            __builtin_amdgcn_sched_barrier(0);      // the three resources stand: the 24 state loads back to back
-#pragma unroll
-            for (int k = 0; k < 12; ++k) m[k] = plane_load(mb, k);
-#pragma unroll
-            for (int k = 0; k < 12; ++k) v[k] = plane_load(vb, k);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                x[0 + k] = ps.mi.n[k];
-                x[3 + k] = fit_stash(k, 0.0f, true);
-                x[6 + k] = fit_stash(3 + k, 0.0f, true);
-                x[9 + k] = ps.mi.s[k];
-                g[0 + k] = ps.acc.n[k];
-                g[3 + k] = ps.acc.d[k];
-                g[6 + k] = ps.acc.r[k];
-                g[9 + k] = ps.acc.s[k];
-            }
-#pragma unroll
-            for (int k = 0; k < 12; ++k) {
-                const float xn = adam_channel(adam, k, x[k], g[k], m[k], v[k]);
-                plane_store(xb, k, xn);
-                plane_store(mb, k, m[k]);
-                plane_store(vb, k, v[k]);
-            }
+            // the fit step's update, for the lanes that own a pixel ONLY
+            adam_epilogue(maps, exp_avg, exp_avg_sq, b, plane, wi.pix, ps, adam);
         } else {
             lsum -= lsum;       // +0; a NaN stays
         }
@@ -166,33 +140,19 @@ int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg, float *ex
                                           void *workspace, size_t workspace_bytes, int B, int S, int H, int W, void *stream)
 {
     const char *who = "photo_fit_adam_step_scene_grad";
-    char text[200];
-    const auto bad = [&](int code, const char *what) {
-        std::snprintf(text, sizeof(text), "%s: %s", who, what);
-        return fail(code, text);
-    };
     LossPlan p;
     double units;       // N 2^24
     // the scene-gradient entry's checks in its order (grad_out may be null and the kernels are forward + adjoint whatever
-    // it is: the plan is the one with a gradient), then the fit entry's
+    // it is: the plan is the one with a gradient), then the fit entry's (adam_args)
     if (int e = plan_sums(who, {maps, exp_avg, exp_avg_sq, photos, grad_scenes, scenes, xrow, loss_out}, weights,
                           weight_planes, nullptr, eps, grad_out ? grad_out : maps, workspace, workspace_bytes, 9, kPoseSpill,
                           B, S, H, W, &p, &units)) return e;
     // fit_stash's six words per thread stand beside the rows of sums: the workgroup's LDS stays inside what plan_sums
     // allows the scene-gradient kernels (60 KB of rows), S <= 383
     if (p.lds_bytes + 6 * kLossThreads * sizeof(float) > 60 * 1024)
-        return bad(SVBRDF_ERR_DIMS, "too many scenes per item for the LDS sums (max 383)");
+        return fit_bad(who, SVBRDF_ERR_DIMS, "too many scenes per item for the LDS sums (max 383)");
     AdamArgs a;
-    float sc[4];
-    if (!adam_scalars(lr, beta1, beta2, step, sc))
-        return bad(SVBRDF_ERR_DIMS, "step >= 1, a finite lr >= 0 and betas in [0, 1) are required");
-    if (!(adam_eps >= 0.0f) || !std::isfinite(adam_eps)) return bad(SVBRDF_ERR_DIMS, "adam_eps must be finite and >= 0");
-    a.beta1 = beta1; a.c1 = sc[0]; a.beta2 = beta2; a.c2 = sc[1]; a.step_size = sc[2]; a.rsb2 = sc[3]; a.adam_eps = adam_eps;
-    for (int k = 0; k < 12; ++k) {
-        a.lo[k] = bounds_host ? bounds_host[2 * k] : -__builtin_inff();
-        a.hi[k] = bounds_host ? bounds_host[2 * k + 1] : __builtin_inff();
-        if (!(a.lo[k] <= a.hi[k])) return bad(SVBRDF_ERR_DIMS, "bounds must hold lo <= hi for every channel, and no NaN");
-    }
+    if (int e = adam_args(who, kStepRule, bounds_host, lr, beta1, beta2, adam_eps, step, &a)) return e;
     hipLaunchKernelGGL(weights ? k_joint_fit_weighted : k_joint_fit, p.grid, dim3(kLossThreads), p.lds_bytes,
                        static_cast<hipStream_t>(stream), maps, exp_avg, exp_avg_sq, photos, weights, weight_planes, scenes,
                        xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, 1.0 / units, (float)units, a, grad_out,

@@ -190,6 +190,30 @@ class PhotoFit:
         return (losses.PhotoLoss(self.renderer).uses_fused_kernel() and self.maps.is_cuda
                 and self.maps.dtype == torch.float32)
 
+    def _fused_inputs(self, x, photos, scenes, weights, exposure, constants):
+        """What ``step`` and ``steps`` hand the fused entries, or None where the update is ``composed_step``'s (anything but
+        float32 maps on a ROCm device with ``LocalRenderer``, and float64 gains) -> (photos, weights, table, want): photos
+        and weights checked as PhotoLoss checks them; the scene table with the checked gains multiplied into its colour
+        columns; want = the loss is differentiable towards table and gains (never with ``constants``).  Without ``want``
+        table and gains are detached, and a table without gains stays where it is: the binding uploads it."""
+        if not self.uses_fused_kernel() or (isinstance(exposure, torch.Tensor) and exposure.dtype == torch.float64):
+            return None
+        photos = losses.PhotoLoss._check(x, photos)
+        weights = losses._check_weights(weights, x, photos)
+        exposure = losses._check_exposure(exposure, x, photos)
+        table = losses.PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
+        want = not constants and _wants_grad(table, exposure)
+        if not want:
+            table = table.detach()
+            exposure = None if exposure is None else exposure.detach()
+        if want or exposure is not None:
+            # the kernels take a device table and no exposure: the gains multiply the colour columns in front of them
+            # (_PhotoLossModule._forward), and autograd chains the table's gradient back through both
+            table = table.to(x.device)
+            if exposure is not None:
+                table = torch.cat((table[..., :6], table[..., 6:] * exposure), dim=-1)
+        return photos, weights, table, want
+
     def step(self, photos, scenes, weights=None, exposure=None):
         """One update from ``photos`` [B,S,3,H,W] (or [B,3,H,W]), ``scenes``, optional ``weights`` and optional ``exposure``
         (a positive gain per photo and colour channel) as ``losses.PhotoLoss`` takes them -> the 0-dim loss at the maps
@@ -209,24 +233,12 @@ class PhotoFit:
         constant."""
         x = self.maps.detach()
         t = int(self.state["step"]) + 1
-        if not self.uses_fused_kernel() or (isinstance(exposure, torch.Tensor) and exposure.dtype == torch.float64):
+        fused = self._fused_inputs(x, photos, scenes, weights, exposure, constants=False)
+        if fused is None:
             loss = composed_step(x, self.exp_avg, self.exp_avg_sq, t, photos, scenes, weights, self.lr, self.betas, self.eps,
                                  self._bounds, self.loss_eps, self.renderer, exposure)
         else:
-            photos = losses.PhotoLoss._check(x, photos)
-            weights = losses._check_weights(weights, x, photos)
-            exposure = losses._check_exposure(exposure, x, photos)
-            table = losses.PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1])
-            want = _wants_grad(table, exposure)
-            if not want:
-                table = table.detach()
-                exposure = None if exposure is None else exposure.detach()
-            if want or exposure is not None:
-                # the kernels take a device table and no exposure: the gains multiply the colour columns in front of them
-                # (_PhotoLossModule._forward), and autograd chains the table's gradient back through both
-                table = table.to(x.device)
-                if exposure is not None:
-                    table = torch.cat((table[..., :6], table[..., 6:] * exposure), dim=-1)
+            photos, weights, table, want = fused
             args = (x, self.exp_avg, self.exp_avg_sq, photos)
             rest = (t, self.lr, self.betas, self.eps, self._bounds_c, self.loss_eps, weights)
 
@@ -259,7 +271,8 @@ class PhotoFit:
         x = self.maps.detach()
         lr, betas, eps, bounds, bounds_c = self.lr, self.betas, self.eps, self._bounds, self._bounds_c
         t = int(self.state["step"]) + 1
-        if not self.uses_fused_kernel() or (isinstance(exposure, torch.Tensor) and exposure.dtype == torch.float64):
+        fused = self._fused_inputs(x, photos, scenes, weights, exposure, constants=True)
+        if fused is None:
             seen = []
             with torch.no_grad():
                 for k in range(n):
@@ -267,13 +280,7 @@ class PhotoFit:
                                               eps, bounds, self.loss_eps, self.renderer, exposure))
                     self.state["step"] = t + k
             return torch.stack(seen)
-        photos = losses.PhotoLoss._check(x, photos)
-        weights = losses._check_weights(weights, x, photos)
-        exposure = losses._check_exposure(exposure, x, photos)
-        table = losses.PhotoLoss._scene_table(scenes, photos.shape[0], photos.shape[1]).detach()
-        if exposure is not None:
-            table = table.to(x.device)
-            table = torch.cat((table[..., :6], table[..., 6:] * exposure.detach()), dim=-1)
+        photos, weights, table, _ = fused
         out = []
         for first in range(0, n, _native.PHOTO_FIT_MAX_STEPS):
             k = min(_native.PHOTO_FIT_MAX_STEPS, n - first)

@@ -55,45 +55,13 @@ def abi_scene_grad(native, dev, c, shift=0):
 
 def abi_joint(native, dev, c, t=None, bounds=None, want_grad=True, shift=0, lr=fc.LR, beta1=fc.BETA1, beta2=fc.BETA2,
               adam_eps=fc.ADAM_EPS, ws=None):
-    """svbrdf_photo_fit_adam_step_scene_grad on the case through its own ctypes call, every buffer between canaries,
-    grad_scenes included.  -> dict: loss [1], grad (or None), grad_scenes, x, m, v after the step, `inputs_intact` (photos,
-    weights, scenes unchanged), `canaries_intact`, `launches` (the library's counter moved by), `scratch_zero`"""
-    import torch
-    lib = native._load()
-    B, S, H = c["B"], c["S"], c["H"]
-    t = c["t"] if t is None else t
-    x, m, v = fc.Guarded(c["maps"], dev, shift), fc.Guarded(c["m"], dev, shift), fc.Guarded(c["v"], dev, shift)
-    ph, sc = fc.Guarded(c["photos"], dev, shift), fc.Guarded(c["scenes"], dev, shift)
-    w, wptr, planes = _weights(c, dev, shift)
-    g = fc.Guarded(np.full_like(c["maps"], 7.0), dev, shift) if want_grad else None
-    gs = fc.Guarded(np.full_like(c["scenes"], 7.0), dev, shift)
-    loss = torch.full((1,), -1.0, device=dev)
-    ws = scratch(lib, dev, c) if ws is None else ws
-    xr = native.xrow(dev, H)
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    bptr = None
-    if bounds is not None:
-        barr = (ctypes.c_float * 24)(*np.asarray(bounds, dtype=np.float32).reshape(-1).tolist())
-        bptr = ctypes.cast(barr, ctypes.c_void_p)
-    before = lib.svbrdf_debug_launch_count()
-    rc = getattr(lib, JOINT_ENTRY)(x.ptr(), m.ptr(), v.ptr(), ph.ptr(), wptr, planes, sc.ptr(), xr.data_ptr(), ctypes.c_float(EPS),
-                                   bptr, ctypes.c_float(lr), ctypes.c_float(beta1), ctypes.c_float(beta2),
-                                   ctypes.c_float(adam_eps), int(t), loss.data_ptr(), None if g is None else g.ptr(), gs.ptr(),
-                                   ws.data_ptr(), ws.numel() * 8, B, S, H, H, st)
-    assert rc == 0, lib.svbrdf_last_error()
-    torch.cuda.synchronize(dev)
-    out = dict(launches=lib.svbrdf_debug_launch_count() - before, scratch_zero=not ws.any().item(), loss=loss.cpu().numpy())
-    canaries, intact = True, True
-    for key, buf in (("x", x), ("m", m), ("v", v), ("grad", g), ("grad_scenes", gs)):
-        out[key], ok = (None, True) if buf is None else buf.get()
-        canaries = canaries and ok
-    for buf, src in ((ph, c["photos"]), (sc, c["scenes"]), (w, c["weights"])):
-        if buf is not None:
-            got, ok = buf.get()
-            canaries = canaries and ok
-            intact = intact and fc.same_bits(got, src)
-    out.update(canaries_intact=canaries, inputs_intact=intact)
-    return out
+    """svbrdf_photo_fit_adam_step_scene_grad on the case (fc.call_fit_entry), grad_scenes between canaries too -> dict: loss
+    [1], grad (or None), grad_scenes, x, m, v after the step, `inputs_intact`, `canaries_intact`, `launches`, `scratch_zero`"""
+    outs = (("loss", np.full(1, -1.0, np.float32)), ("grad", np.full_like(c["maps"], 7.0) if want_grad else None),
+            ("grad_scenes", np.full_like(c["scenes"], 7.0)))
+    ws = scratch(native._load(), dev, c) if ws is None else ws
+    return fc.call_fit_entry(native, dev, c, JOINT_ENTRY, (c["t"] if t is None else t,), outs, ws, bounds, shift, lr, beta1,
+                             beta2, adam_eps)
 
 
 # ------------------------------------------------------------------------------------------------ the speed measurement
@@ -110,17 +78,9 @@ def measure_joint_fit(dev, native, sets=6, n=40, rounds=3, pose_lr=2e-3):
         composed_fused_us the same with torch.optim.Adam(fused=True)
     """
     import torch
-    from bench import synthetic_maps
-    from svbrdf_estimation_amd import environment, fitting, losses, renderers
-    B, H, S = 8, 256, 9
+    from svbrdf_estimation_amd import fitting
     lib = native._load()
-    gen = torch.Generator().manual_seed(5)
-    torch.manual_seed(11)
-    table = environment.BatchSceneSampler(B, 3, 6).sample().contiguous().to(dev)
-    starts = [synthetic_maps(gen, B, H, tied=True).to(dev) for _ in range(sets)]
-    photos = [native.render_fwd(synthetic_maps(gen, B, H, tied=True).to(dev), table).clamp_(0.0, 1.0) for _ in range(sets)]
-    u = [torch.rand((B, S, H, H), generator=gen) for _ in range(sets)]
-    weights = [torch.where(t < 0.25, torch.zeros(()), torch.where(t >= 0.75, torch.ones(()), (t - 0.25) * 2.0)).to(dev) for t in u]
+    B, H, S, table, starts, photos, weights = fc.fit_workload(dev, native, sets)
     bounds = torch.from_numpy(fc.BOUNDS_FIT)
     fits = [fitting.PhotoFit(a.clone(), lr=fc.LR, bounds=bounds) for a in starts]
     leaves = [table.clone().requires_grad_(True) for _ in range(sets)]
@@ -131,7 +91,6 @@ def measure_joint_fit(dev, native, sets=6, n=40, rounds=3, pose_lr=2e-3):
     ws = torch.zeros(getattr(lib, WORKSPACE_BYTES)(B, S, H, H) // 8, dtype=torch.int64, device=dev)
     loss = torch.empty(1, device=dev)
     st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    fn = losses.PhotoLoss(renderers.LocalRenderer())
 
     def joint(i):
         k = i % sets
@@ -146,22 +105,9 @@ def measure_joint_fit(dev, native, sets=6, n=40, rounds=3, pose_lr=2e-3):
                                             grad_s.data_ptr(), ws.data_ptr(), ws.numel() * 8, B, S, H, H, st)
         assert rc == 0, lib.svbrdf_last_error()
 
-    def composed_leg(**adam):
-        xs = [a.clone().requires_grad_(True) for a in starts]
-        ts = [table.clone().requires_grad_(True) for _ in range(sets)]
-        opts = [torch.optim.Adam([{"params": [x]}, {"params": [t], "lr": pose_lr}], lr=fc.LR, **adam) for x, t in zip(xs, ts)]
-
-        def step(i):
-            k = i % sets
-            opts[k].zero_grad(set_to_none=True)
-            fn(xs[k], photos[k], ts[k], weights[k]).backward()
-            opts[k].step()
-            with torch.no_grad():
-                xs[k][:, 3:].clamp_(0.0, 1.0)
-        return step
-
-    legs = (("joint_us", joint), ("scene_grad_us", scene_grad), ("composed_us", composed_leg()),
-            ("composed_fused_us", composed_leg(fused=True)))
+    legs = (("joint_us", joint), ("scene_grad_us", scene_grad),
+            ("composed_us", fc.composed_fit_leg(starts, photos, table, weights, pose_lr)),
+            ("composed_fused_us", fc.composed_fit_leg(starts, photos, table, weights, pose_lr, fused=True)))
     out, res = photo_checks.timed_legs(legs, n, rounds, photo_checks.spinning_wave(native, dev), dev)
     out.update(rounds=res, device=torch.cuda.get_device_name(dev), steps_per_round=n, sets=sets)
     out["joint_over_scene_grad"] = out["joint_us"] / out["scene_grad_us"]

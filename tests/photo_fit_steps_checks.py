@@ -9,61 +9,25 @@ import ctypes
 import numpy as np
 
 import photo_fit_checks as fc
-from photo_fit_checks import BOUNDS_FIT, CASES, Guarded, abi_fit, case_inputs, library_scalars, same_bits  # noqa: F401
+from photo_fit_checks import (BOUNDS_FIT, CASES, Guarded, abi_fit, bounds_array, case_inputs, library_scalars,  # noqa: F401
+                              same_bits)
 
 STEPS_ENTRY, STEPS_BYTES = "svbrdf_photo_fit_adam_steps", "svbrdf_photo_fit_steps_workspace_bytes"
 MAX_STEPS = 64
 
 
-def bounds_array(bounds):
-    """-> (ctypes array kept alive by the caller, pointer) or (None, None)"""
-    if bounds is None:
-        return None, None
-    arr = (ctypes.c_float * 24)(*np.asarray(bounds, dtype=np.float32).reshape(-1).tolist())
-    return arr, ctypes.cast(arr, ctypes.c_void_p)
-
-
 def abi_steps(native, dev, c, n, first_step=None, bounds=None, shift=0, ws=None, lr=fc.LR, beta1=fc.BETA1, beta2=fc.BETA2,
               adam_eps=fc.ADAM_EPS):
-    """svbrdf_photo_fit_adam_steps on the case `c` (maps, m, v, photos, scenes, weights) through its own ctypes call, every
-    buffer between canaries.  -> dict: losses [n], x, m, v after the launch, `inputs_intact`, `canaries_intact`, `launches`
-    (the library's counter moved by), `scratch_zero` (all 65 n words)"""
+    """svbrdf_photo_fit_adam_steps on the case `c` (maps, m, v, photos, scenes, weights; fc.call_fit_entry) -> dict: losses
+    [n], x, m, v after the launch, `inputs_intact`, `canaries_intact`, `launches`, `scratch_zero` (all 65 n words)"""
     import torch
     lib = native._load()
-    B, S, H = c["B"], c["S"], c["H"]
-    first_step = c["t"] if first_step is None else first_step
-    x, m, v = Guarded(c["maps"], dev, shift), Guarded(c["m"], dev, shift), Guarded(c["v"], dev, shift)
-    ph, sc = Guarded(c["photos"], dev, shift), Guarded(c["scenes"], dev, shift)
-    w = None if c["weights"] is None else Guarded(c["weights"], dev, shift)
-    losses = Guarded(np.full(n, -1.0, np.float32), dev, shift)
-    need = getattr(lib, STEPS_BYTES)(n, B, S, H, H)
-    assert need == n * lib.svbrdf_rendering_loss_workspace_bytes(B, S, H, H) == n * 65 * 8
+    need = getattr(lib, STEPS_BYTES)(n, c["B"], c["S"], c["H"], c["H"])
+    assert need == n * lib.svbrdf_rendering_loss_workspace_bytes(c["B"], c["S"], c["H"], c["H"]) == n * 65 * 8
     ws = torch.zeros(need // 8, dtype=torch.int64, device=dev) if ws is None else ws
     assert ws.numel() * 8 >= need
-    xr = native.xrow(dev, H)
-    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    keep, bptr = bounds_array(bounds)
-    before = lib.svbrdf_debug_launch_count()
-    rc = getattr(lib, STEPS_ENTRY)(x.ptr(), m.ptr(), v.ptr(), ph.ptr(), None if w is None else w.ptr(),
-                                   0 if w is None else int(c["weights"].shape[1]), sc.ptr(), xr.data_ptr(),
-                                   ctypes.c_float(fc.EPS), bptr, ctypes.c_float(lr), ctypes.c_float(beta1),
-                                   ctypes.c_float(beta2), ctypes.c_float(adam_eps), int(first_step), int(n), losses.ptr(),
-                                   ws.data_ptr(), ws.numel() * 8, B, S, H, H, st)
-    assert rc == 0, lib.svbrdf_last_error()
-    torch.cuda.synchronize(dev)
-    del keep
-    out = dict(launches=lib.svbrdf_debug_launch_count() - before, scratch_zero=not ws.any().item())
-    canaries, intact = True, True
-    for key, buf in (("x", x), ("m", m), ("v", v), ("losses", losses)):
-        out[key], ok = buf.get()
-        canaries = canaries and ok
-    for buf, src in ((ph, c["photos"]), (sc, c["scenes"]), (w, c["weights"])):
-        if buf is not None:
-            got, ok = buf.get()
-            canaries = canaries and ok
-            intact = intact and same_bits(got, src)
-    out.update(canaries_intact=canaries, inputs_intact=intact)
-    return out
+    return fc.call_fit_entry(native, dev, c, STEPS_ENTRY, (c["t"] if first_step is None else first_step, n),
+                             (("losses", np.full(n, -1.0, np.float32)),), ws, bounds, shift, lr, beta1, beta2, adam_eps)
 
 
 def sequential(native, dev, c, n, first_step=None, bounds=None, **hyper):
@@ -108,17 +72,8 @@ def measure_steps_against_single(dev, native, steps=16, sets=6, n=10, rounds=3):
     """
     import torch
     import photo_checks
-    from bench import synthetic_maps
-    from svbrdf_estimation_amd import environment
-    B, H, S = 8, 256, 9
     lib = native._load()
-    gen = torch.Generator().manual_seed(5)
-    torch.manual_seed(11)
-    table = environment.BatchSceneSampler(B, 3, 6).sample().contiguous().to(dev)
-    starts = [synthetic_maps(gen, B, H, tied=True).to(dev) for _ in range(sets)]
-    photos = [native.render_fwd(synthetic_maps(gen, B, H, tied=True).to(dev), table).clamp_(0.0, 1.0) for _ in range(sets)]
-    u = [torch.rand((B, S, H, H), generator=gen) for _ in range(sets)]
-    weights = [torch.where(t < 0.25, torch.zeros(()), torch.where(t >= 0.75, torch.ones(()), (t - 0.25) * 2.0)).to(dev) for t in u]
+    B, H, S, table, starts, photos, weights = fc.fit_workload(dev, native, sets)
     state = {leg: [(a.clone(), torch.zeros_like(a), torch.zeros_like(a)) for a in starts] for leg in ("run", "single")}
     keep, bptr = bounds_array(BOUNDS_FIT)
     xr = native.xrow(dev, H)

@@ -294,3 +294,11 @@ def test_source_holds_no_inline_assembly_with_instructions_and_no_fma():
     assert '#define SVBRDF_PHOTO_SHARED_ONLY\n#include "svbrdf_photo_loss.hip"' in src
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert "fma" not in code and "rcp_" not in code and "rsq_" not in code      # the update is plain, individually rounded operations
+    # the single step's epilogue stands once -- the 24 state loads between its two scheduling barriers, adam_channel, the 36
+    # stores -- and fit_body calls it; fit_run_body's LDS-resident update is the only other use of adam_channel
+    assert len(re.findall(r"\bvoid adam_epilogue\(", code)) == 1 and code.count("adam_epilogue(") == 2
+    assert code.count("__builtin_amdgcn_sched_barrier(0)") == 2 and code.count("plane_load(mb, k)") == 2
+    assert code.count("adam_channel(") == 3
+    # and so do the checks of the weights and of the Adam arguments: one definition, every entry calls it
+    assert "const auto bad" not in code and code.count("bounds_host[2 * k]") == 1 and code.count("adam_eps must be") == 1
+    assert code.count("fit_weights_check(who,") == 2 and code.count("adam_args(who,") == 2

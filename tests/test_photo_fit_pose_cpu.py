@@ -344,10 +344,19 @@ def test_source_reuses_the_two_units_and_restates_no_arithmetic():
     assert not re.search(r"\basm\b", code) and "Cooperative" not in code and "grid_group" not in code
     assert '#define SVBRDF_PHOTO_POSE_SHARED_ONLY\n#include "svbrdf_photo_pose.hip"' in src
     assert '#define SVBRDF_PHOTO_FIT_SHARED_ONLY\n#include "svbrdf_photo_fit.hip"' in src
-    for used in ("pose_scene_loop<1, WEIGHTED>", "pose_scene_loop<3, WEIGHTED>", "photo_sums_finish<true>", "adam_channel(",
-                 "adam_scalars(", "plan_sums(", "fit_stash(", "expo_stash(", "wave_index(", "if (wi.live)"):
+    for used in ("pose_scene_loop<1, WEIGHTED>", "pose_scene_loop<3, WEIGHTED>", "photo_sums_finish<true>", "adam_epilogue(",
+                 "adam_args(", "plan_sums(", "fit_stash(", "expo_stash(", "wave_index(", "if (wi.live)"):
         assert used in code, used
     assert "sqrtf" not in code and "fma" not in code
+    # the update and the Adam-argument check are the fit unit's, called and not restated: the epilogue inside the live
+    # lanes' branch, no state load or store, no scheduling barrier and no reporter of its own here
+    assert re.search(r"if \(wi\.live\) \{[^}]*\badam_epilogue\(", code)
+    for own in ("plane_load(mb", "plane_store(", "adam_channel(", "adam_scalars(", "sched_barrier", "const auto bad", "a.lo["):
+        assert own not in code, own
+    with open(os.path.join(CSRC, "svbrdf_photo_fit.hip")) as f:
+        fit_code = "\n".join(line.split("//")[0] for line in f.read().splitlines())
+    assert (fit_code + code).count("__builtin_amdgcn_sched_barrier(0)") == 2        # the epilogue's pair, once
+    assert len(re.findall(r"\bvoid adam_epilogue\(", fit_code)) == 1 and len(re.findall(r"\bint adam_args\(", fit_code)) == 1
     assert re.findall(r"SVBRDF_JOINT_KERNEL\((k_\w+),", code) == ["k_joint_fit", "k_joint_fit_weighted"]
     for name, guard in (("svbrdf_photo_pose.hip", "SVBRDF_PHOTO_POSE_SHARED_ONLY"), ("svbrdf_photo_fit.hip", "SVBRDF_PHOTO_FIT_SHARED_ONLY")):
         with open(os.path.join(CSRC, name)) as f:
