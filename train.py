@@ -24,19 +24,30 @@ Convolutions: the U-Net runs on stock PyTorch-ROCm (MIOpen).  ``--conv-mode auto
 the reference's cudnn flags and MIOpen's immediate-mode choice (a four-step calibration of the forward; backward always
 immediate: the reference's ``deterministic=True`` pins MIOpen to a backward 5-20x slower) -- DESIGN.md section 10.
 
+``run(args)`` reads top to bottom: setup_rank -> build_model -> build_data -> train_steps -> assemble_result.  The modes
+that reach into the step loop each have one home, called unconditionally and a no-op when off: ConvFlags (--conv-mode),
+PhaseTimer (--phase-times), DdpProbe (the untimed DDP / no_sync steps behind the timed region).
+
 Prints one JSON line per run on rank 0 (end-to-end patches/s, mean loss of the first/last steps).
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
 import time
+import types
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
+import torch.distributed as dist  # noqa: E402
+
+from svbrdf_estimation_amd import distributed, launch, losses, renderers, training, utils  # noqa: E402
+from svbrdf_estimation_amd.training import data, models  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -130,12 +141,166 @@ def parse_args(argv=None):
     return ap.parse_args(argv)
 
 
-def run(args):
-    from svbrdf_estimation_amd import distributed, losses, renderers, training, utils
-    from svbrdf_estimation_amd.training import data, models
-    import torch.distributed as dist
-    miopen_cache = training.use_in_tree_miopen_cache()      # before the first convolution of the process
+def mark():
+    e = torch.cuda.Event(enable_timing=True)
+    e.record()
+    return e
 
+
+def stopwatch(device):
+    """starts now; the call it returns ends it and gives the milliseconds (HIP events and one device synchronisation, or
+    the host clock on the CPU)"""
+    start = mark() if device.type == "cuda" else time.perf_counter()
+
+    def stop():
+        if device.type != "cuda":
+            return 1e3 * (time.perf_counter() - start)
+        end = mark()
+        torch.cuda.synchronize(device)
+        return start.elapsed_time(end)
+    return stop
+
+
+class ConvFlags:
+    """--conv-mode in one place: what cudnn.deterministic / benchmark are around forward, backward and optimizer.
+    reference / fast / autotune set them once and never toggle; hybrid: the reference's flags while the network runs
+    forward, MIOpen's immediate-mode choice while autograd runs backward (only on a GPU).
+    auto: hybrid, with the forward under the reference's flags at steps 0-1, under the immediate-mode choice at steps 2-3
+    (the first of each pair compiles, the second is timed by `stopwatch`); from step 4 on the faster of the two.  The four
+    calibration steps are EXTRA untimed steps in front of the warm-up (they carry two device synchronisations and two
+    steps under the slower setting: never part of `value`, whatever --warmup says), and the ranks agree on the choice:
+    the timings go through `max_over_ranks` (None with one rank) before they are compared."""
+
+    def __init__(self, mode, on_gpu, max_over_ranks=None, stopwatch=None):
+        self.mode, self.max_over_ranks, self.stopwatch = mode, max_over_ranks, stopwatch
+        self.hybrid = mode in ("hybrid", "auto") and on_gpu
+        self.auto = mode == "auto" and on_gpu
+        self.calib_steps = 4 if self.auto else 0
+        self.forward_flag, self.calib, self.stop = True, {}, None
+        if mode in ("fast", "autotune"):       # enable_deterministic_random_engine set the reference's flags before this
+            torch.backends.cudnn.deterministic = False
+            torch.backends.cudnn.benchmark = mode == "autotune"
+
+    def before_forward(self, step):
+        if self.auto:
+            if step < 4:
+                self.forward_flag = step < 2
+            elif step == 4 and len(self.calib) == 2:
+                if self.max_over_ranks:     # one choice for the whole job: the slowest rank's timing of each setting decides
+                    self.calib = dict(zip((True, False), self.max_over_ranks([self.calib[True], self.calib[False]])))
+                self.forward_flag = self.calib[True] <= self.calib[False]
+            if step in (1, 3):
+                self.stop = self.stopwatch()
+        if self.hybrid:
+            torch.backends.cudnn.deterministic = self.forward_flag
+
+    def after_forward(self):
+        if self.stop is not None:
+            self.calib[self.forward_flag] = self.stop()
+            self.stop = None
+        if self.hybrid:      # backward always takes MIOpen's immediate-mode choice
+            torch.backends.cudnn.deterministic = False
+
+    def after_optimizer(self):
+        if self.hybrid:
+            torch.backends.cudnn.deterministic = True
+
+    def report(self):       # result["config"]["conv_forward"]; None outside auto
+        name = {True: "reference flags", False: "immediate mode"}
+        return {"chosen": name[self.forward_flag], "calibration_ms": {name[k]: v for k, v in self.calib.items()}} if self.auto else None
+
+
+class PhaseTimer:
+    """--phase-times: HIP events between the phases of a step and one device synchronisation at its end; off, every
+    call returns at once."""
+    phases = ("data_wait", "upload_synthesis", "forward", "loss", "backward", "optimizer")
+
+    def __init__(self, on, device):
+        self.on, self.device, self.ms = on, device, {k: [] for k in self.phases}
+
+    def start(self, wait_s):
+        if self.on:
+            self.wait_s, self.marks = wait_s, [mark()]
+
+    def mark(self):
+        if self.on:
+            self.marks.append(mark())
+
+    def commit(self, timed):
+        if self.on:
+            self.marks.append(mark())
+            torch.cuda.synchronize(self.device)
+            if timed:
+                self.ms["data_wait"].append(1e3 * self.wait_s)
+                for name, a, b in zip(self.phases[1:], self.marks[:-1], self.marks[1:]):
+                    self.ms[name].append(a.elapsed_time(b))
+
+    def report(self):
+        return {"phase_ms_mean": {k: sum(v) / max(1, len(v)) for k, v in self.ms.items()},
+                "phase_note": "per-step means over the timed steps; one device synchronisation per step (not a throughput run)"}
+
+
+class DdpProbe:
+    """After the timed region, DDP runs only: the same step WITH the bucketed all-reduce (DDP's hooks launch a bucket's
+    all-reduce on RCCL's stream as soon as its gradients exist, overlapping the rest of the backward) and WITHOUT it,
+    alternating, a `stopwatch` around loss.backward() -- what the all-reduce of ~320 MB costs a step beyond the backward it
+    hides behind.  DDP decides whether a backward synchronises when the FORWARD runs (require_backward_grad_sync is read
+    in DistributedDataParallel.forward), so a no_sync probe step has its forward, its loss and its backward inside
+    model.no_sync() (round 4 entered it around the backward only and measured the all-reduce twice).  Each probe step
+    also checks what it claims: a checksum of the first parameter's gradient goes through `gather` to every rank -- equal
+    on all ranks after a synchronised step, rank-local after a no_sync step.  No optimizer step in these.
+    The probe steps are `first` .. `first + 7` (none when off); odd offsets run under no_sync."""
+
+    def __init__(self, on, first, gather=None, stopwatch=None):
+        self.steps, self.first, self.gather, self.stopwatch = 8 if on else 0, first, gather, stopwatch
+        self.ms = {True: [], False: []}
+        self.sums = {True: [], False: []}          # per probe step: the gradient checksum of every rank
+
+    def probing(self, step):
+        return self.first <= step < self.first + self.steps
+
+    def synced(self, step):
+        return not (self.probing(step) and (step - self.first) % 2 == 1)
+
+    def start(self, step):
+        return self.stopwatch() if self.probing(step) else None
+
+    def finish(self, step, stop, net):
+        ms = stop()
+        g0 = next(p.grad for p in net.parameters() if p.grad is not None)
+        self.record(step, ms, self.gather(g0.detach().double().abs().sum().reshape(1)))
+
+    def record(self, step, ms, sums):
+        if step - self.first >= 2:                    # the first pair warms the no_sync path up
+            self.ms[self.synced(step)].append(ms)
+            self.sums[self.synced(step)].append([float(e) for e in sums])
+
+    def backward_ms(self):
+        return {("with_allreduce" if k else "no_sync"): (sum(v) / len(v) if v else None) for k, v in self.ms.items()}
+
+    @staticmethod
+    def spread(sums):       # largest relative difference between the ranks' gradient checksums of one step
+        return max((max(v) - min(v)) / max(abs(max(v)), 1e-300) for v in sums) if sums else None
+
+    def report(self, world, on_gpu):
+        """result["ddp_backward_probe"]"""
+        w, n = self.ms[True], self.ms[False]
+        synced, no_sync = self.spread(self.sums[True]), self.spread(self.sums[False])
+        return {"backward_ms_with_allreduce": sum(w) / len(w), "backward_ms_no_sync": sum(n) / len(n), "samples_each": len(w),
+                "grad_checksum_spread_over_ranks_synced": synced, "grad_checksum_spread_over_ranks_no_sync": no_sync,
+                "no_sync_left_gradients_rank_local": (no_sync > 1e-9 and synced <= 1e-9) if world > 1 else None,
+                "note": "rank 0, untimed steps after the timed region, %s around loss.backward(): DDP's bucketed "
+                        "all-reduce (gradient_as_bucket_view, 25 MB buckets) against a step whose forward and backward both ran "
+                        "inside model.no_sync(); the difference is what the all-reduce of the U-Net's gradients costs a step "
+                        "beyond the backward it overlaps with.  grad_checksum_spread_*: sum |grad| of the first parameter, "
+                        "gathered from every rank per probe step -- 0 after a synchronised step, > 0 after a no_sync step (the "
+                        "ranks hold different shards), which is the evidence that the second figure is a backward WITHOUT the "
+                        "all-reduce (with one rank there is nothing to compare)" % ("HIP events" if on_gpu else "the host clock")}
+
+
+def setup_rank(args):
+    """Rank bring-up: the rank environment, the CPU binding before the first GPU call, the device, the process group.
+    May set args.backend (--share-device)."""
     # this pool's host driver only supports dmabuf IPC: RCCL between rank processes needs it (read when the HSA runtime
     # starts, i.e. at the first GPU call; the self-spawning parent sets it for its children too)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -147,14 +312,11 @@ def run(args):
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: start one rank per GPU (or run train.py without a rank "
                          "environment and let it spawn them)" % (args.gpus, world))
     on_gpu = args.device == "cuda"
-    # first thing in a rank, before any GPU call: pin it (and the DataLoader workers it will fork) to the CPUs next to its
-    # GPU, ranks on one socket splitting that socket's cores (launch.py)
-    from svbrdf_estimation_amd import launch
     host_cpus = os.sched_getaffinity(0)
-    placement = launch.bind_rank_to_gpu_numa(local_rank, local_world, args.share_device) if on_gpu else \
-        {"cpus": launch.format_cpulist(os.sched_getaffinity(0)), "n_cpus": len(os.sched_getaffinity(0)), "numa_node": None,
-         "source": "unbound: --device cpu", "bound": False}
     if on_gpu:
+        # first thing in a rank, before any GPU call: pin it (and the DataLoader workers it will fork) to the CPUs next to
+        # its GPU, ranks on one socket splitting that socket's cores (launch.py)
+        placement = launch.bind_rank_to_gpu_numa(local_rank, local_world, args.share_device)
         assert torch.cuda.is_available(), "no ROCm device visible"
         if args.share_device:
             local_rank = 0
@@ -169,6 +331,8 @@ def run(args):
         dev = torch.device("cuda", local_rank)
         placement = launch.crosscheck_placement(placement, local_rank, host_cpus)   # PCI address: sysfs vs the runtime
     else:
+        placement = {"cpus": launch.format_cpulist(host_cpus), "n_cpus": len(host_cpus), "numa_node": None,
+                     "source": "unbound: --device cpu", "bound": False}
         if args.loss != "l1":
             raise SystemExit("the rendering loss has no CPU path; --device cpu only supports --loss l1 (plumbing tests)")
         if args.mix_materials:
@@ -181,7 +345,6 @@ def run(args):
     if grouped:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         if world == 1:                          # --force-dist without a launcher: a rendezvous of one
-            from svbrdf_estimation_amd import launch
             os.environ.setdefault("MASTER_PORT", str(launch.free_port()))
             os.environ.setdefault("RANK", "0")
             os.environ.setdefault("WORLD_SIZE", "1")
@@ -191,36 +354,47 @@ def run(args):
         if on_gpu:      # one rank per GPU, or the job stops here with the reason (--share-device: the plumbing tests' exception)
             distributed.require_distinct_devices(dev, args.share_device, rank)
 
-    def barrier():
+    def fence():    # what opens and closes the timed region: one device synchronisation, one barrier when grouped, the clock
+        if on_gpu:
+            torch.cuda.synchronize(dev)
         if nccl:
             dist.barrier(device_ids=[local_rank])
-        else:
+        elif grouped:
             dist.barrier()
+        return time.perf_counter()
+    return types.SimpleNamespace(rank=rank, local_rank=local_rank, world=world, local_world=local_world, on_gpu=on_gpu,
+                                 device=dev, placement=placement, grouped=grouped, backend=backend, nccl=nccl,
+                                 ranks_seen=ranks_seen, fence=fence)
 
+
+def max_over_ranks(r, values):
+    t = torch.tensor(values, dtype=torch.float64, device=r.device if r.nccl else "cpu")
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return t.tolist()
+
+
+def gather_over_ranks(r, mine):
+    if r.on_gpu and not r.nccl:                      # gloo moves host tensors
+        mine = mine.cpu()
+    every = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]
+    dist.all_gather(every, mine)
+    return every
+
+
+def build_model(args, r):
+    """Seed, network (+ --resume), DDP, optimizer, loss and the convolution flags, in the order the RNG and cudnn need."""
     verify = args.verify_global_batch
     # per-rank scene RNG -- or, for --verify-global-batch, one stream shared by all ranks (each skips the others' draws)
-    utils.enable_deterministic_random_engine(args.seed if verify else distributed.rank_seed(args.seed, rank))
-    if on_gpu:      # the rank's own CPU work is tiny (scene sampler, collation): a big intra-op pool only spins (bench.py main)
-        torch.set_num_threads(max(1, min(8, placement["n_cpus"])))
+    utils.enable_deterministic_random_engine(args.seed if verify else distributed.rank_seed(args.seed, r.rank))
+    if r.on_gpu:    # the rank's own CPU work is tiny (scene sampler, collation): a big intra-op pool only spins (bench.py main)
+        torch.set_num_threads(max(1, min(8, r.placement["n_cpus"])))
     decode = not args.fused_head
     if args.model == "multi":
         net = models.MultiViewModel(use_coords=not args.no_coords, decode=decode)
     else:
         net = models.SingleViewModel(use_coords=not args.no_coords, decode=decode)
-    # identical initial weights on every rank: DDP broadcasts rank 0's parameters at construction
-    conv_mode = "autotune" if args.autotune else args.conv_mode
-    if conv_mode in ("fast", "autotune"):       # enable_deterministic_random_engine set the reference's flags above
-        torch.backends.cudnn.deterministic = False
-        torch.backends.cudnn.benchmark = conv_mode == "autotune"
-    hybrid = conv_mode in ("hybrid", "auto") and on_gpu
-    auto = conv_mode == "auto" and on_gpu
-    # auto: forward under the reference's flags at steps 0-1, under the immediate-mode choice at steps 2-3 (the first of
-    # each pair compiles, the second is timed with HIP events); from step 4 on the faster of the two.  The four
-    # calibration steps are EXTRA untimed steps in front of the warm-up (they carry two device synchronisations and two
-    # steps under the slower setting: never part of `value`, whatever --warmup says), and the ranks agree on the choice:
-    # the timings are MAX-reduced over the ranks before they are compared.
-    forward_flag, calib = True, {}
-    calib_steps = 4 if auto else 0
+    conv = ConvFlags("autotune" if args.autotune else args.conv_mode, r.on_gpu,
+                     (lambda values: max_over_ranks(r, values)) if r.grouped else None, lambda: stopwatch(r.device))
     steps_done = 0
     if args.resume:
         ck = torch.load(args.resume, map_location="cpu", weights_only=False)
@@ -230,16 +404,17 @@ def run(args):
         # this package's own names (written by --save before it switched to the reference's layout)
         net.load_state_dict(state if set(state.keys()) <= own else models.convert_reference_state_dict(state))
         steps_done = int(ck.get("steps", 0))
-    net = net.to(dev).train()
+    net = net.to(r.device).train()
     if verify:
         for m in net.modules():
             if isinstance(m, torch.nn.Dropout):
                 m.p = 0.0
     if args.channels_last:
         net = net.to(memory_format=torch.channels_last)
+    # identical initial weights on every rank: DDP broadcasts rank 0's parameters at construction.
     # gradient_as_bucket_view: the parameters' .grad ARE views of the all-reduce buckets (no 320 MB copy per step)
-    model = torch.nn.parallel.DistributedDataParallel(net, device_ids=[local_rank] if on_gpu else None,
-                                                      gradient_as_bucket_view=True) if grouped else net
+    model = torch.nn.parallel.DistributedDataParallel(net, device_ids=[r.local_rank] if r.on_gpu else None,
+                                                      gradient_as_bucket_view=True) if r.grouped else net
     optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
     if args.resume and "optimizer_state_dict_amd" in ck:
         optimizer.load_state_dict(ck["optimizer_state_dict_amd"])
@@ -253,41 +428,43 @@ def run(args):
         loss_fn = (losses.FusedHeadLoss if args.fused_head else losses.MixedLoss)(renderers.LocalRenderer(), weight)
         loss_fn.rendering_loss.random_configuration_count = args.random_scenes
         loss_fn.rendering_loss.specular_configuration_count = args.specular_scenes
+    return types.SimpleNamespace(net=net, model=model, optimizer=optimizer, loss_fn=loss_fn, conv=conv, steps_done=steps_done)
 
-    total_steps = calib_steps + args.warmup + args.steps
+
+def build_data(args, r, n_steps):
+    """The batch source for `n_steps` steps: an endless iterator, and whether it draws on the device.  Sets args.workers."""
+    verify = args.verify_global_batch
     if args.workers < 0:        # the rank's CPU set is its share of the node already (placement), else split the host
-        mine = placement["n_cpus"] if placement.get("bound") else (os.cpu_count() or 2) // max(1, local_world)
+        mine = r.placement["n_cpus"] if r.placement.get("bound") else (os.cpu_count() or 2) // max(1, r.local_world)
         args.workers = max(2, min(16, mine - 1))
-    device_source = args.data == "synthetic" and on_gpu and not verify
-    if device_source:
-        dataset, args.workers = None, 0
-    elif args.data in ("synthetic", "synthetic-cpu"):
-        n = args.samples or total_steps * args.batch * world
+    if args.data == "synthetic" and r.on_gpu and not verify:
+        args.workers = 0
+
+        def device_batches():
+            gen = torch.Generator(device=r.device).manual_seed(distributed.rank_seed(args.seed * 7919, r.rank))
+            empty = torch.zeros(args.batch, 0, 3, args.size, args.size)
+            while True:
+                yield {"inputs": empty, "svbrdf": data.synthetic_svbrdf_batch(args.batch, args.size, r.device, gen)}
+        return device_batches(), True
+    if args.data in ("synthetic", "synthetic-cpu"):
+        n = args.samples or n_steps * args.batch * r.world
         dataset = data.SyntheticSvbrdfDataset(n, image_size=args.size, seed=args.seed)
     else:
         dataset = data.TiledPngDataset(args.data, image_size=args.size, image_count=args.image_count,
                                        used_image_count=args.views, is_linear=args.linear_input,
                                        scale_mode=args.scale_mode, random_crop=args.random_crop,
-                                       mix_materials=args.mix_materials, uint8_transport=on_gpu and not args.float_transport)
-    if device_source:
-        sampler = loader = None
-    elif verify:
-        sampler = distributed.ContiguousShardSampler(len(dataset), args.batch, rank, world)
+                                       mix_materials=args.mix_materials, uint8_transport=r.on_gpu and not args.float_transport)
+    if verify:
+        sampler = distributed.ContiguousShardSampler(len(dataset), args.batch, r.rank, r.world)
     else:
-        sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=world, rank=rank, shuffle=True,
-                                                                  seed=args.seed, drop_last=True) if world > 1 else None
-    if not device_source:
-        loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch, sampler=sampler, shuffle=sampler is None,
-                                             num_workers=args.workers, pin_memory=on_gpu and not args.no_pin, drop_last=True,
-                                             persistent_workers=args.workers > 0,
-                                             **({"prefetch_factor": args.prefetch} if args.workers > 0 else {}))
+        sampler = torch.utils.data.distributed.DistributedSampler(dataset, num_replicas=r.world, rank=r.rank, shuffle=True,
+                                                                  seed=args.seed, drop_last=True) if r.world > 1 else None
+    loader = torch.utils.data.DataLoader(dataset, batch_size=args.batch, sampler=sampler, shuffle=sampler is None,
+                                         num_workers=args.workers, pin_memory=r.on_gpu and not args.no_pin, drop_last=True,
+                                         persistent_workers=args.workers > 0,
+                                         **({"prefetch_factor": args.prefetch} if args.workers > 0 else {}))
 
-    def batches():
-        if device_source:
-            gen = torch.Generator(device=dev).manual_seed(distributed.rank_seed(args.seed * 7919, rank))
-            empty = torch.zeros(args.batch, 0, 3, args.size, args.size)
-            while True:
-                yield {"inputs": empty, "svbrdf": data.synthetic_svbrdf_batch(args.batch, args.size, dev, gen)}
+    def epochs():
         epoch = 0
         while True:
             if sampler is not None and hasattr(sampler, "set_epoch"):
@@ -295,216 +472,161 @@ def run(args):
             for b in loader:
                 yield b
             epoch += 1
+    return epochs(), False
 
-    phases = ("data_wait", "upload_synthesis", "forward", "loss", "backward", "optimizer")
-    phase_ms = {k: [] for k in phases}
-    timing = args.phase_times and on_gpu
 
-    def mark():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record()
-        return e
+def prepare_inputs(args, r, batch):
+    """a batch as the source delivers it -> the network's input and the target maps, on the device"""
+    batch = data.decode_uint8_batch(batch, r.device, is_linear=args.linear_input)    # 8-bit transport: decoded on the device
+    svbrdf = batch["svbrdf"].to(r.device, non_blocking=True)
+    stored = batch["inputs"].to(r.device, non_blocking=True)
+    if r.on_gpu and not args.verify_global_batch:
+        svbrdf = data.apply_mixing(svbrdf, batch)                            # K4: material mixing, whole batch
+        photos = data.complete_inputs(stored, svbrdf, args.views)           # K1: missing photos, whole batch
+    else:                                                                    # CPU plumbing runs: constant photos
+        photos = torch.cat((stored, svbrdf[:, None, 3:6].expand(-1, max(args.views - stored.shape[1], 0), -1, -1, -1)), 1)
+    return (photos if args.model == "multi" else photos[:, 0]), svbrdf
 
-    # after the timed region, DDP runs only: the same step WITH the bucketed all-reduce (DDP's hooks launch a bucket's
-    # all-reduce on RCCL's stream as soon as its gradients exist, overlapping the rest of the backward) and WITHOUT it,
-    # alternating, HIP events around loss.backward() -- what the all-reduce of ~320 MB costs a step beyond the backward it
-    # hides behind.  DDP decides whether a backward synchronises when the FORWARD runs (require_backward_grad_sync is read
-    # in DistributedDataParallel.forward), so a no_sync probe step has its forward, its loss and its backward inside
-    # model.no_sync() (round 4 entered it around the backward only and measured the all-reduce twice).  Each probe step
-    # also checks what it claims: a checksum of the first parameter's gradient is gathered from every rank -- equal on all
-    # ranks after a synchronised step, rank-local after a no_sync step.  No optimizer step in these.
-    probe_steps = 8 if (grouped and (on_gpu or args.ddp_probe) and not verify and not args.no_ddp_probe) else 0
-    end_timed = total_steps
-    total_steps += probe_steps
-    probe_ms = {True: [], False: []}
-    probe_sums = {True: [], False: []}          # per probe step: the gradient checksum of every rank
-    import contextlib
-    losses_seen, t0, elapsed, it = [], None, None, batches()
-    for step in range(total_steps):
-        if step == calib_steps + args.warmup:
-            if on_gpu:
-                torch.cuda.synchronize(dev)
-            if grouped:
-                barrier()
-            t0 = time.perf_counter()
+
+def save_global_gradient(path, args, r, net, loss):
+    """--verify-global-batch: rank 0's gradient after the first backward (DDP-averaged) and the global loss"""
+    g_loss = distributed.global_mean(loss.detach() if (r.nccl or not r.grouped) else loss.detach().cpu()).item()
+    if r.rank == 0:
+        flat = torch.cat([p.grad.reshape(-1) for p in net.parameters() if p.grad is not None])
+        np.savez(path, grad=flat.cpu().numpy(), loss=np.float64(g_loss), world=r.world, per_rank_batch=args.batch)
+
+
+def train_steps(args, r, m, batches, timer, probe, first_timed, end_timed):
+    """The step loop: untimed steps up to `first_timed`, the timed region up to `end_timed` (outside the helpers' modes no
+    device synchronisation inside it; one fence opens it, one closes it), then the probe's steps.  Returns the loss of every
+    step that updated the weights and the seconds this rank spent in the timed region."""
+    verify, conv, model, optimizer = args.verify_global_batch, m.conv, m.model, m.optimizer
+
+    def skip_scenes(items_of_ranks):     # --verify-global-batch: ONE scene stream, the other ranks' draws skipped
+        if verify and args.loss != "l1" and items_of_ranks > 0:
+            m.loss_fn.rendering_loss.sample_scene_table(items_of_ranks * args.batch)
+    losses_seen, t0, elapsed = [], None, None
+    for step in range(end_timed + probe.steps):
+        if step == first_timed:
+            t0 = r.fence()
         if step == end_timed:
-            if on_gpu:
-                torch.cuda.synchronize(dev)
-            if grouped:
-                barrier()
-            elapsed = time.perf_counter() - t0
-        probing = step >= end_timed
-        synced = not (probing and (step - end_timed) % 2 == 1)
+            elapsed = r.fence() - t0
         t_wait = time.perf_counter()
-        batch = next(it)
-        t_wait = time.perf_counter() - t_wait
-        marks = [mark()] if timing else None
-        batch = data.decode_uint8_batch(batch, dev, is_linear=args.linear_input)    # 8-bit transport: decoded on the device
-        svbrdf = batch["svbrdf"].to(dev, non_blocking=True)
-        stored = batch["inputs"].to(dev, non_blocking=True)
-        if on_gpu and not verify:
-            svbrdf = data.apply_mixing(svbrdf, batch)                            # K4: material mixing, whole batch
-            photos = data.complete_inputs(stored, svbrdf, args.views)           # K1: missing photos, whole batch
-        else:                                                                    # CPU plumbing runs: constant photos
-            photos = torch.cat((stored, svbrdf[:, None, 3:6].expand(-1, max(args.views - stored.shape[1], 0), -1, -1, -1)), 1)
-        net_in = photos if args.model == "multi" else photos[:, 0]
+        batch = next(batches)
+        timer.start(time.perf_counter() - t_wait)
+        net_in, svbrdf = prepare_inputs(args, r, batch)
         optimizer.zero_grad(set_to_none=True)
-        if timing:
-            marks.append(mark())
-        if auto:
-            if step < 4:
-                forward_flag = step < 2
-            elif step == 4 and len(calib) == 2:
-                if grouped:     # one choice for the whole job: the slowest rank's timing of each setting decides
-                    both = torch.tensor([calib[True], calib[False]], dtype=torch.float64, device=dev if nccl else "cpu")
-                    dist.all_reduce(both, op=dist.ReduceOp.MAX)
-                    calib = {True: float(both[0]), False: float(both[1])}
-                forward_flag = calib[True] <= calib[False]
-            probe = (mark(), None) if step in (1, 3) else None
-        if hybrid:
-            torch.backends.cudnn.deterministic = forward_flag
-        with (contextlib.nullcontext() if synced else model.no_sync()):      # forward AND backward: see the probe note above
+        timer.mark()
+        conv.before_forward(step)
+        with (contextlib.nullcontext() if probe.synced(step) else model.no_sync()):     # forward AND backward: see DdpProbe
             out = model(net_in)
-            if auto and probe is not None:
-                probe = (probe[0], mark())
-                torch.cuda.synchronize(dev)
-                calib[forward_flag] = probe[0].elapsed_time(probe[1])
-            if hybrid:      # backward always takes MIOpen's immediate-mode choice
-                torch.backends.cudnn.deterministic = False
-            if timing:
-                marks.append(mark())
-            if verify and args.loss != "l1":                                         # the scenes of the lower ranks' items
-                if rank > 0:
-                    loss_fn.rendering_loss.sample_scene_table(rank * args.batch)
-            loss = loss_fn(out, svbrdf)
-            if verify and args.loss != "l1":                                         # ... and of the higher ranks' items
-                if rank < world - 1:
-                    loss_fn.rendering_loss.sample_scene_table((world - 1 - rank) * args.batch)
-            if timing:
-                marks.append(mark())
-            if probing:
-                bw0 = mark() if on_gpu else time.perf_counter()
+            conv.after_forward()
+            timer.mark()
+            skip_scenes(r.rank)                                                         # the scenes of the lower ranks' items
+            loss = m.loss_fn(out, svbrdf)
+            skip_scenes(r.world - 1 - r.rank)                                           # ... and of the higher ranks' items
+            timer.mark()
+            stop = probe.start(step)
             loss.backward()
-        if probing:
-            if on_gpu:
-                bw1 = mark()
-                torch.cuda.synchronize(dev)
-                ms = bw0.elapsed_time(bw1)
-            else:
-                ms = 1e3 * (time.perf_counter() - bw0)
-            g0 = next(p.grad for p in net.parameters() if p.grad is not None)
-            mine = g0.detach().double().abs().sum().reshape(1)
-            if on_gpu and not nccl:                      # gloo moves host tensors
-                mine = mine.cpu()
-            every = [torch.zeros_like(mine) for _ in range(dist.get_world_size())]
-            dist.all_gather(every, mine)
-            if step - end_timed >= 2:                    # the first pair warms the no_sync path up
-                probe_ms[synced].append(ms)
-                probe_sums[synced].append([float(e.item()) for e in every])
+        if stop is not None:
+            probe.finish(step, stop, m.net)
             optimizer.zero_grad(set_to_none=True)
             continue
         if verify and step == 0:
-            g_loss = distributed.global_mean(loss.detach() if (nccl or not grouped) else loss.detach().cpu()).item()
-            if rank == 0:
-                import numpy as np
-                flat = torch.cat([p.grad.reshape(-1) for p in net.parameters() if p.grad is not None])
-                np.savez(verify, grad=flat.cpu().numpy(), loss=np.float64(g_loss), world=world, per_rank_batch=args.batch)
-        if timing:
-            marks.append(mark())
+            save_global_gradient(verify, args, r, m.net, loss)
+        timer.mark()
         optimizer.step()
-        if hybrid:
-            torch.backends.cudnn.deterministic = True
+        conv.after_optimizer()
         losses_seen.append(loss.detach())
-        if timing:
-            marks.append(mark())
-            torch.cuda.synchronize(dev)
-            if step >= calib_steps + args.warmup:
-                phase_ms["data_wait"].append(1e3 * t_wait)
-                for name, a, b in zip(phases[1:], marks[:-1], marks[1:]):
-                    phase_ms[name].append(a.elapsed_time(b))
-    if on_gpu:
-        torch.cuda.synchronize(dev)
-    if grouped:
-        barrier()
-    if elapsed is None:
-        elapsed = time.perf_counter() - t0
-    own_elapsed = elapsed
-    per_rank = {"elapsed_s": [own_elapsed], "cpus": [placement["cpus"]], "numa_node": [placement["numa_node"]],
-                "cpu_binding": [placement["source"]], "pci_crosscheck": [placement.get("pci_crosscheck")]}
-    if grouped:
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if nccl else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-        every = [None] * dist.get_world_size()
-        dist.all_gather_object(every, {"elapsed_s": own_elapsed, "cpus": placement["cpus"], "numa_node": placement["numa_node"],
-                                       "cpu_binding": placement["source"], "pci_crosscheck": placement.get("pci_crosscheck"),
-                                       "backward_ms": {("with_allreduce" if k else "no_sync"): (sum(v) / len(v) if v else None)
-                                                       for k, v in probe_ms.items()}})
-        per_rank = {k: [e[k] for e in every] for k in every[0]}
-    per_rank["ms_per_step"] = [1e3 * e / args.steps for e in per_rank["elapsed_s"]]
-    per_rank["patches_per_s"] = [args.batch * args.steps / e for e in per_rank["elapsed_s"]]
+        timer.commit(step >= first_timed)
+    t1 = r.fence()
+    return losses_seen, (t1 - t0 if elapsed is None else elapsed)
+
+
+def rank_record(placement, elapsed, backward_ms=None):
+    """what one rank reports about itself; `backward_ms` (the probe's means) only in a process group"""
+    rec = {"elapsed_s": elapsed, "cpus": placement["cpus"], "numa_node": placement["numa_node"],
+           "cpu_binding": placement["source"], "pci_crosscheck": placement.get("pci_crosscheck")}
+    return rec if backward_ms is None else dict(rec, backward_ms=backward_ms)
+
+
+def per_rank_table(records, batch, steps):
+    """result["per_rank"]: the ranks' records column by column, with the rates that follow from elapsed_s"""
+    per_rank = {k: [e[k] for e in records] for k in records[0]}
+    per_rank["ms_per_step"] = [1e3 * e / steps for e in per_rank["elapsed_s"]]
+    per_rank["patches_per_s"] = [batch * steps / e for e in per_rank["elapsed_s"]]
+    return per_rank
+
+
+def assemble_result(args, r, m, device_source, miopen_cache, losses_seen, own_elapsed, timer, probe):
+    own = rank_record(r.placement, own_elapsed, probe.backward_ms() if r.grouped else None)
+    records, elapsed = [own], own_elapsed
+    if r.grouped:
+        elapsed, = max_over_ranks(r, [own_elapsed])
+        records = [None] * dist.get_world_size()
+        dist.all_gather_object(records, own)
     vals = torch.stack(losses_seen).float()
-    if grouped and not nccl:
+    if r.grouped and not r.nccl:
         vals = vals.cpu()
     first, last = vals[: max(1, len(vals) // 4)].mean(), vals[-max(1, len(vals) // 4):].mean()
     first, last = distributed.global_mean(first).item(), distributed.global_mean(last).item()
     result = {"metric": "end-to-end training patches/s (U-Net + %s loss)" % args.loss,
-              "value": world * args.batch * args.steps / elapsed, "unit": "patches/s", "n_gpus": world,
+              "value": r.world * args.batch * args.steps / elapsed, "unit": "patches/s", "n_gpus": r.world,
               "per_gpu_value": args.batch * args.steps / elapsed,
-              "ranks_seen": ranks_seen, "per_rank": per_rank,
-              "process_group": ("%s, world size %d, DistributedDataParallel" % (backend, dist.get_world_size())) if grouped else None,
+              "ranks_seen": r.ranks_seen, "per_rank": per_rank_table(records, args.batch, args.steps),
+              "process_group": ("%s, world size %d, DistributedDataParallel" % (r.backend, dist.get_world_size())) if r.grouped else None,
               "ms_per_step": 1e3 * elapsed / args.steps, "steps": args.steps, "warmup": args.warmup,
               "loss_first_quarter": first, "loss_last_quarter": last,
               "config": {"model": args.model, "views": args.views, "size": args.size, "per_gpu_batch": args.batch,
                          "scenes": args.random_scenes + args.specular_scenes, "fused_head": bool(args.fused_head),
                          "data": ("synthetic (device)" if device_source else args.data) if args.data.startswith("synthetic") else "tiled-png",
-                         "workers": args.workers, "conv_mode": conv_mode, "channels_last": bool(args.channels_last),
+                         "workers": args.workers, "conv_mode": m.conv.mode, "channels_last": bool(args.channels_last),
                          "miopen_cache": training.miopen_cache_identity(miopen_cache)}}
     if len(vals) <= 64:         # short runs (tests): every step's own loss, calibration and warm-up steps included
         result["loss_per_step"] = [float(v) for v in vals.tolist()]
-        result["untimed_leading_steps"] = calib_steps + args.warmup
-    if probe_steps:
-        w, n = probe_ms[True], probe_ms[False]
+        result["untimed_leading_steps"] = m.conv.calib_steps + args.warmup
+    if probe.steps:
+        result["ddp_backward_probe"] = probe.report(r.world, r.on_gpu)
+    if m.conv.auto:
+        result["config"]["conv_forward"] = m.conv.report()
+    if timer.on:
+        result.update(timer.report())
+    return result
 
-        def spread(sums):       # largest relative difference between the ranks' gradient checksums of one step
-            return max((max(v) - min(v)) / max(abs(max(v)), 1e-300) for v in sums) if sums else None
-        result["ddp_backward_probe"] = {
-            "backward_ms_with_allreduce": sum(w) / len(w), "backward_ms_no_sync": sum(n) / len(n), "samples_each": len(w),
-            "grad_checksum_spread_over_ranks_synced": spread(probe_sums[True]),
-            "grad_checksum_spread_over_ranks_no_sync": spread(probe_sums[False]),
-            "no_sync_left_gradients_rank_local": (spread(probe_sums[False]) > 1e-9 and spread(probe_sums[True]) <= 1e-9)
-                                                 if world > 1 else None,
-            "note": "rank 0, untimed steps after the timed region, %s around loss.backward(): DDP's bucketed "
-                    "all-reduce (gradient_as_bucket_view, 25 MB buckets) against a step whose forward and backward both ran "
-                    "inside model.no_sync(); the difference is what the all-reduce of the U-Net's gradients costs a step "
-                    "beyond the backward it overlaps with.  grad_checksum_spread_*: sum |grad| of the first parameter, "
-                    "gathered from every rank per probe step -- 0 after a synchronised step, > 0 after a no_sync step (the "
-                    "ranks hold different shards), which is the evidence that the second figure is a backward WITHOUT the "
-                    "all-reduce (with one rank there is nothing to compare)" % ("HIP events" if on_gpu else "the host clock")}
-    if auto:
-        result["config"]["conv_forward"] = {"chosen": "reference flags" if forward_flag else "immediate mode",
-                                            "calibration_ms": {("reference flags" if k else "immediate mode"): v for k, v in calib.items()}}
-    if timing:
-        result["phase_ms_mean"] = {k: sum(v) / max(1, len(v)) for k, v in phase_ms.items()}
-        result["phase_note"] = "per-step means over the timed steps; one device synchronisation per step (not a throughput run)"
-    if rank == 0:
-        if args.save:
-            # the reference's checkpoint.tar layout (persistence.py:52-69) with the REFERENCE's parameter names, so that
-            # its Checkpoint.restore_model_state loads the weights into its own SingleViewModel / MultiViewModel.  The
-            # optimizer state indexes parameters by position, which differs between the two module trees: it is kept
-            # under its own key instead of one the reference would load into the wrong slots.
-            torch.save({"model_type": args.model, "use_coords": not args.no_coords, "epoch": 0,
-                        "model_state_dict": models.convert_to_reference_state_dict(net.state_dict()),
-                        "optimizer_state_dict_amd": optimizer.state_dict(), "steps": steps_done + total_steps}, args.save)
+
+def save_checkpoint(path, args, m, steps):
+    # the reference's checkpoint.tar layout (persistence.py:52-69) with the REFERENCE's parameter names, so that
+    # its Checkpoint.restore_model_state loads the weights into its own SingleViewModel / MultiViewModel.  The
+    # optimizer state indexes parameters by position, which differs between the two module trees: it is kept
+    # under its own key instead of one the reference would load into the wrong slots.
+    torch.save({"model_type": args.model, "use_coords": not args.no_coords, "epoch": 0,
+                "model_state_dict": models.convert_to_reference_state_dict(m.net.state_dict()),
+                "optimizer_state_dict_amd": m.optimizer.state_dict(), "steps": steps}, path)
+
+
+def run(args):
+    miopen_cache = training.use_in_tree_miopen_cache()      # before the first convolution of the process
+    r = setup_rank(args)
+    m = build_model(args, r)
+    first_timed = m.conv.calib_steps + args.warmup
+    end_timed = first_timed + args.steps
+    batches, device_source = build_data(args, r, end_timed)
+    timer = PhaseTimer(args.phase_times and r.on_gpu, r.device)
+    probe = DdpProbe(r.grouped and (r.on_gpu or args.ddp_probe) and not args.verify_global_batch and not args.no_ddp_probe,
+                     end_timed, lambda mine: gather_over_ranks(r, mine), lambda: stopwatch(r.device))
+    losses_seen, elapsed = train_steps(args, r, m, batches, timer, probe, first_timed, end_timed)
+    result = assemble_result(args, r, m, device_source, miopen_cache, losses_seen, elapsed, timer, probe)
+    if r.rank == 0:
+        if args.save:       # total steps: calibration, warm-up and probe steps included
+            save_checkpoint(args.save, args, m, m.steps_done + end_timed + probe.steps)
         print(json.dumps(result), flush=True)
-    if grouped:
+    if r.grouped:
         dist.destroy_process_group()
     return result
 
 
 def main(argv=None):
     args = parse_args(argv)
-    from svbrdf_estimation_amd import launch
     if args.gpus > 1 and not launch.launched_as_rank():
         # one plain process asked for N GPUs: become the parent of N fresh rank processes (no GPU call has
         # happened in this process and none will)
