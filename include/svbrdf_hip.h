@@ -412,6 +412,45 @@ SVBRDF_API int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg
                                                      float *grad_out, float *grad_scenes, void *workspace,
                                                      size_t workspace_bytes, int B, int S, int H, int W, void *stream);
 
+/* CAPTURED PHOTOGRAPHS ONTO THE PATCH GRID, ONE launch: what stands between a camera image -- a perspective view, usually
+ * 8-bit and gamma encoded, far larger than the grid, with clipped highlights and pixels outside the patch -- and the
+ * `photos` / `weights` of the entries above.  P source photographs are resampled through a 3x3 homography each onto an
+ * [Hd,Wd] grid with bilinear taps; 8-bit codes are decoded through a 256-entry table; the {0,1} confidence plane is written
+ * beside the values.  With the inverse matrix the same call is the reference's rendering-to-perspective mapping
+ * (OrthoToPerspectiveMapping.apply, renderers.py:171-173: zeros outside, like cv2's constant border).
+ *   src          SVBRDF_RECTIFY_F32_PLANAR:     float32 [P,3,Hs,Ws], used as it is
+ *                SVBRDF_RECTIFY_U8_INTERLEAVED: uint8 [P,Hs,Ws,3] (what an image decoder returns; any byte alignment);
+ *                a tap's value is lut[code], `lut` a DEVICE float32 [256] table of the caller's (gamma 2.2, sRGB, a camera
+ *                response; NULL for float sources).  No pow runs on the device.
+ *   matrices     DEVICE float32 [P,9], row-major m0..m8 per photo: a DESTINATION pixel index (x, y, 1) -> SOURCE pixel-index
+ *                coordinates.  Integer coordinates are pixel centres (cv2's convention, and the patch grid's: pixel 0's
+ *                centre lies on the patch edge, xrow = linspace(-1, 1, W)).
+ *   k            k x k sub-samples per destination pixel, k in {1, 2, 4}
+ *   out          [P,3,Hd,Wd];  weights_out [P,Hd,Wd], or NULL: not wanted
+ * Every line is one individually rounded float32 operation (no fused multiply-add, IEEE division):
+ *   xs = x + ((i + 0.5)/k - 0.5),  ys = y + ((j + 0.5)/k - 0.5)               sub-sample (i, j); the offsets are exact
+ *   X = (m0 xs + m1 ys) + m2,  Y = (m3 xs + m4 ys) + m5,  Z = (m6 xs + m7 ys) + m8,  u = X / Z,  v = Y / Z
+ *   geometrically valid  <=>  Z > 0 and 0 <= u <= Ws-1 and 0 <= v <= Hs-1     (false for NaN; else u = v = 0 for addressing)
+ *   x0 = floor(u), fx = u - x0, x1 = min(x0 + 1, Ws-1), likewise y;  a = (y0,x0), b = (y0,x1), c = (y1,x0), d = (y1,x1)
+ *   top = a + fx (b - a),  bot = c + fx (d - c),  val = top + fy (bot - top)
+ *   value = (sum of val over the sub-samples, (j, i) row-major) * (1/k^2)
+ * A tap is invalid if any of its three channels is not finite, <= clip_lo or >= clip_hi (float sources: -inf / +inf switch
+ * the thresholds off), or has a code <= clip_lo or >= clip_hi (uint8 sources: the floats are converted exactly, floor and
+ * ceil; -1 / 256 or beyond switch them off).  All four taps are checked, also where fx or fy is 0.  If ANY sub-sample of a
+ * pixel is invalid, by geometry or by a tap, its three values are 0.0 and its weight 0.0; otherwise its weight is 1.0.
+ * u and v are clamped in float before the conversion to int: every load address lies inside the source WHATEVER `matrices`
+ * holds (NaN, infinities, 1e30, m8 = 0: such pixels are invalid, nothing else happens).  Results are a pure function of the
+ * arguments: bit for bit the numpy float32 restatement of tests/capture_checks.py.
+ * Error codes before any launch: SVBRDF_ERR_DIMS for another src_format, k not in {1, 2, 4}, a size < 1, P > 65535, a size
+ * > 32768 or a NaN threshold; SVBRDF_ERR_NULL for src, matrices, out, or lut with uint8 sources; SVBRDF_ERR_ALIGN for a
+ * float pointer that is not 4-byte aligned.  No workspace.  No gradient through the resampling.
+ * ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect it by symbol presence. */
+#define SVBRDF_RECTIFY_F32_PLANAR 0
+#define SVBRDF_RECTIFY_U8_INTERLEAVED 1
+SVBRDF_API int svbrdf_rectify_photos(const void *src, int src_format, int P, int Hs, int Ws, const float *matrices, int Hd,
+                                     int Wd, int k, const float *lut, float clip_lo, float clip_hi, float *out,
+                                     float *weights_out, void *stream);
+
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd
  * wrapper to apply the upstream gradient of the loss (the chain rule through

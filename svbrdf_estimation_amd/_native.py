@@ -94,6 +94,8 @@ SIGNATURES = {
     "svbrdf_photo_fit_adam_step_scene_grad": (_int, _LOSS_FIT_SG),
     "svbrdf_photo_fit_steps_workspace_bytes": (_size, [_int] * 5),
     "svbrdf_photo_fit_adam_steps": (_int, _LOSS_FIT_STEPS),
+    # src, format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi, out, weights_out, stream
+    "svbrdf_rectify_photos": (_int, [_fp, _int, _int, _int, _int, _fp, _int, _int, _int, _fp, _float, _float, _fp, _fp, _fp]),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
     "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
     "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
@@ -128,7 +130,7 @@ def _load():
             raise NativeLibraryError("cannot load %s: %s" % (_SO, e))
         for name, (restype, argtypes) in SIGNATURES.items():
             if not hasattr(lib, name):
-                if "photo_loss" in name or "photo_exposure" in name or "photo_scene_grad" in name or "photo_fit" in name:    # joined ABI version 8 without a bump: an older build lacks them
+                if "photo_loss" in name or "photo_exposure" in name or "photo_scene_grad" in name or "photo_fit" in name or "rectify" in name:    # joined ABI version 8 without a bump: an older build lacks them
                     raise NativeLibraryError("%s lacks %s (a build of ABI version 8 older than this binding) -- rebuild"
                                              % (_SO, name))
                 raise NativeLibraryError("%s does not export %s -- rebuild" % (_SO, name))

@@ -1,0 +1,247 @@
+"""Captured photographs onto the patch grid, and renderings into a perspective camera: the step between a camera image and
+``losses.PhotoLoss`` / ``fitting.PhotoFit``.
+
+The photo losses take photographs as ``[B,S,3,H,W]`` float32, linear, on the patch's orthographic pixel grid, with an optional
+confidence plane per photo.  A captured photograph is a perspective image of the patch, usually 8-bit and gamma encoded, much
+larger than the grid, with clipped highlights and pixels outside the patch.  ``rectify`` takes it there in ONE kernel launch
+(svbrdf_rectify_photos, csrc/svbrdf_capture.hip): a 3x3 homography per photo, bilinear taps, the decode of 8-bit codes
+through a 256-entry table, and the ``{0,1}`` weights, all bit for bit a numpy float32 restatement (tests/capture_checks.py).
+
+    corners = ...                                                # the patch's four corners in the photo, in pixels
+    M = capture.patch_homography(corners, (256, 256))            # destination pixel -> source pixel
+    photos, weights = capture.rectify(images_u8, M, 256, lut=capture.gamma_lut(), clip=(5, 250), samples=2)
+    loss = losses.PhotoLoss(renderers.LocalRenderer())(maps, photos, scenes, weights)
+
+``to_perspective`` is the other direction, the reference's ``OrthoToPerspectiveMapping.apply`` (renderers.py:106-173, there a
+cv2 warp): the same kernel with the inverse matrix.  ``camera_corners`` / ``camera_from_corners`` go between a camera
+position and the corners it sees, for a first guess of the pose that ``PhotoLoss``'s scene gradient then refines.
+
+Conventions.  A matrix maps a DESTINATION pixel index ``(x, y, 1)`` to SOURCE pixel-index coordinates; integer coordinates
+are pixel centres (cv2's convention).  That matches the patch grid: ``linspace(-1, 1, W)`` puts pixel 0's centre on the patch
+edge, so the patch corners are the centres of the grid's corner pixels, ``(0, 0)``, ``(0, H-1)``, ``(W-1, H-1)``, ``(W-1, 0)``
+in the reference's corner order top-left, bottom-left, bottom-right, top-right.  (The reference's ``get_homography`` stretches
+the ``W`` x ``H`` image over ``[0, W] x [0, H]`` instead, half a pixel off at each edge; what is kept here is the camera.)
+
+No gradient flows through the resampling, neither towards the images nor towards the matrices.  There is no CPU path.
+"""
+import math
+
+import numpy as np
+import torch
+
+from . import _native
+
+F32_PLANAR, U8_INTERLEAVED = 0, 1        # SVBRDF_RECTIFY_F32_PLANAR / SVBRDF_RECTIFY_U8_INTERLEAVED of include/svbrdf_hip.h
+_PATCH_CORNERS = np.array([[-1.0, 1.0], [-1.0, -1.0], [1.0, -1.0], [1.0, 1.0]])    # top-left, bottom-left, bottom-right, top-right
+
+
+# ------------------------------------------------------------------------------------------------ lookup tables
+
+def gamma_lut(gamma=2.2):
+    """float32 [256]: code / 255 to the power ``gamma`` (``utils.gamma_decode``'s rule on an 8-bit code), computed on the host
+    in float64 and rounded once"""
+    codes = np.arange(256, dtype=np.float64) / 255.0
+    return torch.from_numpy(np.power(codes, float(gamma)).astype(np.float32))
+
+
+def srgb_lut():
+    """float32 [256]: the sRGB electro-optical transfer function (IEC 61966-2-1) on an 8-bit code: c / 12.92 up to 0.04045,
+    ((c + 0.055) / 1.055) ** 2.4 above; float64 on the host, rounded once"""
+    c = np.arange(256, dtype=np.float64) / 255.0
+    lin = np.where(c <= 0.04045, c / 12.92, np.power((c + 0.055) / 1.055, 2.4))
+    return torch.from_numpy(lin.astype(np.float32))
+
+
+# ------------------------------------------------------------------------------------------------ homographies
+
+def _size(size):
+    """(H, W) from an int or a pair"""
+    if isinstance(size, (int, np.integer)):
+        return int(size), int(size)
+    H, W = size
+    return int(H), int(W)
+
+
+def _homography(src, dst):
+    """float64 [3,3] with h8 = 1 that sends the four points ``src`` [4,2] to ``dst`` [4,2]: the 8x8 linear system"""
+    src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
+    if src.shape != (4, 2) or dst.shape != (4, 2):
+        raise ValueError("a homography needs four (x, y) points on each side")
+    A, b = np.zeros((8, 8)), np.zeros(8)
+    for k, ((x, y), (u, v)) in enumerate(zip(src, dst)):
+        A[2 * k] = (x, y, 1.0, 0.0, 0.0, 0.0, -u * x, -u * y)
+        A[2 * k + 1] = (0.0, 0.0, 0.0, x, y, 1.0, -v * x, -v * y)
+        b[2 * k], b[2 * k + 1] = u, v
+    return np.append(np.linalg.solve(A, b), 1.0).reshape(3, 3)
+
+
+def patch_homography(corners, size, dtype=np.float32):
+    """The matrix ``rectify`` takes for a photograph in which the patch's corners sit at the source-pixel positions
+    ``corners`` [4,2] (x, y), in the reference's order top-left, bottom-left, bottom-right, top-right: it sends the
+    destination pixel centres (0, 0), (0, H-1), (W-1, H-1), (W-1, 0) of a ``size`` = (H, W) grid onto them.  One float64 8x8
+    solve, rounded to ``dtype`` once at the end (float32: what the kernel reads; float64: the solve itself)."""
+    H, W = _size(size)
+    if H < 2 or W < 2:
+        raise ValueError("a grid of %dx%d has no four distinct corner centres" % (H, W))
+    corners = np.asarray(corners, np.float64)
+    if corners.shape == (4, 3):         # homogeneous, as the reference's target_points
+        corners = corners[:, :2] / corners[:, 2:3]
+    grid = np.array([[0.0, 0.0], [0.0, H - 1.0], [W - 1.0, H - 1.0], [W - 1.0, 0.0]])
+    return _homography(grid, corners).astype(dtype)
+
+
+def _camera(camera_pos, sensor_size):
+    """(K, R, C): intrinsics, world-to-camera rotation (rows = the camera's axes in world coordinates) and centre of the
+    reference's look-at camera (renderers.py:106-156), float64"""
+    C = np.asarray(camera_pos, np.float64).reshape(3)
+    dist = np.linalg.norm(C)
+    if not dist > 0.0:
+        raise ValueError("the camera cannot sit in the origin it looks at")
+    cz = -C / dist                                          # the principal axis points at the origin
+    cx = np.cross(cz, np.array([0.0, 0.0, 1.0]))            # up is the patch's normal
+    n = np.linalg.norm(cx)
+    cx = np.array([1.0, 0.0, 0.0]) if n == 0.0 else cx / n  # straight overhead (or below): up and axis are parallel
+    cy = np.cross(cz, cx)
+    R = np.stack((cx, cy, cz))
+    sw, sh = float(sensor_size[0]), float(sensor_size[1])
+    K = np.array([[sw / 2.0, 0.0, sw / 2.0], [0.0, sw / 2.0, sh / 2.0], [0.0, 0.0, 1.0]])   # focal length: half the width
+    return K, R, C
+
+
+def camera_corners(camera_pos, sensor_size):
+    """float64 [4,2]: where a camera at ``camera_pos`` that looks at the origin sees the patch corners (-1,1,0), (-1,-1,0),
+    (1,-1,0), (1,1,0) on a sensor of ``sensor_size`` = (width, height) pixels -- the reference's
+    ``OrthoToPerspectiveMapping(camera, sensor_size).target_points`` without the homogeneous column.  The principal axis
+    points at the origin, up is +z (x = (1, 0, 0) straight overhead), the focal length is width / 2 and the principal point
+    the sensor's centre."""
+    K, R, C = _camera(camera_pos, sensor_size)
+    P = K @ np.concatenate((R, (-R @ C)[:, None]), axis=1)
+    world = np.concatenate((_PATCH_CORNERS, np.zeros((4, 1)), np.ones((4, 1))), axis=1)
+    img = (P @ world.T).T
+    return img[:, :2] / img[:, 2:3]
+
+
+def camera_from_corners(corners, sensor_size):
+    """Inverse of ``camera_corners``: the camera position, float64 [3], from the four corner positions by planar pose --
+    the homography G from patch coordinates (X, Y) to pixels is K [r1 r2 t] up to scale, so K^-1 G gives two columns of
+    the rotation and the translation, and the centre is -R^T t.  A first guess for the pose (``tools/fit_photos.py
+    --captured --fit-pose`` refines it); exact for corners that ``camera_corners`` made."""
+    corners = np.asarray(corners, np.float64)
+    if corners.shape == (4, 3):
+        corners = corners[:, :2] / corners[:, 2:3]
+    G = _homography(_PATCH_CORNERS, corners)
+    sw, sh = float(sensor_size[0]), float(sensor_size[1])
+    Kinv = np.array([[2.0 / sw, 0.0, -1.0], [0.0, 2.0 / sw, -sh / sw], [0.0, 0.0, 1.0]])
+    A = Kinv @ G
+    scale = 2.0 / (np.linalg.norm(A[:, 0]) + np.linalg.norm(A[:, 1]))
+    if A[2, 2] < 0.0:               # the patch lies in front of the camera: t_z > 0
+        scale = -scale
+    r1, r2, t = A[:, 0] * scale, A[:, 1] * scale, A[:, 2] * scale
+    R = np.stack((r1, r2, np.cross(r1, r2)), axis=1)
+    return -R.T @ t
+
+
+def perspective_matrix(camera_pos, sensor_size, size, t=1.0, dtype=np.float32):
+    """The matrix ``to_perspective`` hands the kernel: the INVERSE of ``t G + (1 - t) I`` with G the mapping from the pixels
+    of a ``size`` = (H, W) rendering to the sensor of the camera (``patch_homography(camera_corners(...), size)`` in float64)
+    -- the reference's ``apply`` blends its homography with the identity the same way.  t = 0: the identity."""
+    G = patch_homography(camera_corners(camera_pos, sensor_size), size, dtype=np.float64)
+    blend = float(t) * G + (1.0 - float(t)) * np.eye(3)
+    return np.linalg.inv(blend).astype(dtype)
+
+
+# ------------------------------------------------------------------------------------------------ the launch
+
+def _device_matrices(matrices, lead, device):
+    """``matrices`` (tensor or array, [...,3,3] or [...,9] with the photos' leading dimensions, or one [3,3] for all) ->
+    contiguous float32 [P,9] on ``device``"""
+    P = int(np.prod(lead)) if lead else 1
+    m = matrices if isinstance(matrices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(matrices)))
+    if m.shape[-2:] == (3, 3):
+        m = m.reshape(m.shape[:-2] + (9,))
+    if m.shape[-1:] != (9,):
+        raise ValueError("matrices must be [...,3,3] or [...,9], got %s" % (tuple(m.shape),))
+    if m.dim() == 1:
+        m = m.expand(P, 9)
+    elif tuple(m.shape[:-1]) != tuple(lead):
+        raise ValueError("matrices %s do not match the photos' leading dimensions %s" % (tuple(m.shape), tuple(lead)))
+    return m.reshape(P, 9).to(device=device, dtype=torch.float32).contiguous()
+
+
+def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights=True):
+    """Source photographs through one homography each onto a ``size`` = (H, W) (or int) grid, ONE launch.
+
+    ``photos``: a device tensor, uint8 ``[...,Hs,Ws,3]`` (interleaved, what an image decoder returns) or float32
+    ``[...,3,Hs,Ws]``; the leading dimensions ``[B,S]`` or ``[P]`` (or none) are kept.  ``matrices``: ``[...,3,3]`` with the
+    same leading dimensions, or one ``[3,3]`` for all; tensor or array, on any device (see the module's conventions).
+    ``lut``: float32 [256], required for uint8 sources (``gamma_lut()``, ``srgb_lut()``, a camera response) and refused for
+    float ones.  ``clip`` = (lo, hi): a tap with a channel <= lo or >= hi is invalid (codes for uint8 sources, values for
+    float ones; None: off).  ``samples``: k of the k x k sub-samples per pixel, 1, 2 or 4.
+    -> (photos ``[...,3,H,W]``, weights ``[...,H,W]``) float32 on the source's device: what ``PhotoLoss.forward(..., weights)``
+    and ``PhotoFit.step`` accept.  A pixel with any invalid sub-sample -- outside the source, behind the horizon, a NaN or
+    clipped tap -- has values 0 and weight 0, every other weight 1.  ``want_weights=False``: -> (photos, None), the weight
+    plane is never written."""
+    if not isinstance(photos, torch.Tensor):
+        raise TypeError("photos must be a torch.Tensor")
+    if not photos.is_cuda:
+        raise _native.NativeLibraryError(
+            "photos are on %s: the MI355X engine only computes on a ROCm device (no CPU fallback)" % photos.device)
+    if samples not in (1, 2, 4):
+        raise ValueError("samples must be 1, 2 or 4, got %r" % (samples,))
+    Hd, Wd = _size(size)
+    if Hd < 1 or Wd < 1:
+        raise ValueError("size must be at least 1x1")
+    if photos.dtype == torch.uint8:
+        if photos.dim() < 3 or photos.shape[-1] != 3:
+            raise ValueError("uint8 photos must be [...,Hs,Ws,3], got %s" % (tuple(photos.shape),))
+        fmt, lead, (Hs, Ws) = U8_INTERLEAVED, tuple(photos.shape[:-3]), photos.shape[-3:-1]
+        if lut is None:
+            raise ValueError("uint8 photos need a lut (capture.gamma_lut(), capture.srgb_lut() or a camera response)")
+        lut = torch.as_tensor(lut)
+        if lut.dtype != torch.float32 or tuple(lut.shape) != (256,):
+            raise ValueError("lut must be float32 [256]")
+        lut = lut.to(photos.device).contiguous()
+    elif photos.dtype == torch.float32:
+        if photos.dim() < 3 or photos.shape[-3] != 3:
+            raise ValueError("float32 photos must be [...,3,Hs,Ws], got %s" % (tuple(photos.shape),))
+        fmt, lead, (Hs, Ws) = F32_PLANAR, tuple(photos.shape[:-3]), photos.shape[-2:]
+        if lut is not None:
+            raise ValueError("float32 photos are used as they are: no lut")
+    else:
+        raise TypeError("photos must be uint8 [...,Hs,Ws,3] or float32 [...,3,Hs,Ws] (got %s)" % photos.dtype)
+    if clip is None:
+        lo, hi = -math.inf, math.inf
+    else:
+        lo, hi = float(clip[0]), float(clip[1])
+        if math.isnan(lo) or math.isnan(hi):
+            raise ValueError("clip thresholds must not be NaN")
+    P = int(np.prod(lead)) if lead else 1
+    if P < 1 or Hs < 1 or Ws < 1:
+        raise ValueError("photos must not be empty, got %s" % (tuple(photos.shape),))
+    src = photos.contiguous()
+    mats = _device_matrices(matrices, lead, photos.device)
+    out = torch.empty(lead + (3, Hd, Wd), dtype=torch.float32, device=photos.device)
+    weights = torch.empty(lead + (Hd, Wd), dtype=torch.float32, device=photos.device) if want_weights else None
+    _native._call("svbrdf_rectify_photos", photos.device, src.data_ptr(), fmt, P, int(Hs), int(Ws), mats.data_ptr(), Hd, Wd,
+                  int(samples), None if lut is None else lut.data_ptr(), lo, hi, out.data_ptr(),
+                  None if weights is None else weights.data_ptr())
+    return out, weights
+
+
+def to_perspective(renderings, camera_pos, sensor_size, t=1.0, samples=1):
+    """The reference's ``OrthoToPerspectiveMapping(camera, sensor_size).apply(image, t)`` for device tensors: ``renderings``
+    float32 ``[...,3,H,W]`` on the patch grid -> ``[...,3,sensor_size[1],sensor_size[0]]``, the patch as the camera at
+    ``camera_pos`` sees it (one position ``[3]`` for all, or ``[...,3]``: one per image), zeros outside the patch like cv2's
+    constant border.  ``t`` blends the mapping with the identity (the reference's animation parameter).  The float path of
+    ``rectify``'s kernel with the inverse matrix, one launch; bilinear taps (cv2's default interpolation)."""
+    if not isinstance(renderings, torch.Tensor) or renderings.dtype != torch.float32 or renderings.dim() < 3:
+        raise TypeError("renderings must be a float32 [...,3,H,W] tensor")
+    lead, size = tuple(renderings.shape[:-3]), tuple(renderings.shape[-2:])
+    pos = np.asarray(camera_pos.detach().cpu() if isinstance(camera_pos, torch.Tensor) else camera_pos, np.float64)
+    if pos.shape == (3,):
+        mats = perspective_matrix(pos, sensor_size, size, t)
+    elif pos.shape == lead + (3,):
+        mats = np.stack([perspective_matrix(c, sensor_size, size, t) for c in pos.reshape(-1, 3)]).reshape(lead + (3, 3))
+    else:
+        raise ValueError("camera_pos must be [3] or %s, got %s" % (lead + (3,), pos.shape))
+    return rectify(renderings, mats, (int(sensor_size[1]), int(sensor_size[0])), samples=samples, want_weights=False)[0]

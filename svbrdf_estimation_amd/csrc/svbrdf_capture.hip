@@ -1,0 +1,198 @@
+// svbrdf_capture.hip -- translation unit of libsvbrdf_hip.so: captured photographs onto the patch grid (ABI version 8).
+//
+// The photo losses and the photo fit take their photographs as [B,S,3,H,W] float32, linear, on the patch's orthographic
+// pixel grid, with a {0,1} confidence plane beside them.  A captured photograph is a perspective image, usually 8-bit and
+// gamma encoded, much larger than the grid, with clipped highlights and pixels that fall outside the patch.  One launch of
+// k_rectify resamples P source photographs through a 3x3 homography each onto a destination grid with bilinear taps,
+// decodes 8-bit codes through a 256-entry table, and writes the three value planes and the confidence plane.  Run with the
+// inverse matrix the same kernel is the reference's rendering-to-perspective mapping (OrthoToPerspectiveMapping.apply,
+// renderers.py:171-173: cv2.warpPerspective with a constant zero border).
+//
+// Definition (include/svbrdf_hip.h has it in full; tests/capture_checks.py restates it in numpy float32, and the kernel
+// equals that restatement bit for bit).  M = m0..m8, row-major float32, sends a DESTINATION pixel index (x, y, 1) to
+// SOURCE pixel-index coordinates; integer coordinates are pixel centres.  Per sub-sample (i, j) of K x K:
+//     xs = x + ((i + 0.5)/K - 0.5)            ys likewise                     (the offsets are exact)
+//     X = (m0 xs + m1 ys) + m2,  Y = (m3 xs + m4 ys) + m5,  Z = (m6 xs + m7 ys) + m8
+//     u = X / Z,  v = Y / Z
+//     valid  <=>  Z > 0  and  0 <= u <= Ws-1  and  0 <= v <= Hs-1             (false for NaN)
+//     x0 = floor(u), fx = u - x0, x1 = min(x0 + 1, Ws-1); taps a = (y0,x0), b = (y0,x1), c = (y1,x0), d = (y1,x1)
+//     top = a + fx (b - a),  bot = c + fx (d - c),  val = top + fy (bot - top)
+// A pixel's value is the sum of its sub-samples in (j, i) row-major order times 1/K^2; one invalid sub-sample -- by
+// geometry or by a tap that is not finite or beyond the clip thresholds -- makes the pixel's three values and its weight 0.
+//
+// Arithmetic.  Every operation above is ONE individually rounded float32 operation: the unit is built with the Makefile's
+// HIPFLAGS (-ffp-contract=off: no FMA is formed; -fno-fast-math), and no fmaf() is written here.  The two quotients are the
+// language's plain `/`: hipcc's default for float division is the correctly rounded IEEE sequence (v_div_scale /
+// v_div_fmas / v_div_fixup, denormals kept), which the flags above leave in place -- div_rn of svbrdf_kernels.hip is NOT
+// used: it is exact only for operands of moderate magnitude, and M is the caller's.  tests/test_capture_cpu.py holds the
+// compiled kernels to that (two v_div_fixup_f32 per sub-sample, no v_fma / v_mad / v_rcp-only quotient).
+//
+// Addressing.  u and v are clamped IN FLOAT to [0, Ws-1] x [0, Hs-1] (fmaxf / fminf return the other operand for a NaN
+// and saturate +-inf) BEFORE the conversion to int, and an invalid sub-sample addresses texel (0, 0): every load address
+// lies inside the source whatever M holds.  Threads beyond the destination store nothing.
+//
+// Shape of a launch.  One workgroup of 256 threads covers a 64 x 4 tile of one photo's destination: a wave is 64
+// consecutive pixels of ONE row, so each of its four stores (three value planes, the weight plane) is one contiguous
+// 256-byte row segment.  The photo index is blockIdx.z; its nine matrix entries are wave-uniform loads from the [P,9]
+// table (scalar loads; nothing is stored through the scalar unit).  The uint8 kernels stage the 256-entry table in LDS once
+// per workgroup (1 KiB).  Neighbouring destination pixels hit neighbouring source texels, so the gather leans on L2: the
+// source is not tiled through LDS.  No atomics, no scratch, no second pass.  It includes svbrdf_kernels.hip with
+// SVBRDF_TU = 4 for the host-side helpers only (fail, aligned, launch_status): none of its kernels, none of its entries.
+#define SVBRDF_TU 4
+#include "svbrdf_kernels.hip"
+
+namespace {
+
+constexpr int kRectifyTileW = 64;       // one wave = one row segment
+constexpr int kRectifyTileH = 4;        // four waves per workgroup
+constexpr int kRectifyMaxDim = 32768;   // Hs, Ws, Hd, Wd: (float)(Ws - 1) is exact and every index fits an int
+
+struct RectifyClip {
+    float lo_f, hi_f;       // float sources: a tap is invalid at or below lo_f, at or above hi_f, or if not finite
+    int lo_i, hi_i;         // uint8 sources: the same thresholds as integers (floor(lo), ceil(hi), within [-1, 256])
+};
+
+// one tap of one channel -> its value, and `ok` cleared if the tap rule refuses it
+template <bool U8>
+__device__ __forceinline__ float rectify_tap(const void *src, size_t index, const float *s_lut, const RectifyClip &clip,
+                                             bool &ok)
+{
+    if (U8) {
+        const int code = static_cast<const unsigned char *>(src)[index];
+        ok = ok && code > clip.lo_i && code < clip.hi_i;
+        return s_lut[code];
+    }
+    const float t = static_cast<const float *>(src)[index];
+    // (t > -inf and t < +inf already refuse NaN and the infinities; the finiteness test is written out for thresholds
+    // that are themselves finite on one side only)
+    ok = ok && t > clip.lo_f && t < clip.hi_f && fabsf(t) < __builtin_inff();
+    return t;
+}
+
+template <bool U8, int K>
+__global__ __launch_bounds__(kRectifyTileW * kRectifyTileH) void k_rectify(
+    const void *__restrict__ src, const float *__restrict__ matrices, const float *__restrict__ lut, RectifyClip clip,
+    float *__restrict__ out, float *__restrict__ weights_out, int Hs, int Ws, int Hd, int Wd)
+{
+    __shared__ float s_lut[U8 ? 256 : 1];
+    if (U8) {
+        s_lut[threadIdx.x] = lut[threadIdx.x];      // 256 threads, 256 entries
+        __syncthreads();
+    }
+    const int p = blockIdx.z;
+    const int x = blockIdx.x * kRectifyTileW + (threadIdx.x & (kRectifyTileW - 1));
+    const int y = blockIdx.y * kRectifyTileH + (threadIdx.x / kRectifyTileW);
+    if (x >= Wd || y >= Hd) return;                 // (behind the barrier)
+    const float *m = matrices + (size_t)p * 9;
+    const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5], m6 = m[6], m7 = m[7], m8 = m[8];
+    const float wmax = (float)(Ws - 1), hmax = (float)(Hs - 1);
+    const size_t plane = (size_t)Hs * Ws;
+    const size_t base = (size_t)p * 3 * plane;      // first element of photo p in either layout
+    float acc[3] = {0.0f, 0.0f, 0.0f};
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            const float xs = (float)x + ((i + 0.5f) / K - 0.5f);        // the offset is a compile-time constant, exact
+            const float ys = (float)y + ((j + 0.5f) / K - 0.5f);
+            const float X = (m0 * xs + m1 * ys) + m2;
+            const float Y = (m3 * xs + m4 * ys) + m5;
+            const float Z = (m6 * xs + m7 * ys) + m8;
+            float u = X / Z, v = Y / Z;
+            const bool valid = Z > 0.0f && u >= 0.0f && u <= wmax && v >= 0.0f && v <= hmax;
+            ok = ok && valid;
+            u = valid ? u : 0.0f;
+            v = valid ? v : 0.0f;
+            u = fminf(fmaxf(u, 0.0f), wmax);        // in float, before the conversion: NaN and +-inf cannot reach it
+            v = fminf(fmaxf(v, 0.0f), hmax);
+            const float x0f = floorf(u), y0f = floorf(v);
+            const float fx = u - x0f, fy = v - y0f;
+            const int x0 = (int)x0f, y0 = (int)y0f;
+            const int x1 = min(x0 + 1, Ws - 1), y1 = min(y0 + 1, Hs - 1);
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch) {
+                size_t ia, ib, ic, id;
+                if (U8) {       // [P,Hs,Ws,3]
+                    ia = base + ((size_t)y0 * Ws + x0) * 3 + ch;
+                    ib = base + ((size_t)y0 * Ws + x1) * 3 + ch;
+                    ic = base + ((size_t)y1 * Ws + x0) * 3 + ch;
+                    id = base + ((size_t)y1 * Ws + x1) * 3 + ch;
+                } else {        // [P,3,Hs,Ws]
+                    const size_t cb = base + ch * plane;
+                    ia = cb + (size_t)y0 * Ws + x0;
+                    ib = cb + (size_t)y0 * Ws + x1;
+                    ic = cb + (size_t)y1 * Ws + x0;
+                    id = cb + (size_t)y1 * Ws + x1;
+                }
+                const float a = rectify_tap<U8>(src, ia, s_lut, clip, ok);
+                const float b = rectify_tap<U8>(src, ib, s_lut, clip, ok);
+                const float c = rectify_tap<U8>(src, ic, s_lut, clip, ok);
+                const float d = rectify_tap<U8>(src, id, s_lut, clip, ok);
+                const float top = a + fx * (b - a);
+                const float bot = c + fx * (d - c);
+                const float val = top + fy * (bot - top);
+                acc[ch] = (i == 0 && j == 0) ? val : acc[ch] + val;
+            }
+        }
+    }
+    const size_t dplane = (size_t)Hd * Wd;
+    const size_t pix = (size_t)y * Wd + x;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+        out[((size_t)p * 3 + ch) * dplane + pix] = ok ? acc[ch] * (1.0f / (K * K)) : 0.0f;
+    if (weights_out) weights_out[(size_t)p * dplane + pix] = ok ? 1.0f : 0.0f;
+}
+
+template <bool U8>
+void launch_rectify(int k, dim3 grid, hipStream_t st, const void *src, const float *matrices, const float *lut,
+                    RectifyClip clip, float *out, float *weights_out, int Hs, int Ws, int Hd, int Wd)
+{
+    const dim3 block(kRectifyTileW * kRectifyTileH);
+    if (k == 1) k_rectify<U8, 1><<<grid, block, 0, st>>>(src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+    else if (k == 2) k_rectify<U8, 2><<<grid, block, 0, st>>>(src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+    else k_rectify<U8, 4><<<grid, block, 0, st>>>(src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+}
+
+}  // namespace
+
+extern "C" {
+
+int svbrdf_rectify_photos(const void *src, int src_format, int P, int Hs, int Ws, const float *matrices, int Hd, int Wd,
+                          int k, const float *lut, float clip_lo, float clip_hi, float *out, float *weights_out,
+                          void *stream)
+{
+    const char *who = "svbrdf_rectify_photos";
+    char text[200];
+    const auto bad = [&](int code, const char *what) {
+        std::snprintf(text, sizeof(text), "%s: %s", who, what);
+        return fail(code, text);
+    };
+    if (src_format != SVBRDF_RECTIFY_F32_PLANAR && src_format != SVBRDF_RECTIFY_U8_INTERLEAVED)
+        return bad(SVBRDF_ERR_DIMS, "src_format must be SVBRDF_RECTIFY_F32_PLANAR (0) or SVBRDF_RECTIFY_U8_INTERLEAVED (1)");
+    const bool u8 = src_format == SVBRDF_RECTIFY_U8_INTERLEAVED;
+    if (!src || !matrices || !out) return bad(SVBRDF_ERR_NULL, "src, matrices and out are required");
+    if (u8 && !lut) return bad(SVBRDF_ERR_NULL, "uint8 sources need the 256-entry lut");
+    if (k != 1 && k != 2 && k != 4) return bad(SVBRDF_ERR_DIMS, "k must be 1, 2 or 4 (k x k sub-samples per pixel)");
+    if (P < 1 || Hs < 1 || Ws < 1 || Hd < 1 || Wd < 1) return bad(SVBRDF_ERR_DIMS, "P, Hs, Ws, Hd, Wd must be at least 1");
+    if (P > 65535) return bad(SVBRDF_ERR_DIMS, "P exceeds 65535 (grid.z)");
+    if (Hs > kRectifyMaxDim || Ws > kRectifyMaxDim || Hd > kRectifyMaxDim || Wd > kRectifyMaxDim)
+        return bad(SVBRDF_ERR_DIMS, "Hs, Ws, Hd, Wd must not exceed 32768");
+    if (clip_lo != clip_lo || clip_hi != clip_hi) return bad(SVBRDF_ERR_DIMS, "clip_lo and clip_hi must not be NaN");
+    if (!aligned(matrices, 4) || !aligned(out, 4) || !aligned(weights_out, 4) || !aligned(lut, 4) || (!u8 && !aligned(src, 4)))
+        return bad(SVBRDF_ERR_ALIGN, "float pointers must be 4-byte aligned");
+    RectifyClip clip;
+    clip.lo_f = clip_lo;
+    clip.hi_f = clip_hi;
+    // code <= clip_lo <=> code <= floor(clip_lo), code >= clip_hi <=> code >= ceil(clip_hi), for integer codes: exact
+    clip.lo_i = (int)std::floor(std::fmin(std::fmax((double)clip_lo, -1.0), 256.0));
+    clip.hi_i = (int)std::ceil(std::fmin(std::fmax((double)clip_hi, -1.0), 256.0));
+    const dim3 grid((unsigned)((Wd + kRectifyTileW - 1) / kRectifyTileW), (unsigned)((Hd + kRectifyTileH - 1) / kRectifyTileH),
+                    (unsigned)P);
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (u8) launch_rectify<true>(k, grid, st, src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+    else launch_rectify<false>(k, grid, st, src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+    return launch_status(who);
+}
+
+}  // extern "C"

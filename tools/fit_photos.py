@@ -2,6 +2,7 @@
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
                                [--fit-exposure] [--fit-pose [--pose-lr 0.002]] [--fused-step [--steps-per-launch K]]
+                               [--captured [--sensor 640x480] [--clip 250]]
 
 Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
 each from ``synthesis.render_inputs`` (the scene table is what that call draws from torch's global generator: the same seed
@@ -31,6 +32,16 @@ are printed from the returned tensor -- the maps' error only where a launch ends
 and the time per step is the time of a launch divided by its steps.  Maps only: refused with ``--fit-pose`` or
 ``--fit-exposure`` -- the table's gradient sums over all pixels, and applying it between two steps of one launch would need a
 grid barrier.
+
+``--captured``: the fit is run twice, once on the photographs as synthesised on the patch grid (as without the option) and
+once on what a camera would deliver.  Every synthesised photograph is pushed through ``capture.to_perspective`` from its own
+camera position onto a ``--sensor`` of WIDTHxHEIGHT pixels, encoded with gamma 2.2 to 8 bits on the host, and ingested again
+with ``capture.rectify``: the homography of the patch corners the camera sees (``camera_corners`` / ``patch_homography``),
+``gamma_lut()``, 2 x 2 sub-samples, codes of 0 (the border around the patch) and of ``--clip`` or more (clipped highlights)
+refused.  The material of this mode is band limited (the generator's maps at an eighth of the size, enlarged): photographs
+of per-pixel white noise survive no resampling.  The second fit runs on the rectified photographs WITH their weights through the same path as the first
+(``--fused-step`` included); with ``--fit-pose`` its camera positions start from ``capture.camera_from_corners`` instead of
+from the perturbed truth.  The share of zero weights and both final map errors are printed at the end.
 """
 import argparse
 import os
@@ -45,7 +56,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import synth  # noqa: E402
-from svbrdf_estimation_amd import _native, fitting, losses, renderers, synthesis  # noqa: E402
+from svbrdf_estimation_amd import _native, capture, fitting, losses, renderers, synthesis  # noqa: E402
 
 
 def main():
@@ -63,6 +74,9 @@ def main():
     ap.add_argument("--pose-lr", type=float, default=0.002)
     ap.add_argument("--fused-step", action="store_true", help="loss, gradient, Adam update and clamp of the maps in one launch")
     ap.add_argument("--steps-per-launch", type=int, default=None, help="with --fused-step: this many consecutive steps per launch")
+    ap.add_argument("--captured", action="store_true", help="fit a second time, on 8-bit perspective photographs rectified onto the grid")
+    ap.add_argument("--sensor", default="640x480", help="with --captured: the camera's sensor, WIDTHxHEIGHT pixels")
+    ap.add_argument("--clip", type=int, default=250, help="with --captured: codes of this value or more are clipped highlights")
     args = ap.parse_args()
     if args.steps_per_launch is not None and not args.fused_step:
         ap.error("--steps-per-launch needs --fused-step: only the fused step runs several steps in a launch")
@@ -75,23 +89,72 @@ def main():
     dev = torch.device("cuda:0")
     B, H, S = args.batch, args.size, args.photos
     truth = torch.from_numpy(synth.make_maps(args.seed, B, H)).to(dev)
+    if args.captured:
+        truth = band_limited_maps(args.seed, B, H).to(dev)
     torch.manual_seed(args.seed)
     torch.cuda.manual_seed(args.seed)
     photos = synthesis.render_inputs(truth, S, use_augmentation=True, noise="device" if args.noise else None)
     torch.manual_seed(args.seed)
     table = torch.stack([synthesis.input_scene_table(S, True) for _ in range(B)], dim=0).to(dev)
-    log_e, hidden = None, None
+    hidden = None
     if args.fit_exposure:
         if args.noise:
             ap.error("--fit-exposure renders its photographs noise-free: not combined with --noise")
         hidden = 0.5 + 1.5 * torch.from_numpy(synth.uniform01(args.seed + 2000, (B, S, 3))).to(dev)
         scaled = torch.cat((table[..., :6], table[..., 6:] * hidden), dim=-1)
         photos = _native.render_fwd(truth, scaled).clamp_(0.0, 1.0)
-        log_e = torch.zeros((B, S, 3), device=dev, requires_grad=True)
+    if not args.captured:
+        return fit(args, dev, truth, photos, table, hidden)
+    on_grid = fit(args, dev, truth, photos, table, hidden)
+    rectified, weights, cameras = ingest(args, dev, photos, table)
+    seen = weights.unsqueeze(2).expand_as(photos) > 0
+    print("--- the same fit on the captured photographs: %s sensor, gamma 2.2, 8 bits, rectified with 2 x 2 sub-samples; "
+          "%.2f %% of the weights are zero, %.2f %% of the pixels are seen by no photograph; mean |rectified - on the grid| %.5f "
+          "where the weight is 1" % (args.sensor, 100.0 * (weights == 0).float().mean().item(),
+                                     100.0 * (weights.amax(dim=1) == 0).float().mean().item(),
+                                     (rectified - photos)[seen].abs().mean().item()))
+    captured = fit(args, dev, truth, rectified, table, hidden, weights, cameras)
+    print("final mean |d,r,s - truth|: on the grid %.5f, captured %.5f (zero weights: %.2f %%)" % (
+        on_grid, captured, 100.0 * (weights == 0).float().mean().item()))
+
+
+def band_limited_maps(seed, B, H, cell=8):
+    """--captured: the generator's maps at 1 / `cell` of the size, enlarged bilinearly, normals renormalised.  The generator
+    draws every pixel independently; photographs of white noise survive no resampling at all (rectifying them gives the mean
+    of unrelated neighbours), so the captured mode -- both of its fits -- uses a material whose features span a few pixels."""
+    small = torch.from_numpy(synth.make_maps(seed, B, max(H // cell, 2)))
+    maps = torch.nn.functional.interpolate(small, size=(H, H), mode="bilinear", align_corners=True)
+    maps[:, :3] = maps[:, :3] / maps[:, :3].norm(dim=1, keepdim=True)
+    return maps.contiguous()
+
+
+def ingest(args, dev, photos, table):
+    """--captured: the photographs as a camera at each photo's position delivers them -- perspective, gamma 2.2, 8 bits --
+    and back onto the grid -> (photos [B,S,3,H,W], weights [B,S,H,W], the camera positions recovered from the corners)"""
+    sensor = tuple(int(v) for v in args.sensor.lower().split("x"))
+    B, S, H = photos.shape[0], photos.shape[1], photos.shape[-1]
+    cams = table[..., :3].cpu().numpy().astype(np.float64)
+    seen = capture.to_perspective(photos, cams, sensor)                                  # [B,S,3,sensor h,sensor w]
+    codes = (seen.clamp(0.0, 1.0).cpu().double().pow(1.0 / 2.2) * 255.0).round().to(torch.uint8)
+    images = codes.permute(0, 1, 3, 4, 2).contiguous().to(dev)                           # what an image decoder returns: HWC
+    corners = [capture.camera_corners(c, sensor) for c in cams.reshape(-1, 3)]
+    matrices = np.stack([capture.patch_homography(c, (H, H)) for c in corners]).reshape(B, S, 3, 3)
+    rectified, weights = capture.rectify(images, matrices, H, lut=capture.gamma_lut(), clip=(0, args.clip), samples=2)
+    recovered = np.stack([capture.camera_from_corners(c, sensor) for c in corners]).reshape(B, S, 3)
+    return rectified, weights, torch.from_numpy(recovered).float().to(dev)
+
+
+def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None):
+    """one fit of perturbed maps to `photos` (with `weights`, if given) -> the final mean |d,r,s - truth|"""
+    B, H, S = args.batch, args.size, args.photos
+    log_e = torch.zeros((B, S, 3), device=dev, requires_grad=True) if args.fit_exposure else None
     pos, true_pos, colour = None, table[..., :6], table[..., 6:]
     if args.fit_pose:
         off = 1.0 + 0.06 * (torch.from_numpy(synth.uniform01(args.seed + 3000, (B, S, 6))).to(dev) - 0.5)
-        pos = (true_pos * off).requires_grad_(True)                          # every coordinate up to 3 % off
+        pos = true_pos * off                                                 # every coordinate up to 3 % off
+        if cameras is not None:                                              # --captured: the camera from the corners it saw
+            pos = torch.cat((cameras, pos[..., 3:]), dim=-1)
+        pos = pos.requires_grad_(True)
     start = truth.clone()
     jitter = torch.from_numpy(synth.uniform01(args.seed + 1000, (B, 9, H, H))).to(dev) - 0.5
     start[:, 3:] = (start[:, 3:] + 0.3 * jitter).clamp_(0.02, 0.98)        # diffuse, roughness, specular off by up to 0.15
@@ -111,7 +174,7 @@ def main():
         ", positions fitted too (lr %g)" % args.pose_lr if args.fit_pose else "", args.lr,
         ", the whole step in one launch" if fit is not None else ""))
     if args.steps_per_launch is not None:
-        return run_in_launches(args, fit, photos, table, x, truth)
+        return run_in_launches(args, fit, photos, table, x, truth, weights)
     t_last, step_ms = None, []
     for step in range(args.steps):
         if step % args.print_every == 0:
@@ -121,17 +184,17 @@ def main():
                 step_ms.append(1e3 * (now - t_last) / args.print_every)
             t_last = now
         if fit is not None and opt is None:
-            loss = fit.step(photos, table)
+            loss = fit.step(photos, table, weights)
         elif fit is not None:
             opt.zero_grad(set_to_none=True)
             scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
-            loss = fit.step(photos, scenes, None, exposure=None if log_e is None else log_e.exp())
+            loss = fit.step(photos, scenes, weights, exposure=None if log_e is None else log_e.exp())
             loss.backward()
             opt.step()
         else:
             opt.zero_grad(set_to_none=True)
             scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
-            loss = fn(x, photos, scenes) if log_e is None else fn(x, photos, scenes, None, log_e.exp())
+            loss = fn(x, photos, scenes, weights) if log_e is None else fn(x, photos, scenes, weights, log_e.exp())
             loss.backward()
             opt.step()
             with torch.no_grad():
@@ -145,9 +208,10 @@ def main():
                 step, loss.item(), err, gains, "  %.3f ms/step" % step_ms[-1] if step_ms else ""))
     if step_ms:
         print("median %.3f ms per step (loss + backward + Adam + clamp, host included)" % float(np.median(step_ms)))
+    return (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
 
 
-def run_in_launches(args, fit, photos, table, x, truth):
+def run_in_launches(args, fit, photos, table, x, truth, weights=None):
     """--steps-per-launch: the fit in launches of K steps, the losses read from the tensors the launches return"""
     K, launch_ms = args.steps_per_launch, []
     print("%d steps per launch" % K)
@@ -155,7 +219,7 @@ def run_in_launches(args, fit, photos, table, x, truth):
         n = min(K, args.steps - first)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        losses_dev = fit.steps(n, photos, table)
+        losses_dev = fit.steps(n, photos, table, weights)
         torch.cuda.synchronize()
         ms = 1e3 * (time.perf_counter() - t0) / n
         if first:                               # (the first launch loads the code object)
@@ -170,6 +234,7 @@ def run_in_launches(args, fit, photos, table, x, truth):
                 print("step %4d  loss %.6f%s  %.3f ms/step" % (step, loss, err, ms))
     if launch_ms:
         print("median %.3f ms per step (%d steps per launch, host included)" % (float(np.median(launch_ms)), K))
+    return (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
 
 
 if __name__ == "__main__":
