@@ -412,6 +412,51 @@ SVBRDF_API int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg
                                                      float *grad_out, float *grad_scenes, void *workspace,
                                                      size_t workspace_bytes, int B, int S, int H, int W, void *stream);
 
+/* One step of the fit WITH A SMOOTHNESS PRIOR ACROSS PIXELS, still ONE launch.  Every entry above is pixel-local: a pixel
+ * that no photograph sees (weight 0 in all of them) has an all-zero gradient and never moves.  The objective here is
+ *   photo loss + R(x),  R(x) = sum_ch lambda[ch] / (B H W) sum_b ( sum_{i, j < W-1} |x[b,ch,i,j+1] - x[b,ch,i,j]|
+ *                                                                  + sum_{i < H-1, j} |x[b,ch,i+1,j] - x[b,ch,i,j]| )
+ * an anisotropic total variation per plane, no wrap-around, no coupling between items.  The gradient the step uses, per
+ * element, with g the photo gradient exactly as svbrdf_photo_fit_adam_step[_scene_grad] forms it:
+ *   s(a, b) = +1 if a > b, -1 if a < b, 0 if a == b, NaN if unordered     (compares of the stored values, no subtraction)
+ *   k       = s(x, left) + s(x, right) + s(x, up) + s(x, down)            (a neighbour outside the patch contributes 0)
+ *   g'      = g + (c[ch] (float)k)                                        (two individually rounded float32 operations)
+ *   c[ch]   = (float)((double)lambda[ch] / ((double)B H W))               (on the host, rounded once)
+ * and g' goes through the three lines of svbrdf_photo_fit_adam_step unchanged.
+ *  - `smooth_host`: lambda, 12 finite floats >= 0 ON THE HOST, one per plane (REQUIRED; they ride in the launch's argument
+ *    block).  A channel with lambda == 0 skips the term: no neighbour is read and g' = g bit for bit, so all-zero lambda
+ *    leaves maps_out, exp_avg and exp_avg_sq EQUAL BIT FOR BIT to the twin entry's in-place results.
+ *  - OUT OF PLACE for the maps: the neighbours are read as they were before the update, and other workgroups own them.
+ *    `maps_in` is only read and is left intact; `maps_out` [B,12,H,W] receives x' and MUST NOT OVERLAP maps_in
+ *    (SVBRDF_ERR_DIMS).  exp_avg and exp_avg_sq are element-wise and stay in place.
+ *  - loss_out[0] is the PHOTO TERM alone, bit for bit the twin entry's: R is never reduced on the device.  grad_out, if
+ *    given, is g'.  grad_scenes (the _scene_grad form) is the twin's bit for bit: R does not depend on the table.
+ *  - A NaN neighbour makes the term NaN, as torch.sign(nan) does: that channel of the four neighbouring pixels becomes NaN
+ *    in this step and the NaN spreads by one pixel per step; channels with lambda == 0 are untouched.  The NaN pixel itself:
+ *    its 36 values become NaN, as in the twins.  Two EQUAL INFINITE neighbours give 0 where torch.sign(inf - inf) gives NaN.
+ *  - Error codes, all before any launch and with no device buffer touched: smooth_host NULL or a lambda that is NaN,
+ *    negative or infinite, then an overlap of maps_in and maps_out: SVBRDF_ERR_DIMS; then the twin entry's checks in its
+ *    order (maps_out is required and 4-byte aligned like maps_in).
+ * `workspace`: the twin's (svbrdf_rendering_loss_workspace_bytes; svbrdf_photo_scene_grad_workspace_bytes), same contract.
+ * Not offered: several steps in one launch (a second step needs the neighbours' UPDATED values: a grid barrier), a head
+ * form, isotropic or Huber variants, R reduced on the device.  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect the two by
+ * symbol presence. */
+SVBRDF_API int svbrdf_photo_fit_smooth_adam_step(const float *maps_in, float *maps_out, float *exp_avg, float *exp_avg_sq,
+                                                 const float *photos, const float *weights, int weight_planes,
+                                                 const float *scenes, const float *xrow, float eps,
+                                                 const float *smooth_host, const float *bounds_host, float lr,
+                                                 float beta1, float beta2, float adam_eps, int step, float *loss_out,
+                                                 float *grad_out, void *workspace, size_t workspace_bytes, int B, int S,
+                                                 int H, int W, void *stream);
+SVBRDF_API int svbrdf_photo_fit_smooth_adam_step_scene_grad(const float *maps_in, float *maps_out, float *exp_avg,
+                                                            float *exp_avg_sq, const float *photos, const float *weights,
+                                                            int weight_planes, const float *scenes, const float *xrow,
+                                                            float eps, const float *smooth_host, const float *bounds_host,
+                                                            float lr, float beta1, float beta2, float adam_eps, int step,
+                                                            float *loss_out, float *grad_out, float *grad_scenes,
+                                                            void *workspace, size_t workspace_bytes, int B, int S, int H,
+                                                            int W, void *stream);
+
 /* CAPTURED PHOTOGRAPHS ONTO THE PATCH GRID, ONE launch: what stands between a camera image -- a perspective view, usually
  * 8-bit and gamma encoded, far larger than the grid, with clipped highlights and pixels outside the patch -- and the
  * `photos` / `weights` of the entries above.  P source photographs are resampled through a 3x3 homography each onto an

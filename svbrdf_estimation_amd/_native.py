@@ -54,6 +54,10 @@ _LOSS_FIT = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_in
 _LOSS_FIT_SG = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_int] + [_fp] * 4 + [_size] + _DIMS
 # ... adam_eps, first_step, n_steps, losses, ws, bytes: the step's list with (first_step, n_steps) for `step` and no gradient
 _LOSS_FIT_STEPS = [_fp] * 5 + [_int] + [_fp] * 2 + [_float, _fp] + [_float] * 4 + [_int] * 2 + [_fp] * 2 + [_size] + _DIMS
+# maps_in, maps_out, exp_avg, exp_avg_sq, photos, weights, planes, scenes, xrow, eps, smooth, bounds, lr, ...: the step's
+# list with maps_out behind the maps and the 12 lambdas in front of the bounds; the same with grad_scenes
+_LOSS_FIT_SMOOTH = [_fp] * 6 + [_int] + [_fp] * 2 + [_float, _fp, _fp] + [_float] * 4 + [_int] + [_fp] * 3 + [_size] + _DIMS
+_LOSS_FIT_SMOOTH_SG = [_fp] * 6 + [_int] + [_fp] * 2 + [_float, _fp, _fp] + [_float] * 4 + [_int] + [_fp] * 4 + [_size] + _DIMS
 _LOSS_L1 = [_fp] * 4 + [_float] * 3 + [_fp] * 3 + [_size] + _DIMS     # ... eps, l1_weight, eps_l1 ...
 _INPUTS = [_fp] * 3 + [_u64] * 2 + [_fp] * 2 + _DIMS
 # name -> (restype, argtypes) of every SVBRDF_API function of include/svbrdf_hip.h, applied once in _load();
@@ -92,6 +96,8 @@ SIGNATURES = {
     "svbrdf_photo_fit_adam_scalars": (_int, [_float] * 3 + [_int, _fp]),
     "svbrdf_photo_fit_adam_step": (_int, _LOSS_FIT),
     "svbrdf_photo_fit_adam_step_scene_grad": (_int, _LOSS_FIT_SG),
+    "svbrdf_photo_fit_smooth_adam_step": (_int, _LOSS_FIT_SMOOTH),
+    "svbrdf_photo_fit_smooth_adam_step_scene_grad": (_int, _LOSS_FIT_SMOOTH_SG),
     "svbrdf_photo_fit_steps_workspace_bytes": (_size, [_int] * 5),
     "svbrdf_photo_fit_adam_steps": (_int, _LOSS_FIT_STEPS),
     # src, format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi, out, weights_out, stream
@@ -661,6 +667,35 @@ def photo_fit_adam_step(maps, exp_avg, exp_avg_sq, photos, scenes, step, lr=1e-2
                                       extra, (grad_scenes.data_ptr(),), "svbrdf_photo_scene_grad_workspace_bytes")
         return loss, grad, grad_scenes
     return _fused_loss_call("svbrdf_photo_fit_adam_step", maps, exp_avg, scenes, floats, want_grad, *dims, extra)
+
+
+def photo_fit_smooth_adam_step(maps, maps_out, exp_avg, exp_avg_sq, photos, scenes, step, smooth, lr=1e-2, betas=(0.9, 0.999),
+                               adam_eps=1e-8, bounds=None, eps=0.1, weights=None, want_grad=False, want_scene_grad=False):
+    """One step of a photo fit with the smoothness prior across pixels (svbrdf_photo_fit_smooth_adam_step): the step of
+    photo_fit_adam_step with the gradient of sum_ch smooth[ch] TV(maps[:, ch]) / (B H W) added to the photo gradient, in
+    ONE launch, OUT OF PLACE for the maps: `maps` is only read, `maps_out` -- a contiguous float32 device tensor of the
+    same shape that shares no memory with `maps` -- receives the updated maps; `exp_avg`, `exp_avg_sq` are updated in
+    place.  `smooth`: a ctypes array of 12 floats on the host, one lambda per plane, finite and >= 0; a plane with 0
+    skips the term.  The other arguments as photo_fit_adam_step.  -> (photo loss at `maps`, [1] device tensor -- the
+    prior's own value is not part of it, fitting.smoothness gives it --; the gradient WITH the prior's term, or None).
+
+    ``want_scene_grad=True``: svbrdf_photo_fit_smooth_adam_step_scene_grad -> (loss, grad or None, grad_scenes [B,S,9]),
+    grad_scenes bit for bit photo_fit_adam_step's: the prior does not depend on the table."""
+    scenes, dims, extra, keep = _fit_operands(maps, exp_avg, exp_avg_sq, photos, scenes, weights)
+    _require_device_f32(maps_out, "maps_out")
+    if not maps_out.is_contiguous() or maps_out.shape != maps.shape or maps_out.device != maps.device:
+        raise ValueError("maps_out receives the updated maps: a contiguous tensor of the maps' shape on their device")
+    if smooth is None:
+        raise ValueError("smooth must be a ctypes array of 12 floats")
+    eps_, *adam = _adam_floats(eps, bounds, lr, betas, adam_eps, step)
+    floats = (eps_, ctypes.cast(smooth, _fp), *adam)
+    extra = (exp_avg.data_ptr(),) + extra
+    if want_scene_grad:
+        grad_scenes = torch.empty_like(scenes)
+        loss, grad = _fused_loss_call("svbrdf_photo_fit_smooth_adam_step_scene_grad", maps, maps_out, scenes, floats, want_grad,
+                                      *dims, extra, (grad_scenes.data_ptr(),), "svbrdf_photo_scene_grad_workspace_bytes")
+        return loss, grad, grad_scenes
+    return _fused_loss_call("svbrdf_photo_fit_smooth_adam_step", maps, maps_out, scenes, floats, want_grad, *dims, extra)
 
 
 PHOTO_FIT_MAX_STEPS = 64        # SVBRDF_PHOTO_FIT_MAX_STEPS of include/svbrdf_hip.h

@@ -99,15 +99,22 @@ __device__ __forceinline__ void adam_epilogue(float *maps, float *exp_avg, float
     }
 }
 
+// What fit_body and joint_body do with a pixel behind the scene loop.  This one: the gradient to grad_out if given, then
+// adam_epilogue on `maps` itself.  A unit that includes this file may pass an update of its own, called as
+// update(b, plane, pix, ps) and then in charge of grad_out too (svbrdf_photo_fit_smooth.hip: `maps` is then only read).
+struct UpdateInPlace {
+    static constexpr bool in_place = true;
+};
+
 // One thread = one pixel, all S renders of it and its 36 values of maps and state; workgroup = 256 pixels of one item, as
 // photo_loss_body<true, false, false, WEIGHTED>.
-template <bool WEIGHTED>
+template <bool WEIGHTED, typename Update = UpdateInPlace>
 __device__ __forceinline__ void fit_body(float *maps, float *exp_avg, float *exp_avg_sq, const float *__restrict__ photos,
                                          const float *__restrict__ weights, int weight_planes,
                                          const float *__restrict__ scenes, const float *__restrict__ xrow, float eps,
                                          float inv_count, double loss_scale, float fixed_scale, const AdamArgs &adam,
                                          float *grad_out, unsigned long long *__restrict__ ws,
-                                         float *__restrict__ loss_out, int S, int H, int W)
+                                         float *__restrict__ loss_out, int S, int H, int W, const Update &update = {})
 {
     const size_t plane = (size_t)H * W;
     const size_t pix = (size_t)blockIdx.x * kLossThreads + threadIdx.x;
@@ -131,8 +138,12 @@ __device__ __forceinline__ void fit_body(float *maps, float *exp_avg, float *exp
         else
             lsum = photo_scene_loop<3, true, 3, WEIGHTED>(ps.mi, ps.x, ps.y, scp, nullptr, pp, plane, pix, S, eps, inv_count,
                                                           ps.acc, wp, wstride, ps.poison);
-        if (grad_out) store_grads_k3(grad_out + (size_t)b * 12 * plane, plane, pix, ps.acc);
-        adam_epilogue(maps, exp_avg, exp_avg_sq, b, plane, pix, ps, adam);
+        if constexpr (Update::in_place) {
+            if (grad_out) store_grads_k3(grad_out + (size_t)b * 12 * plane, plane, pix, ps.acc);
+            adam_epilogue(maps, exp_avg, exp_avg_sq, b, plane, pix, ps, adam);
+        } else {
+            update(b, plane, pix, ps);
+        }
     }
     {
         __shared__ float wave_part[kLossThreads / 64];

@@ -40,14 +40,17 @@
 
 namespace {
 
-template <bool WEIGHTED>
+// (`update`: what a live lane does with its pixel behind the loop, UpdateInPlace of svbrdf_photo_fit.hip unless a unit that
+// includes this file passes its own)
+template <bool WEIGHTED, typename Update = UpdateInPlace>
 __device__ __forceinline__ void joint_body(float *maps, float *exp_avg, float *exp_avg_sq, const float *__restrict__ photos,
                                            const float *__restrict__ weights, int weight_planes,
                                            const float *__restrict__ scenes, const float *__restrict__ xrow, float eps,
                                            float inv_count, double loss_scale, float fixed_scale, double grad_scale,
                                            float per_count, const AdamArgs &adam, float *grad_out,
                                            float *__restrict__ grad_scenes, unsigned long long *__restrict__ ws,
-                                           float *__restrict__ loss_out, int S, int H, int W)
+                                           float *__restrict__ loss_out, int S, int H, int W,
+                                           const Update &update = {})
 {
     float *sums = pose_lds();
     const size_t plane = (size_t)H * W;
@@ -83,9 +86,13 @@ __device__ __forceinline__ void joint_body(float *maps, float *exp_avg, float *e
             if (!(c > 0.0f && c < __builtin_inff())) lsum = __builtin_nanf("");
         }
         if (wi.live) {
-            if (grad_out) store_grads_k3(grad_out + (size_t)b * 12 * plane, plane, wi.pix, ps.acc);
             // the fit step's update, for the lanes that own a pixel ONLY
-            adam_epilogue(maps, exp_avg, exp_avg_sq, b, plane, wi.pix, ps, adam);
+            if constexpr (Update::in_place) {
+                if (grad_out) store_grads_k3(grad_out + (size_t)b * 12 * plane, plane, wi.pix, ps.acc);
+                adam_epilogue(maps, exp_avg, exp_avg_sq, b, plane, wi.pix, ps, adam);
+            } else {
+                update(b, plane, wi.pix, ps);
+            }
         } else {
             lsum -= lsum;       // +0; a NaN stays
         }
@@ -110,6 +117,10 @@ __device__ __forceinline__ void joint_body(float *maps, float *exp_avg, float *e
         });
 }
 
+// svbrdf_photo_fit_smooth.hip includes this file for joint_body only (and, through it, the two units above): its kernels and
+// entry points are its own
+#ifndef SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY
+
 #define SVBRDF_JOINT_KERNEL(NAME, WEIGHTED)                                                                           \
     __global__ SVBRDF_PHOTO_LOSS_ATTRS void NAME(float *maps, float *exp_avg, float *exp_avg_sq,                      \
                                                  const float *__restrict__ photos, const float *__restrict__ weights, \
@@ -129,8 +140,11 @@ SVBRDF_JOINT_KERNEL(k_joint_fit, false)
 SVBRDF_JOINT_KERNEL(k_joint_fit_weighted, true)
 #undef SVBRDF_JOINT_KERNEL
 
+#endif  // SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY
+
 }  // namespace
 
+#ifndef SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY
 extern "C" {
 
 int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg, float *exp_avg_sq, const float *photos,
@@ -161,3 +175,4 @@ int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg, float *ex
 }
 
 }  // extern "C"
+#endif  // SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY

@@ -17,6 +17,10 @@ on chip between the steps, bit for bit the n single steps.
 (csrc/svbrdf_photo_fit_pose.hip) and the loss it returns carries it to autograd -- towards the table and the gains only,
 never towards the maps, which the launch has already updated.
 
+``PhotoFit(maps, smooth=...)`` couples neighbouring pixels: an anisotropic total-variation prior on the maps
+(``smoothness``) whose gradient joins the photo gradient inside the same ONE launch (csrc/svbrdf_photo_fit_smooth.hip).
+Without it a pixel that no photograph sees never moves.
+
 ``composed_step`` is the same step in stock torch ops and the specification of the fused one.
 """
 import ctypes
@@ -59,6 +63,43 @@ def _check_bounds(bounds):
     return b
 
 
+def _check_smooth(smooth):
+    """``smooth`` -> None or a host float64 [12] tensor of lambdas, one per plane: 4 values (one per map group: normal,
+    diffuse, roughness, specular) are expanded x3"""
+    if smooth is None:
+        return None
+    lam = torch.as_tensor(smooth, dtype=torch.float64, device="cpu").reshape(-1)
+    if lam.numel() == 4:
+        lam = lam.repeat_interleave(3)
+    if lam.numel() != 12:
+        raise ValueError("smooth must be None, 4 values (normal, diffuse, roughness, specular) or 12 (one per plane), got %d"
+                         % lam.numel())
+    if not torch.isfinite(lam).all() or (lam < 0).any():
+        raise ValueError("smooth must hold finite values >= 0")
+    return lam.contiguous()
+
+
+def smoothness(maps, lam):
+    """The smoothness prior R(x) of a ``[B,12,H,W]`` map tensor in stock torch ops, differentiable, any dtype and device --
+    THE SPECIFICATION of what ``PhotoFit(smooth=lam)`` adds to the photo loss, and what to call to monitor it:
+
+        R(x) = sum_ch lam[ch] / (B H W) sum_b ( sum_{i, j<W-1} |x[b,ch,i,j+1] - x[b,ch,i,j]|
+                                              + sum_{i<H-1, j} |x[b,ch,i+1,j] - x[b,ch,i,j]| )
+
+    an anisotropic total variation per plane, no wrap-around, no coupling between items.  ``lam``: 12 finite values >= 0,
+    or 4 (one per map group, expanded x3).  lam[ch] / (B H W) is formed in double and rounded once to the maps' dtype.
+    -> 0-dim tensor."""
+    if maps.dim() != 4 or maps.shape[1] != 12:
+        raise ValueError("maps must be [B,12,H,W]")
+    lam = _check_smooth(lam)
+    if lam is None:
+        raise ValueError("lam must be 4 or 12 values")
+    B, _, H, W = maps.shape
+    scale = (lam / float(B * H * W)).to(device=maps.device, dtype=maps.dtype)
+    tv = (maps[:, :, :, 1:] - maps[:, :, :, :-1]).abs().sum(dim=(0, 2, 3)) + (maps[:, :, 1:, :] - maps[:, :, :-1, :]).abs().sum(dim=(0, 2, 3))
+    return (tv * scale).sum()
+
+
 def _wants_grad(scenes, exposure):
     """a step's loss is differentiable: grad mode is on and the scene table (a tensor) or the exposure requires grad"""
     return torch.is_grad_enabled() and ((isinstance(scenes, torch.Tensor) and scenes.requires_grad)
@@ -85,7 +126,7 @@ class _StepLoss(torch.autograd.Function):
 
 
 def composed_step(maps, exp_avg, exp_avg_sq, step, photos, scenes, weights=None, lr=1e-2, betas=(0.9, 0.999), eps=1e-8,
-                  bounds=None, loss_eps=0.1, renderer=None, exposure=None):
+                  bounds=None, loss_eps=0.1, renderer=None, exposure=None, smooth=None):
     """One step of the fit in stock torch ops -- THE SPECIFICATION of ``PhotoFit.step``: the gradient g of
     ``losses.PhotoLoss(renderer, loss_eps)(maps, photos, scenes, weights)``, then per element, each operation rounded in
     the maps' dtype,
@@ -102,19 +143,27 @@ def composed_step(maps, exp_avg, exp_avg_sq, step, photos, scenes, weights=None,
 
     With grad mode on and a ``scenes`` tensor or an ``exposure`` that requires grad, the returned loss carries its graph
     towards them -- ``d loss / d scenes`` and ``d loss / d exposure`` at the maps before the update, as ``PhotoLoss``
-    defines them -- and not towards the maps; otherwise it is detached."""
+    defines them -- and not towards the maps; otherwise it is detached.
+
+    ``smooth``: None, or 4 / 12 lambdas: the gradient is that of the photo loss + ``smoothness(maps, smooth)``, the prior's
+    added to the photo gradient on the planes whose lambda is not 0 (the others keep g bit for bit; all zeros is None).
+    The loss returned stays the photo term."""
     _check_hyper(lr, betas, eps)
     bounds = _check_bounds(bounds)
+    smooth = _check_smooth(smooth)
+    if smooth is not None and not smooth.any():
+        smooth = None
     fn = losses.PhotoLoss(renderer if renderer is not None else renderers.LocalRenderer(), loss_eps)
     wanted = []
     if _wants_grad(scenes, exposure):
         wanted = [t for t in (scenes, exposure) if isinstance(t, torch.Tensor) and t.requires_grad]
     update = lambda: _composed_update(fn, maps, exp_avg, exp_avg_sq, step, photos, scenes, weights, exposure, lr, betas, eps,
-                                      bounds, wanted)
+                                      bounds, wanted, smooth)
     return _StepLoss.apply(update, *wanted) if wanted else update()[0]
 
 
-def _composed_update(fn, maps, exp_avg, exp_avg_sq, step, photos, scenes, weights, exposure, lr, betas, eps, bounds, wanted):
+def _composed_update(fn, maps, exp_avg, exp_avg_sq, step, photos, scenes, weights, exposure, lr, betas, eps, bounds, wanted,
+                     smooth=None):
     """composed_step's body -> (the detached loss, d loss / d t for every t of ``wanted``, None where no gradient reaches
     t).  With nothing wanted the table and the gains are constants, whatever requires grad."""
     x = maps.detach().clone().requires_grad_(True)
@@ -125,6 +174,9 @@ def _composed_update(fn, maps, exp_avg, exp_avg_sq, step, photos, scenes, weight
         loss = fn(x, photos, scenes, weights, exposure)
         # (a plugin renderer works with scene objects: no gradient reaches the table, as in PhotoLoss)
         g, *grads = torch.autograd.grad(loss, [x] + wanted, allow_unused=True)
+        if smooth is not None:
+            prior, = torch.autograd.grad(smoothness(x, smooth), [x])
+            g = torch.where((smooth != 0).to(g.device).view(1, 12, 1, 1), g + prior, g)
     c1, c2, step_size, rsb2 = adam_scalars(lr, betas[0], betas[1], step, maps.dtype)
     with torch.no_grad():
         m = exp_avg.mul_(betas[0]).add_(g * c1)
@@ -152,6 +204,14 @@ class PhotoFit:
     steps; ``bounds``: None, or ``[12,2]`` (lo, hi) per channel applied to the updated maps, +-inf = none on that side;
     ``loss_eps``: PhotoLoss's eps; ``renderer``: None = this package's ``LocalRenderer``.
 
+    ``smooth``: None, or the lambdas of the smoothness prior across pixels -- 4 values (normal, diffuse, roughness,
+    specular) or 12 (one per plane), finite and >= 0, reassignable like ``bounds``.  The objective is then the photo loss
+    + ``smoothness(maps, smooth)``; the loss ``step`` returns stays the photo term.  On the fused path the step is still
+    ONE launch (svbrdf_photo_fit_smooth_adam_step[_scene_grad]), out of place for the maps -- a pixel's neighbours must be
+    read as they were before the update -- into a spare buffer this object owns, then copied back: ``maps`` is updated in
+    place as ever.  ``steps(n)`` alternates between the two buffers, n launches and one copy only when n is odd.  None or
+    all zeros: the entries without the prior.
+
     The optimiser state has ``torch.optim.Adam``'s names and meaning, readable and assignable: ``fit.exp_avg``,
     ``fit.exp_avg_sq`` (tensors like ``maps``) and the number of updates made so far, ``fit.state["step"]`` -- ``state`` is
     the dict ``Adam.state[p]`` would be (the counter has no attribute of its own: ``step`` is the method).
@@ -161,7 +221,7 @@ class PhotoFit:
     gradient, see ``step``).  Anything else -- float64 maps, CPU tensors, a plugin renderer -- is ``composed_step``, the
     specification of the fused step."""
 
-    def __init__(self, maps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, bounds=None, loss_eps=0.1, renderer=None):
+    def __init__(self, maps, lr=1e-2, betas=(0.9, 0.999), eps=1e-8, bounds=None, loss_eps=0.1, renderer=None, smooth=None):
         if not isinstance(maps, torch.Tensor) or maps.dim() != 4 or maps.shape[1] != 12 or not maps.dtype.is_floating_point:
             raise ValueError("maps must be a floating-point [B,12,H,W] tensor")
         if not maps.is_contiguous():
@@ -171,6 +231,8 @@ class PhotoFit:
         self.lr, self.betas, self.eps, self.loss_eps = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(loss_eps)
         self.renderer = renderer if renderer is not None else renderers.LocalRenderer()
         self.bounds = bounds
+        self.smooth = smooth
+        self._spare = None
         self.state = {"step": 0, "exp_avg": torch.zeros_like(maps.detach()), "exp_avg_sq": torch.zeros_like(maps.detach())}
 
     exp_avg = property(lambda self: self.state["exp_avg"], lambda self, t: self.state.__setitem__("exp_avg", t))
@@ -185,6 +247,23 @@ class PhotoFit:
         self._bounds = _check_bounds(value)
         # the fused step takes them from the host, 24 floats in the launch's argument block
         self._bounds_c = None if self._bounds is None else (ctypes.c_float * 24)(*self._bounds.reshape(-1).tolist())
+
+    @property
+    def smooth(self):
+        return self._smooth
+
+    @smooth.setter
+    def smooth(self, value):
+        self._smooth = _check_smooth(value)
+        # the fused step takes the lambdas from the host, 12 floats in the launch's argument block; None: no prior
+        on = self._smooth is not None and bool(self._smooth.any())
+        self._smooth_c = (ctypes.c_float * 12)(*self._smooth.tolist()) if on else None
+
+    def _spare_for(self, x):
+        """the buffer the out-of-place step writes: like ``x``, owned by this object, never the user's tensor"""
+        if self._spare is None or self._spare.shape != x.shape or self._spare.device != x.device or self._spare.dtype != x.dtype:
+            self._spare = torch.empty_like(x)
+        return self._spare
 
     def uses_fused_kernel(self):
         return (losses.PhotoLoss(self.renderer).uses_fused_kernel() and self.maps.is_cuda
@@ -236,20 +315,29 @@ class PhotoFit:
         fused = self._fused_inputs(x, photos, scenes, weights, exposure, constants=False)
         if fused is None:
             loss = composed_step(x, self.exp_avg, self.exp_avg_sq, t, photos, scenes, weights, self.lr, self.betas, self.eps,
-                                 self._bounds, self.loss_eps, self.renderer, exposure)
+                                 self._bounds, self.loss_eps, self.renderer, exposure, self._smooth)
         else:
             photos, weights, table, want = fused
-            args = (x, self.exp_avg, self.exp_avg_sq, photos)
-            rest = (t, self.lr, self.betas, self.eps, self._bounds_c, self.loss_eps, weights)
+            rest = (self.lr, self.betas, self.eps, self._bounds_c, self.loss_eps, weights)
+
+            def launch(table, **kw):
+                if self._smooth_c is None:
+                    return _native.photo_fit_adam_step(x, self.exp_avg, self.exp_avg_sq, photos, table, t, *rest, **kw)
+                # out of place with the prior: into the spare buffer, then back -- ``maps`` is updated in place
+                spare = self._spare_for(x)
+                out = _native.photo_fit_smooth_adam_step(x, spare, self.exp_avg, self.exp_avg_sq, photos, table, t,
+                                                         self._smooth_c, *rest, **kw)
+                x.copy_(spare)
+                return out
 
             def joint():
-                loss, _, grad_scenes = _native.photo_fit_adam_step(*args, table.detach(), *rest, want_scene_grad=True)
+                loss, _, grad_scenes = launch(table.detach(), want_scene_grad=True)
                 return loss.view(()), (grad_scenes,)
 
             if want:
                 loss = _StepLoss.apply(joint, table)
             else:
-                loss = _native.photo_fit_adam_step(*args, table, *rest)[0].view(())
+                loss = launch(table)[0].view(())
         self.state["step"] = t
         return loss
 
@@ -260,6 +348,10 @@ class PhotoFit:
         that owns a pixel runs the steps on it with maps and state kept on chip; csrc/svbrdf_photo_fit.hip).  ``lr``,
         ``betas``, ``eps`` and ``bounds`` are read once per call; ``state["step"]`` advances by ``n``.  Anything but float32
         maps on a ROCm device with ``LocalRenderer`` is ``n`` times ``composed_step``.
+
+        With ``smooth`` the fused path is ``n`` LAUNCHES of the single step, alternating between ``maps`` and the spare
+        buffer, and one copy back only when n is odd: a second step needs the neighbours' updated values, which inside one
+        launch would take a grid barrier.
 
         Maps only: the table and the ``exposure`` gains are CONSTANTS of the n steps, whatever requires grad, and the losses
         returned are never differentiable.  The table's gradient is a sum over all pixels of an item; applying it between
@@ -277,11 +369,22 @@ class PhotoFit:
             with torch.no_grad():
                 for k in range(n):
                     seen.append(composed_step(x, self.exp_avg, self.exp_avg_sq, t + k, photos, scenes, weights, lr, betas,
-                                              eps, bounds, self.loss_eps, self.renderer, exposure))
+                                              eps, bounds, self.loss_eps, self.renderer, exposure, self._smooth))
                     self.state["step"] = t + k
             return torch.stack(seen)
         photos, weights, table, _ = fused
         out = []
+        if self._smooth_c is not None:
+            src, dst = x, self._spare_for(x)
+            for k in range(n):
+                out.append(_native.photo_fit_smooth_adam_step(src, dst, self.exp_avg, self.exp_avg_sq, photos, table, t + k,
+                                                              self._smooth_c, lr, betas, eps, bounds_c, self.loss_eps,
+                                                              weights)[0])
+                src, dst = dst, src
+                self.state["step"] = t + k
+            if src is not x:        # n is odd: the result stands in the spare buffer
+                x.copy_(src)
+            return torch.cat(out)
         for first in range(0, n, _native.PHOTO_FIT_MAX_STEPS):
             k = min(_native.PHOTO_FIT_MAX_STEPS, n - first)
             out.append(_native.photo_fit_adam_steps(x, self.exp_avg, self.exp_avg_sq, photos, table, t + first, k, lr, betas,

@@ -2,7 +2,7 @@
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
                                [--fit-exposure] [--fit-pose [--pose-lr 0.002]] [--fused-step [--steps-per-launch K]]
-                               [--captured [--sensor 640x480] [--clip 250]]
+                               [--captured [--sensor 640x480] [--clip 250]] [--smooth LAMBDA]
 
 Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
 each from ``synthesis.render_inputs`` (the scene table is what that call draws from torch's global generator: the same seed
@@ -42,6 +42,14 @@ refused.  The material of this mode is band limited (the generator's maps at an 
 of per-pixel white noise survive no resampling.  The second fit runs on the rectified photographs WITH their weights through the same path as the first
 (``--fused-step`` included); with ``--fit-pose`` its camera positions start from ``capture.camera_from_corners`` instead of
 from the perturbed truth.  The share of zero weights and both final map errors are printed at the end.
+
+``--smooth LAMBDA``: a smoothness prior across pixels on diffuse, roughness and specular (``fitting.smoothness`` with LAMBDA on
+those nine planes, 0 on the normals): the objective is the photo loss + the prior, the loss printed stays the photo term.
+Without it a pixel that no photograph sees -- every weight 0, as under ``--captured`` -- has an all-zero gradient and stays at
+its start value.  On the unfused path the prior is added to the loss with torch ops; with ``--fused-step`` its gradient is
+formed inside the one launch (``fitting.PhotoFit(smooth=...)``), with ``--fit-pose`` / ``--fit-exposure`` too.  With
+``--steps-per-launch K`` it is K LAUNCHES per call of ``steps`` (a second step needs the neighbours' updated values).  The
+map error on the never-seen pixels is printed beside the overall one.
 """
 import argparse
 import os
@@ -77,7 +85,12 @@ def main():
     ap.add_argument("--captured", action="store_true", help="fit a second time, on 8-bit perspective photographs rectified onto the grid")
     ap.add_argument("--sensor", default="640x480", help="with --captured: the camera's sensor, WIDTHxHEIGHT pixels")
     ap.add_argument("--clip", type=int, default=250, help="with --captured: codes of this value or more are clipped highlights")
+    ap.add_argument("--smooth", type=float, default=None, metavar="LAMBDA",
+                    help="smoothness prior across pixels on diffuse, roughness and specular (normals stay at 0); with "
+                         "--steps-per-launch K it is K launches, not one")
     args = ap.parse_args()
+    if args.smooth is not None and not (args.smooth >= 0.0 and args.smooth < float("inf")):
+        ap.error("--smooth must be finite and >= 0")
     if args.steps_per_launch is not None and not args.fused_step:
         ap.error("--steps-per-launch needs --fused-step: only the fused step runs several steps in a launch")
     if args.steps_per_launch is not None and args.steps_per_launch < 1:
@@ -144,9 +157,21 @@ def ingest(args, dev, photos, table):
     return rectified, weights, torch.from_numpy(recovered).float().to(dev)
 
 
+def map_error(x, truth, unseen):
+    """-> (mean |d,r,s - truth| over all pixels, the text that reports it -- with the never-seen pixels' own beside it)"""
+    diff = (x.detach()[:, 3:] - truth[:, 3:]).abs()
+    err = diff.mean().item()
+    text = "mean |d,r,s - truth| %.5f" % err
+    if unseen is not None and unseen.any():
+        text += " (never seen: %.5f)" % diff[unseen.expand_as(diff)].mean().item()
+    return err, text
+
+
 def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None):
     """one fit of perturbed maps to `photos` (with `weights`, if given) -> the final mean |d,r,s - truth|"""
     B, H, S = args.batch, args.size, args.photos
+    unseen = None if weights is None else weights.amax(dim=1, keepdim=True) == 0      # [B,1,H,W]: no photograph sees it
+    lam = None if args.smooth is None else [0.0, args.smooth, args.smooth, args.smooth]
     log_e = torch.zeros((B, S, 3), device=dev, requires_grad=True) if args.fit_exposure else None
     pos, true_pos, colour = None, table[..., :6], table[..., 6:]
     if args.fit_pose:
@@ -165,16 +190,17 @@ def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None):
     fit = None
     if args.fused_step:
         inf = float("inf")
-        fit = fitting.PhotoFit(x.detach(), lr=args.lr, bounds=[[-inf, inf]] * 3 + [[0.0, 1.0]] * 9)
+        fit = fitting.PhotoFit(x.detach(), lr=args.lr, bounds=[[-inf, inf]] * 3 + [[0.0, 1.0]] * 9, smooth=lam)
         # the maps are the fused step's; what is left for torch.optim is the few hundred floats of gains and positions
         groups = ([] if log_e is None else [{"params": [log_e]}]) + ([] if pos is None else [{"params": [pos], "lr": args.pose_lr}])
         opt = torch.optim.Adam(groups, lr=args.lr) if groups else None
     print("fitting %d x [12,%d,%d] maps to %d photographs each (%s%s%s), Adam lr %g%s" % (
         B, H, H, S, "sensor noise" if args.noise else "noise-free", ", hidden gains fitted too" if args.fit_exposure else "",
         ", positions fitted too (lr %g)" % args.pose_lr if args.fit_pose else "", args.lr,
-        ", the whole step in one launch" if fit is not None else ""))
+        ", the whole step in one launch" if fit is not None else "")
+        + ("" if lam is None else ", smoothness prior %g on d, r, s" % args.smooth))
     if args.steps_per_launch is not None:
-        return run_in_launches(args, fit, photos, table, x, truth, weights)
+        return run_in_launches(args, fit, photos, table, x, truth, weights, unseen)
     t_last, step_ms = None, []
     for step in range(args.steps):
         if step % args.print_every == 0:
@@ -195,23 +221,23 @@ def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None):
             opt.zero_grad(set_to_none=True)
             scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
             loss = fn(x, photos, scenes, weights) if log_e is None else fn(x, photos, scenes, weights, log_e.exp())
-            loss.backward()
+            (loss if lam is None else loss + fitting.smoothness(x, lam)).backward()
             opt.step()
             with torch.no_grad():
                 x[:, 3:].clamp_(0.0, 1.0)
         if step % args.print_every == 0 or step == args.steps - 1:
-            err = (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
+            err = map_error(x, truth, unseen)[1]
             gains = "" if log_e is None else "  mean |log e - log e*| %.5f" % (log_e.detach() - hidden.log()).abs().mean().item()
             if pos is not None:
                 gains += "  mean |position - truth| %.5f" % (pos.detach() - true_pos).abs().mean().item()
-            print("step %4d  loss %.6f  mean |d,r,s - truth| %.5f%s%s" % (
+            print("step %4d  loss %.6f  %s%s%s" % (
                 step, loss.item(), err, gains, "  %.3f ms/step" % step_ms[-1] if step_ms else ""))
     if step_ms:
         print("median %.3f ms per step (loss + backward + Adam + clamp, host included)" % float(np.median(step_ms)))
-    return (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
+    return map_error(x, truth, unseen)[0]
 
 
-def run_in_launches(args, fit, photos, table, x, truth, weights=None):
+def run_in_launches(args, fit, photos, table, x, truth, weights=None, unseen=None):
     """--steps-per-launch: the fit in launches of K steps, the losses read from the tensors the launches return"""
     K, launch_ms = args.steps_per_launch, []
     print("%d steps per launch" % K)
@@ -230,11 +256,11 @@ def run_in_launches(args, fit, photos, table, x, truth, weights=None):
             if step % args.print_every == 0 or step == args.steps - 1:
                 err = ""
                 if k == n - 1:
-                    err = "  mean |d,r,s - truth| %.5f behind it" % (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
+                    err = "  %s behind it" % map_error(x, truth, unseen)[1]
                 print("step %4d  loss %.6f%s  %.3f ms/step" % (step, loss, err, ms))
     if launch_ms:
         print("median %.3f ms per step (%d steps per launch, host included)" % (float(np.median(launch_ms)), K))
-    return (x.detach()[:, 3:] - truth[:, 3:]).abs().mean().item()
+    return map_error(x, truth, unseen)[0]
 
 
 if __name__ == "__main__":
