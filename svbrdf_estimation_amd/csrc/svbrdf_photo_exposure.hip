@@ -11,14 +11,13 @@
 // towards light and camera positions is svbrdf_photo_pose.hip's.
 //
 // Four kernels, {maps, head} x {unweighted, weighted}, forward + adjoint, scene table in device memory.  They are
-// svbrdf_photo_loss.hip's flow -- its per-render device functions with EXPO set, included below without its kernels,
-// launcher and entry points -- plus:
+// svbrdf_photo_loss.hip's flow -- the per-render device functions of svbrdf_photo_loss_device.h with EXPO set -- plus:
 //   * per item and wave: the 3 S gains are checked once, a lane each; one that is NaN, infinite or <= 0 poisons the
 //     loss the way a bad weight does;
 //   * per render: the gains (wave-uniform loads) scale the colour (expo_scale); q = w sign(delta)
 //     (1 - ec / b) per channel from registers the loss already holds (no new transcendental, no division) is summed over
 //     the wave and stored, as a fixed-point integer, in the wave's row of the [waves][kExpoSpill + 3 S] LDS sums by one lane (expo_collect);
-//   * behind the loop the launch ends as photo_sums_finish (svbrdf_photo_loss.hip, where the hand-off is explained) ends
+//   * behind the loop the launch ends as photo_sums_finish (svbrdf_photo_loss_device.h, where the hand-off is explained) ends
 //     it: the four waves' integers added to the B S 3 accumulator words of the workspace, the arrival, and the finisher
 //     writes grad_exposure = sum / (2^24 N e), or NaN everywhere when the loss is NaN.
 // Integer sums from the wave on: bitwise reproducible.
@@ -26,9 +25,8 @@
 // grid x 3 S words of workspace, more than the 65 + B S 3 words of the C ABI, and a finisher that reads all of them: not
 // built, and unmeasured.  What the tail of this variant costs is measured: DESIGN.md section 4.5, round 16.)
 // The wave-whole indexing, the set-up of a pixel, the end of the launch and the launcher's checks are shared with
-// svbrdf_photo_pose.hip through svbrdf_photo_loss.hip (wave_index, wave_pixel_setup, photo_sums_finish, plan_sums).
-#define SVBRDF_PHOTO_SHARED_ONLY
-#include "svbrdf_photo_loss.hip"
+// svbrdf_photo_pose.hip through svbrdf_photo_loss_device.h (wave_index, wave_pixel_setup, photo_sums_finish, plan_sums).
+#include "svbrdf_photo_loss_device.h"
 
 namespace {
 

@@ -9,8 +9,8 @@
 // pose loop holds its pixel's complete map gradient in registers behind the loop exactly like the fit kernel's thread.
 //
 // Two kernels, unweighted and weighted, forward + adjoint, scene table in device memory.  Nothing is computed here that
-// the two units do not compute: they are included below without their kernels, launchers and entry points, and what is
-// written out here is the flow alone.
+// the two units do not compute: their device functions come from their headers, and what is written out
+// (joint_body, in svbrdf_photo_fit_pose_device.h, which svbrdf_photo_fit_smooth.hip includes too) is the flow alone.
 //   * per workgroup pose_body<false, WEIGHTED>'s: a wave that holds a pixel runs whole (wave_index), the per-wave rows of
 //     float sums in dynamic LDS, pose_scene_loop<1|3, WEIGHTED> chosen per wave, the colour check, photo_sums_finish<true>
 //     with the pose body's two lambdas.  loss_out, grad_out and grad_scenes are therefore bit for bit those of
@@ -33,93 +33,9 @@
 //   * the Adam update of the [B,S,9] table and of the gains: a few hundred floats whose parameterisation is the user's
 //     (tools/fit_photos.py fits log e, with a learning rate of its own).  A stock torch.optim on them is one or two tiny
 //     launches; this kernel's job is everything that is H W-sized.
-#define SVBRDF_PHOTO_POSE_SHARED_ONLY
-#include "svbrdf_photo_pose.hip"
-#define SVBRDF_PHOTO_FIT_SHARED_ONLY
-#include "svbrdf_photo_fit.hip"
+#include "svbrdf_photo_fit_pose_device.h"
 
 namespace {
-
-// (`update`: what a live lane does with its pixel behind the loop, UpdateInPlace of svbrdf_photo_fit.hip unless a unit that
-// includes this file passes its own)
-template <bool WEIGHTED, typename Update = UpdateInPlace>
-__device__ __forceinline__ void joint_body(float *maps, float *exp_avg, float *exp_avg_sq, const float *__restrict__ photos,
-                                           const float *__restrict__ weights, int weight_planes,
-                                           const float *__restrict__ scenes, const float *__restrict__ xrow, float eps,
-                                           float inv_count, double loss_scale, float fixed_scale, double grad_scale,
-                                           float per_count, const AdamArgs &adam, float *grad_out,
-                                           float *__restrict__ grad_scenes, unsigned long long *__restrict__ ws,
-                                           float *__restrict__ loss_out, int S, int H, int W,
-                                           const Update &update = {})
-{
-    float *sums = pose_lds();
-    const size_t plane = (size_t)H * W;
-    const int b = blockIdx.y;
-    const int n_sums = 9 * S;
-    const WaveIndex wi = wave_index(plane, kPoseSpill + n_sums);
-    float lsum = 0.0f;
-    if (!wi.wave_live) {
-        for (int i = threadIdx.x & 63; i < n_sums; i += 64) sums[wi.row + kPoseSpill + i] = 0.0f;     // a wave without pixels
-    } else {
-        {
-            // diffuse and roughness as stored, to LDS (fit_body; a lane without a pixel stashes the last pixel's, unread)
-            const PlaneBuf xb = plane_buf(maps + (size_t)b * 12 * plane, 12, plane, wi.pix);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) fit_stash(k, plane_load(xb, 3 + k), false);
-        }
-        PixelSetup ps = wave_pixel_setup<false, WEIGHTED>(maps, xrow, b, plane, wi.pix, W);
-        const float *__restrict__ scp = scenes + (size_t)b * n_sums;
-        const float *__restrict__ pp = photos + (size_t)b * S * 3 * plane;
-        const float *__restrict__ wp = WEIGHTED ? weights + (size_t)b * weight_planes * plane : nullptr;
-        const size_t wstride = weight_planes == 1 ? 0 : plane;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) expo_stash(k, ps.mi.r4m[k], false);
-        if (__builtin_amdgcn_readfirstlane((int)__all(ps.tied)))      // wave-uniform, and known to be
-            lsum = pose_scene_loop<1, WEIGHTED>(ps.mi, ps.x, ps.y, scp, pp, plane, wi.pix, S, eps, inv_count, ps.acc, wp,
-                                                wstride, ps.poison, wi.row, wi.live);
-        else
-            lsum = pose_scene_loop<3, WEIGHTED>(ps.mi, ps.x, ps.y, scp, pp, plane, wi.pix, S, eps, inv_count, ps.acc, wp,
-                                                wstride, ps.poison, wi.row, wi.live);
-        // the item's light colours, a lane each (pose_body)
-        for (int i = threadIdx.x & 63; i < 3 * S; i += 64) {
-            const float c = scp[(i / 3) * 9 + 6 + i % 3];
-            if (!(c > 0.0f && c < __builtin_inff())) lsum = __builtin_nanf("");
-        }
-        if (wi.live) {
-            // the fit step's update, for the lanes that own a pixel ONLY
-            if constexpr (Update::in_place) {
-                if (grad_out) store_grads_k3(grad_out + (size_t)b * 12 * plane, plane, wi.pix, ps.acc);
-                adam_epilogue(maps, exp_avg, exp_avg_sq, b, plane, wi.pix, ps, adam);
-            } else {
-                update(b, plane, wi.pix, ps);
-            }
-        } else {
-            lsum -= lsum;       // +0; a NaN stays
-        }
-    }
-    photo_sums_finish<true>(
-        lsum, b, n_sums, fixed_scale, loss_scale, ws, loss_out,
-        [&](int i, bool &sane) {        // the waves' floats, each checked against kPoseWaveLimit, to fixed point (pose_body)
-            long long sum = 0;
-#pragma unroll
-            for (int w = 0; w < kPoseWaves; ++w) {
-                const float v = sums[w * (kPoseSpill + n_sums) + kPoseSpill + i] * per_count;
-                const bool ok = fabsf(v) <= kPoseWaveLimit;         // false for NaN
-                sane = sane && ok;
-                sum += ok ? (long long)v : 0LL;
-            }
-            return sum;
-        },
-        [&](int i, long long sum, bool nan) {
-            float gr = (float)((double)sum * grad_scale);
-            if (i % 9 >= 6) gr *= rcp_(scenes[i]);       // the colour columns hold sum(Q): d / d colour = Q / colour
-            grad_scenes[i] = nan ? __builtin_nanf("") : gr;
-        });
-}
-
-// svbrdf_photo_fit_smooth.hip includes this file for joint_body only (and, through it, the two units above): its kernels and
-// entry points are its own
-#ifndef SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY
 
 #define SVBRDF_JOINT_KERNEL(NAME, WEIGHTED)                                                                           \
     __global__ SVBRDF_PHOTO_LOSS_ATTRS void NAME(float *maps, float *exp_avg, float *exp_avg_sq,                      \
@@ -140,11 +56,8 @@ SVBRDF_JOINT_KERNEL(k_joint_fit, false)
 SVBRDF_JOINT_KERNEL(k_joint_fit_weighted, true)
 #undef SVBRDF_JOINT_KERNEL
 
-#endif  // SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY
-
 }  // namespace
 
-#ifndef SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY
 extern "C" {
 
 int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg, float *exp_avg_sq, const float *photos,
@@ -175,4 +88,3 @@ int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg, float *ex
 }
 
 }  // extern "C"
-#endif  // SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY

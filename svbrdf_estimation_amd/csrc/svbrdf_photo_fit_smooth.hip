@@ -26,7 +26,7 @@
 // place.  loss_out is the photo term alone (R is never reduced on the device); grad_out, if given, is g'.
 //
 // Four kernels: the flow of fit_body (svbrdf_photo_fit.hip) and of joint_body (svbrdf_photo_fit_pose.hip), unweighted and
-// weighted, both included below for their device functions only and called with this unit's update in the place of
+// weighted, both from svbrdf_photo_fit_pose_device.h and called with this unit's update in the place of
 // adam_epilogue.  What is written out here is that update alone (smooth_epilogue, the one copy):
 //   * the neighbours come from LOADS, not from cross-lane moves: four clamped offsets per pixel (pix -+ 1 inside the row,
 //     pix -+ W inside the item; an absent neighbour loads the pixel itself and is masked), and up to 48 buffer loads on the
@@ -41,8 +41,7 @@
 //     across the scene loop (step_put / step_take): the loops have no scalar registers to spare for it.
 // NOT here: several steps in one launch (the second step needs the neighbours' UPDATED values: a grid barrier, which this
 // project does not build), a head form, isotropic or Huber variants, R reduced on the device.
-#define SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY
-#include "svbrdf_photo_fit_pose.hip"
+#include "svbrdf_photo_fit_pose_device.h"
 
 namespace {
 

@@ -17,18 +17,17 @@ import ctypes
 import json
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import capture_checks as cc
+import unit_build
 from svbrdf_estimation_amd import capture
-from test_photo_loss_cpu import _isa_stats, _make_var, needs_hipcc
+from test_photo_loss_cpu import _isa_stats, needs_hipcc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 SHAPES = (((97, 131), (32, 32)), ((480, 640), (64, 64)), ((1200, 1600), (256, 256)))
 
 
@@ -258,9 +257,7 @@ def test_python_layer_rejects_bad_arguments_and_never_falls_back():
 # ------------------------------------------------------------------------------------------------ the kernels
 
 def test_makefile_builds_the_unit_into_the_library_and_earlier_kernels_kept_their_code():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        mk = f.read()
-    assert "$(HIPCC) $(HIPFLAGS) -c -o $@ svbrdf_capture.hip" in mk and "svbrdf_capture.o" in mk.split("OBJS")[1]
+    unit_build.assert_makefile_builds("svbrdf_capture")        # HIPFLAGS and no scheduler option set
     # profiles/r21_capture_codehash.txt: the diff against the parent's listing holds added lines only, the six k_rectify
     with open(os.path.join(ROOT, "profiles", "r21_capture_codehash.txt")) as f:
         text = f.read()
@@ -275,8 +272,7 @@ def test_makefile_builds_the_unit_into_the_library_and_earlier_kernels_kept_thei
 
 
 def test_source_holds_no_inline_assembly_and_no_fma():
-    with open(os.path.join(CSRC, "svbrdf_capture.hip")) as f:
-        src = f.read()
+    src = unit_build.read_csrc("svbrdf_capture.hip")       # (the unit owns no header)
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert not re.search(r"\basm\b|\b(__builtin_)?fmaf?\(|\bfma_\(|\brcp_\(|\bdiv_rn\(|atomic", code)
     assert code.count("fminf(fmaxf(") == 2 and code.index("fminf(fmaxf(") < code.index("(int)x0f")
@@ -286,12 +282,9 @@ def test_source_holds_no_inline_assembly_and_no_fma():
 @needs_hipcc
 def test_compiled_kernels_divide_in_ieee_and_use_no_scratch(tmp_path):
     """the unit compiled exactly as the Makefile compiles it: HIPFLAGS and no scheduler option set"""
-    out = str(tmp_path / "capture.s")
-    cmd = _make_var("HIPCC") + _make_var("HIPFLAGS") + ["-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "svbrdf_capture.hip")]
-    assert "-ffp-contract=off" in cmd and "-fno-fast-math" in cmd
-    subprocess.check_call([c.replace("../../include", os.path.join(ROOT, "include")) for c in cmd], cwd=CSRC, stderr=subprocess.DEVNULL)
-    with open(out) as f:
-        asm = f.read()
+    flags = unit_build.make_var("HIPFLAGS")
+    assert "-ffp-contract=off" in flags and "-fno-fast-math" in flags
+    asm = unit_build.compile_unit_asm(tmp_path, "svbrdf_capture")
     isa_stats = _isa_stats()
     names = sorted(k for k in isa_stats.kernels(asm) if "k_rectify" in k)
     assert len(names) == 6, names

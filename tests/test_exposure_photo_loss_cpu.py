@@ -26,12 +26,12 @@ import exposure_photo_checks as xp
 import head_checks
 import synth
 import tolerances
+import unit_build
 import weighted_photo_checks as wp
-from test_photo_loss_cpu import (PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, PREFETCH_MIN_DISTANCE, _compile, _isa_stats,
-                                 _ToyRenderer, needs_hipcc)
+from test_photo_loss_cpu import (PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, PREFETCH_MIN_DISTANCE, _isa_stats, _ToyRenderer,
+                                 needs_hipcc)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -295,12 +295,12 @@ def test_exposure_is_checked():
 
 @pytest.fixture(scope="module")
 def exposure_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_exposure"), os.path.join(CSRC, "svbrdf_photo_exposure.hip"), "exposure.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_exposure"), "svbrdf_photo_exposure", "SCHED_PHOTO")
 
 
 @pytest.fixture(scope="module")
 def photo_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_exposure_twin"), os.path.join(CSRC, "svbrdf_photo_loss.hip"), "photo.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_exposure_twin"), "svbrdf_photo_loss", "SCHED_PHOTO")
 
 
 def _scene_loops(isa_stats, asm, k):
@@ -373,10 +373,9 @@ def test_photo_loss_unit_alone_still_lists_its_sixteen_kernels(photo_asm):
 
 def test_sources_hold_no_inline_assembly_with_instructions():
     import re
-    for name in ("svbrdf_photo_exposure.hip", "svbrdf_photo_loss.hip"):
-        with open(os.path.join(CSRC, name)) as f:
-            src = f.read()
-        for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
+    for name in ("svbrdf_photo_exposure.hip", "svbrdf_photo_loss.hip", "svbrdf_photo_loss_device.h"):
+        for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', unit_build.read_csrc(name)):
             assert m.group(1) == "", "inline asm with instructions in %s: %r" % (name, m.group(1))
-    with open(os.path.join(CSRC, "svbrdf_photo_exposure.hip")) as f:
-        assert '#define SVBRDF_PHOTO_SHARED_ONLY\n#include "svbrdf_photo_loss.hip"' in f.read()
+    # the unit takes the photo loss's device functions from their header, and the build gives it the photo units' flags
+    unit_build.assert_includes_shared_header("svbrdf_photo_exposure", "svbrdf_photo_loss_device.h")
+    unit_build.assert_makefile_builds("svbrdf_photo_exposure", "SCHED_PHOTO")

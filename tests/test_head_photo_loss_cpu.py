@@ -23,11 +23,11 @@ import head_photo_checks as hp
 import photo_checks
 import synth
 import tolerances
-from test_photo_loss_cpu import (PHOTO_TIED_LOOP_TRANS, PHOTO_TIED_LOOP_VALU_MAX, PREFETCH_MIN_DISTANCE, _compile, _isa_stats,
-                                 _ToyRenderer, needs_hipcc)
+import unit_build
+from test_photo_loss_cpu import (PHOTO_TIED_LOOP_TRANS, PHOTO_TIED_LOOP_VALU_MAX, PREFETCH_MIN_DISTANCE, _isa_stats, _ToyRenderer,
+                                 needs_hipcc)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -232,7 +232,7 @@ def test_headphotoloss_rejects_bad_arguments():
 
 @pytest.fixture(scope="module")
 def photo_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_head_photo"), os.path.join(CSRC, "svbrdf_photo_loss.hip"), "photo.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_head_photo"), "svbrdf_photo_loss", "SCHED_PHOTO")
 
 
 @needs_hipcc

@@ -23,10 +23,10 @@ import torch
 
 import photo_fit_checks as fc
 import synth
-from test_photo_loss_cpu import PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, _compile, _isa_stats, needs_hipcc
+import unit_build
+from test_photo_loss_cpu import PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, _isa_stats, needs_hipcc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -245,7 +245,7 @@ def test_photofit_rejects_bad_arguments_and_never_falls_back():
 
 @pytest.fixture(scope="module")
 def fit_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_fit"), os.path.join(CSRC, "svbrdf_photo_fit.hip"), "fit.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_fit"), "svbrdf_photo_fit", "SCHED_PHOTO")
 
 
 @needs_hipcc
@@ -281,17 +281,16 @@ def test_fit_kernels_resources_and_scene_loops(fit_asm):
 
 @needs_hipcc
 def test_makefile_builds_the_unit_into_the_library():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        mk = f.read()
-    assert "$(HIPCC) $(HIPFLAGS) $(SCHED_PHOTO) -c -o $@ svbrdf_photo_fit.hip" in mk and "svbrdf_photo_fit.o" in mk.split("OBJS")[1]
+    unit_build.assert_makefile_builds("svbrdf_photo_fit", "SCHED_PHOTO")
 
 
 def test_source_holds_no_inline_assembly_with_instructions_and_no_fma():
-    with open(os.path.join(CSRC, "svbrdf_photo_fit.hip")) as f:
-        src = f.read()
+    # the unit and the header it owns; the photo loss's device functions come through that header
+    header = unit_build.assert_includes_shared_header("svbrdf_photo_fit", "svbrdf_photo_fit_device.h")
+    assert '#include "svbrdf_photo_loss_device.h"' in header
+    src = unit_build.read_csrc("svbrdf_photo_fit.hip", "svbrdf_photo_fit_device.h")
     for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
         assert m.group(1) == "", "inline asm with instructions: %r" % m.group(1)
-    assert '#define SVBRDF_PHOTO_SHARED_ONLY\n#include "svbrdf_photo_loss.hip"' in src
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert "fma" not in code and "rcp_" not in code and "rsq_" not in code      # the update is plain, individually rounded operations
     # the single step's epilogue stands once -- the 24 state loads between its two scheduling barriers, adam_channel, the 36

@@ -15,7 +15,6 @@ that needs no GPU:
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -25,10 +24,11 @@ import torch
 import photo_fit_checks as fc
 import photo_fit_pose_checks as jc
 import synth
+import unit_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
-UNIT = "svbrdf_photo_fit_pose.hip"
+UNIT = "svbrdf_photo_fit_pose"
+HEADER = "svbrdf_photo_fit_pose_device.h"     # joint_body: the unit owns it, and the smooth unit includes it too
 needs_hipcc = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs /opt/rocm/bin/hipcc (cross-compiles gfx950)")
 # per render (the pose loops shade one render per trip): tests/test_photo_loss_cpu.py's counts per two renders, halved
 TIED_LOOP_TRANS, UNTIED_LOOP_TRANS = 10, 18
@@ -270,19 +270,6 @@ def test_a_cpu_table_that_requires_grad_is_no_quiet_fallback():
 
 # ------------------------------------------------------------------------------------------------ the kernels
 
-def _make_var(name):
-    return subprocess.check_output(["make", "-s", "-C", CSRC, "print-" + name], text=True).strip().split()
-
-
-def _compile(tmp, source, out_name):
-    out = str(tmp / out_name)
-    cmd = _make_var("HIPCC") + _make_var("HIPFLAGS") + _make_var("SCHED_PHOTO") + ["-S", "--cuda-device-only", "-o", out, source]
-    cmd = [c.replace("../../include", os.path.join(ROOT, "include")) for c in cmd]
-    subprocess.check_call(cmd, cwd=CSRC, stderr=subprocess.DEVNULL)
-    with open(out) as f:
-        return f.read()
-
-
 def _isa_stats():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_stats
@@ -291,7 +278,7 @@ def _isa_stats():
 
 @pytest.fixture(scope="module")
 def joint_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_joint"), os.path.join(CSRC, UNIT), "joint.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_joint"), UNIT, "SCHED_PHOTO")
 
 
 @needs_hipcc
@@ -329,21 +316,18 @@ def test_joint_kernels_resources_scene_loops_and_update(joint_asm):
 
 @needs_hipcc
 def test_makefile_builds_the_unit_into_the_library():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        mk = f.read()
-    assert "$(HIPCC) $(HIPFLAGS) $(SCHED_PHOTO) -c -o $@ " + UNIT in mk and "svbrdf_photo_fit_pose.o" in mk.split("OBJS")[1]
-    assert "-ffp-contract=off" in _make_var("HIPFLAGS")
+    unit_build.assert_makefile_builds(UNIT, "SCHED_PHOTO")
+    assert "-ffp-contract=off" in unit_build.make_var("HIPFLAGS")
 
 
 def test_source_reuses_the_two_units_and_restates_no_arithmetic():
     """no inline assembly with instructions, no cooperative launch; the pose loop and the update are the two units' own,
-    included with their kernels, launchers and entry points left out"""
-    with open(os.path.join(CSRC, UNIT)) as f:
-        src = f.read()
+    shared through their headers, which hold no kernel and no entry point"""
+    header = unit_build.assert_includes_shared_header(UNIT, HEADER)
+    src = unit_build.read_csrc(HEADER, UNIT + ".hip")
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert not re.search(r"\basm\b", code) and "Cooperative" not in code and "grid_group" not in code
-    assert '#define SVBRDF_PHOTO_POSE_SHARED_ONLY\n#include "svbrdf_photo_pose.hip"' in src
-    assert '#define SVBRDF_PHOTO_FIT_SHARED_ONLY\n#include "svbrdf_photo_fit.hip"' in src
+    assert '#include "svbrdf_photo_pose_device.h"\n#include "svbrdf_photo_fit_device.h"' in header
     for used in ("pose_scene_loop<1, WEIGHTED>", "pose_scene_loop<3, WEIGHTED>", "photo_sums_finish<true>", "adam_epilogue(",
                  "adam_args(", "plan_sums(", "fit_stash(", "expo_stash(", "wave_index(", "if (wi.live)"):
         assert used in code, used
@@ -353,11 +337,10 @@ def test_source_reuses_the_two_units_and_restates_no_arithmetic():
     assert re.search(r"if \(wi\.live\) \{[^}]*\badam_epilogue\(", code)
     for own in ("plane_load(mb", "plane_store(", "adam_channel(", "adam_scalars(", "sched_barrier", "const auto bad", "a.lo["):
         assert own not in code, own
-    with open(os.path.join(CSRC, "svbrdf_photo_fit.hip")) as f:
-        fit_code = "\n".join(line.split("//")[0] for line in f.read().splitlines())
+    fit_src = unit_build.read_csrc("svbrdf_photo_fit_device.h", "svbrdf_photo_fit.hip")
+    fit_code = "\n".join(line.split("//")[0] for line in fit_src.splitlines())
     assert (fit_code + code).count("__builtin_amdgcn_sched_barrier(0)") == 2        # the epilogue's pair, once
     assert len(re.findall(r"\bvoid adam_epilogue\(", fit_code)) == 1 and len(re.findall(r"\bint adam_args\(", fit_code)) == 1
     assert re.findall(r"SVBRDF_JOINT_KERNEL\((k_\w+),", code) == ["k_joint_fit", "k_joint_fit_weighted"]
-    for name, guard in (("svbrdf_photo_pose.hip", "SVBRDF_PHOTO_POSE_SHARED_ONLY"), ("svbrdf_photo_fit.hip", "SVBRDF_PHOTO_FIT_SHARED_ONLY")):
-        with open(os.path.join(CSRC, name)) as f:
-            assert "#ifndef " + guard in f.read(), name
+    for unit, shared in (("svbrdf_photo_pose", "svbrdf_photo_pose_device.h"), ("svbrdf_photo_fit", "svbrdf_photo_fit_device.h")):
+        unit_build.assert_includes_shared_header(unit, shared)

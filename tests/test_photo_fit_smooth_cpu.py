@@ -14,7 +14,6 @@ that needs no GPU:
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -25,10 +24,10 @@ import photo_fit_checks as fc
 import photo_fit_pose_checks as jc
 import photo_fit_smooth_checks as sm
 import synth
+import unit_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
-UNIT = "svbrdf_photo_fit_smooth.hip"
+UNIT = "svbrdf_photo_fit_smooth"
 needs_hipcc = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs /opt/rocm/bin/hipcc (cross-compiles gfx950)")
 OTHER_KERNELS = ("k_fit_maps", "k_fit_run", "k_joint_fit", "k_pose", "k_exposure", "k_photo_loss", "k_head_photo", "wphoto")
 
@@ -369,19 +368,6 @@ def test_argument_errors_come_before_any_launch_and_touch_nothing(lib, joint):
 
 # ------------------------------------------------------------------------------------------------ the kernels
 
-def _make_var(name):
-    return subprocess.check_output(["make", "-s", "-C", CSRC, "print-" + name], text=True).strip().split()
-
-
-def _compile(tmp, source, out_name):
-    out = str(tmp / out_name)
-    cmd = _make_var("HIPCC") + _make_var("HIPFLAGS") + _make_var("SCHED_PHOTO") + ["-S", "--cuda-device-only", "-o", out, source]
-    cmd = [c.replace("../../include", os.path.join(ROOT, "include")) for c in cmd]
-    subprocess.check_call(cmd, cwd=CSRC, stderr=subprocess.DEVNULL)
-    with open(out) as f:
-        return f.read()
-
-
 def _isa_stats():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_stats
@@ -390,7 +376,7 @@ def _isa_stats():
 
 @pytest.fixture(scope="module")
 def smooth_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_smooth"), os.path.join(CSRC, UNIT), "smooth.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_smooth"), UNIT, "SCHED_PHOTO")
 
 
 @needs_hipcc
@@ -425,25 +411,22 @@ def test_smooth_kernels_resources_and_update(smooth_asm):
 
 @needs_hipcc
 def test_makefile_builds_the_unit_into_the_library():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        mk = f.read()
-    assert "$(HIPCC) $(HIPFLAGS) $(SCHED_PHOTO) -c -o $@ " + UNIT in mk and "svbrdf_photo_fit_smooth.o" in mk.split("OBJS")[1]
-    assert "-ffp-contract=off" in _make_var("HIPFLAGS")
+    unit_build.assert_makefile_builds(UNIT, "SCHED_PHOTO")
+    assert "-ffp-contract=off" in unit_build.make_var("HIPFLAGS")
 
 
 def test_source_reuses_the_two_flows_and_holds_one_update():
     """no inline assembly with instructions, no cooperative launch, no fma; the scene loops and the launch tails are the fit
-    and the joint unit's own -- included with their kernels and entry points left out -- and the update with the prior's
-    term stands once"""
-    with open(os.path.join(CSRC, UNIT)) as f:
-        src = f.read()
+    and the joint unit's own -- shared through headers that hold no kernel and no entry point -- and the update with the
+    prior's term stands once"""
+    src = unit_build.read_csrc(UNIT + ".hip")        # (the unit owns no header)
     for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
         assert m.group(1) == "", "inline asm with instructions: %r" % m.group(1)
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert "Cooperative" not in code and "grid_group" not in code and "fma" not in code and "sqrtf" not in code
-    assert '#define SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY\n#include "svbrdf_photo_fit_pose.hip"' in src
-    with open(os.path.join(CSRC, "svbrdf_photo_fit_pose.hip")) as f:
-        assert "#ifndef SVBRDF_PHOTO_FIT_POSE_SHARED_ONLY" in f.read()
+    joint = unit_build.assert_includes_shared_header(UNIT, "svbrdf_photo_fit_pose_device.h")
+    assert "void joint_body(" in joint and '#include "svbrdf_photo_fit_device.h"' in joint
+    assert "void fit_body(" in unit_build.assert_includes_shared_header("svbrdf_photo_fit", "svbrdf_photo_fit_device.h")
     for used in ("fit_body<WEIGHTED>(", "joint_body<WEIGHTED>(", "adam_channel(", "adam_args(who,", "fit_weights_check(who,",
                  "plan_sums(who,", "plan_loss(who,", "fit_bad(who,"):
         assert used in code, used

@@ -21,10 +21,10 @@ import torch
 import photo_fit_checks as fc
 import photo_fit_steps_checks as sc
 import synth
-from test_photo_loss_cpu import PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, _compile, _isa_stats, needs_hipcc
+import unit_build
+from test_photo_loss_cpu import PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, _isa_stats, needs_hipcc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -166,7 +166,7 @@ def test_photofit_steps_never_falls_back():
 
 @pytest.fixture(scope="module")
 def fit_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_fit_steps"), os.path.join(CSRC, "svbrdf_photo_fit.hip"), "fit.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_fit_steps"), "svbrdf_photo_fit", "SCHED_PHOTO")
 
 
 @needs_hipcc
@@ -224,21 +224,20 @@ def test_run_kernels_resources_loops_update_and_stores(fit_asm):
 
 @needs_hipcc
 def test_makefile_builds_the_kernels_into_the_library(lib):
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        mk = f.read()
-    assert "$(HIPCC) $(HIPFLAGS) $(SCHED_PHOTO) -c -o $@ svbrdf_photo_fit.hip" in mk and "svbrdf_photo_fit.o" in mk.split("OBJS")[1]
+    unit_build.assert_makefile_builds("svbrdf_photo_fit", "SCHED_PHOTO")
     from svbrdf_estimation_amd import _codehash, _native
     for name in (("k_fit_run", "AdamArgs", "RunScalars", "9k_fit_runE"), ("k_fit_run_weighted",)):
         assert _codehash.kernel_code_sha256(_native.library_path(), name)["bytes"] > 8000, name
 
 
 def test_source_holds_no_inline_assembly_with_instructions_and_no_fma():
-    with open(os.path.join(CSRC, "svbrdf_photo_fit.hip")) as f:
-        src = f.read()
+    # the header the unit owns, then the unit: the several-steps section and its entry are the unit's own
+    header = unit_build.assert_includes_shared_header("svbrdf_photo_fit", "svbrdf_photo_fit_device.h")
+    assert "k_fit_run" not in header and '#include "svbrdf_photo_loss_device.h"' in header
+    src = unit_build.read_csrc("svbrdf_photo_fit_device.h", "svbrdf_photo_fit.hip")
     assert "k_fit_run" in src and "svbrdf_photo_fit_adam_steps" in src
     for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
         assert m.group(1) == "", "inline asm with instructions: %r" % m.group(1)
-    assert '#define SVBRDF_PHOTO_SHARED_ONLY\n#include "svbrdf_photo_loss.hip"' in src
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert "fma" not in code and "rcp_" not in code and "rsq_" not in code      # the update is plain, individually rounded operations
     # no waiting between workgroups: no grid barrier, no cooperative launch, no spinning

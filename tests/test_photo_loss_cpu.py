@@ -10,7 +10,6 @@
 """
 import ctypes
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -20,6 +19,7 @@ import torch
 import photo_checks
 import synth
 import tolerances
+import unit_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
@@ -213,22 +213,9 @@ PHOTO_UNTIED_LOOP_TRANS = 36
 PREFETCH_MIN_DISTANCE = 100          # instructions between the issue of a render's photo loads and the wait that needs them
 
 
-def _make_var(name):
-    return subprocess.check_output(["make", "-s", "-C", CSRC, "print-" + name], text=True).strip().split()
-
-
-def _compile(tmp, source, out_name):
-    out = str(tmp / out_name)
-    cmd = _make_var("HIPCC") + _make_var("HIPFLAGS") + _make_var("SCHED_PHOTO") + ["-S", "--cuda-device-only", "-o", out, source]
-    cmd = [c.replace("../../include", os.path.join(ROOT, "include")) for c in cmd]
-    subprocess.check_call(cmd, cwd=CSRC, stderr=subprocess.DEVNULL)
-    with open(out) as f:
-        return f.read()
-
-
 @pytest.fixture(scope="module")
 def photo_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_photo"), os.path.join(CSRC, "svbrdf_photo_loss.hip"), "photo.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_photo"), "svbrdf_photo_loss", "SCHED_PHOTO")
 
 
 def _isa_stats():
@@ -239,17 +226,29 @@ def _isa_stats():
 
 @needs_hipcc
 def test_makefile_builds_the_unit_into_the_library():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        mk = f.read()
-    assert "$(HIPCC) $(HIPFLAGS) $(SCHED_PHOTO) -c -o $@ svbrdf_photo_loss.hip" in mk and "svbrdf_photo_loss.o" in mk.split("OBJS")[1]
-    assert "-ffp-contract=off" in _make_var("HIPFLAGS")
-    # K3's source is not touched by the feature's translation unit: it only includes it, with SVBRDF_TU = 4
-    with open(os.path.join(CSRC, "svbrdf_photo_loss.hip")) as f:
-        src = f.read()
-    assert '#define SVBRDF_TU 4\n#include "svbrdf_kernels.hip"' in src
+    unit_build.assert_makefile_builds("svbrdf_photo_loss", "SCHED_PHOTO")
+    assert "-ffp-contract=off" in unit_build.make_var("HIPFLAGS")
+    # K3's source is not touched by the feature's translation unit: its header only includes it, with SVBRDF_TU = 4
+    header = unit_build.assert_includes_shared_header("svbrdf_photo_loss", "svbrdf_photo_loss_device.h")
+    assert '#define SVBRDF_TU 4\n#include "svbrdf_kernels.hip"' in header
     import re
-    for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
+    for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', unit_build.read_csrc("svbrdf_photo_loss.hip", "svbrdf_photo_loss_device.h")):
         assert m.group(1) == "", "inline asm with instructions: %r" % m.group(1)
+
+
+def test_units_share_code_through_headers_only():
+    """the layout of csrc/, stated once: no .hip file includes another .hip file except svbrdf_kernels.hip (shared code
+    lives in headers; no file is compiled "minus its kernels"), and no guard macro of that kind is left anywhere"""
+    import re
+    names = sorted(os.listdir(CSRC))
+    units = [n for n in names if n.endswith(".hip")]
+    assert len(units) >= 9, units
+    for name in units:
+        included = re.findall(r'^\s*#\s*include\s*"([^"]+\.hip)"', unit_build.read_csrc(name), flags=re.M)
+        assert all(i == "svbrdf_kernels.hip" for i in included), (name, included)
+    for name in names:
+        if os.path.isfile(os.path.join(CSRC, name)):
+            assert "SHARED_ONLY" not in unit_build.read_csrc(name), name
 
 
 @needs_hipcc
@@ -295,7 +294,7 @@ def test_geometry_path_holds_no_contracted_fma(tmp_path):
     isa_stats = _isa_stats()
     src = tmp_path / "probe.hip"
     src.write_text('#define SVBRDF_ISA_PROBE 1\n#include "%s"\n' % os.path.join(CSRC, "svbrdf_photo_loss.hip"))
-    text = _compile(tmp_path, str(src), "probe.s")
+    text = unit_build.compile_unit_asm(tmp_path, str(src), "SCHED_PHOTO")
     _, _, whole, _, ins, _ = isa_stats.analyse(text, "svbrdf_isa_probe_dot3")
     mns = [mn for _, _, mn, _ in ins if mn and mn.startswith("v_") and not mn.startswith("v_mov")]
     muls = [m for m in mns if m.startswith("v_mul_f32")]

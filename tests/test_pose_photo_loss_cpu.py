@@ -31,12 +31,12 @@ import photo_checks
 import pose_photo_checks as pc
 import synth
 import tolerances
+import unit_build
 import weighted_photo_checks as wp
 from oracle import c_oracle
-from test_photo_loss_cpu import PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, _compile, _isa_stats, needs_hipcc
+from test_photo_loss_cpu import PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, _isa_stats, needs_hipcc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -314,7 +314,7 @@ def test_a_cpu_table_that_requires_grad_is_no_quiet_fallback():
 
 @pytest.fixture(scope="module")
 def pose_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_pose"), os.path.join(CSRC, "svbrdf_photo_pose.hip"), "pose.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_pose"), "svbrdf_photo_pose", "SCHED_PHOTO")
 
 
 @needs_hipcc
@@ -350,14 +350,13 @@ def test_pose_kernels_resources_and_scene_loops(pose_asm):
 
 @needs_hipcc
 def test_makefile_builds_the_unit_into_the_library():
-    with open(os.path.join(CSRC, "Makefile")) as f:
-        mk = f.read()
-    assert "$(HIPCC) $(HIPFLAGS) $(SCHED_PHOTO) -c -o $@ svbrdf_photo_pose.hip" in mk and "svbrdf_photo_pose.o" in mk.split("OBJS")[1]
+    unit_build.assert_makefile_builds("svbrdf_photo_pose", "SCHED_PHOTO")
 
 
 def test_source_holds_no_inline_assembly_with_instructions():
-    with open(os.path.join(CSRC, "svbrdf_photo_pose.hip")) as f:
-        src = f.read()
-    for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
+    for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', unit_build.read_csrc("svbrdf_photo_pose.hip", "svbrdf_photo_pose_device.h")):
         assert m.group(1) == "", "inline asm with instructions: %r" % m.group(1)
-    assert '#define SVBRDF_PHOTO_SHARED_ONLY\n#include "svbrdf_photo_loss.hip"' in src
+    # its own device code in its header, the photo loss's through that header: no kernel and no entry point in either
+    header = unit_build.assert_includes_shared_header("svbrdf_photo_pose", "svbrdf_photo_pose_device.h")
+    assert '#include "svbrdf_photo_loss_device.h"' in header
+    unit_build.assert_includes_shared_header("svbrdf_photo_loss", "svbrdf_photo_loss_device.h")

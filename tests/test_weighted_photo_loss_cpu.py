@@ -26,12 +26,12 @@ import head_checks
 import photo_checks
 import synth
 import tolerances
+import unit_build
 import weighted_photo_checks as wp
-from test_photo_loss_cpu import (PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, PREFETCH_MIN_DISTANCE, _compile, _isa_stats,
-                                 _ToyRenderer, needs_hipcc)
+from test_photo_loss_cpu import (PHOTO_TIED_LOOP_TRANS, PHOTO_UNTIED_LOOP_TRANS, PREFETCH_MIN_DISTANCE, _isa_stats, _ToyRenderer,
+                                 needs_hipcc)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
@@ -281,7 +281,7 @@ WEIGHT_VALU_MARGIN = 12     # per render over the unweighted loop of the same co
 
 @pytest.fixture(scope="module")
 def photo_asm(tmp_path_factory):
-    return _compile(tmp_path_factory.mktemp("isa_wphoto"), os.path.join(CSRC, "svbrdf_photo_loss.hip"), "photo.s")
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa_wphoto"), "svbrdf_photo_loss", "SCHED_PHOTO")
 
 
 def _scene_loops(isa_stats, asm, k):
@@ -341,8 +341,7 @@ def test_weighted_kernels_resources_and_scene_loops(photo_asm):
 
 def test_source_holds_no_inline_assembly_with_instructions():
     import re
-    with open(os.path.join(CSRC, "svbrdf_photo_loss.hip")) as f:
-        src = f.read()
+    src = unit_build.read_csrc("svbrdf_photo_loss.hip", "svbrdf_photo_loss_device.h")
     for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
         assert m.group(1) == "", "inline asm with instructions: %r" % m.group(1)
     assert "template <bool WITH_GRAD, bool EARLY_COORDS, bool HEAD = false, bool WEIGHTED = false>" in src
