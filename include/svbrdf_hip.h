@@ -488,13 +488,58 @@ SVBRDF_API int svbrdf_photo_fit_smooth_adam_step_scene_grad(const float *maps_in
  * arguments: bit for bit the numpy float32 restatement of tests/capture_checks.py.
  * Error codes before any launch: SVBRDF_ERR_DIMS for another src_format, k not in {1, 2, 4}, a size < 1, P > 65535, a size
  * > 32768 or a NaN threshold; SVBRDF_ERR_NULL for src, matrices, out, or lut with uint8 sources; SVBRDF_ERR_ALIGN for a
- * float pointer that is not 4-byte aligned.  No workspace.  No gradient through the resampling.
+ * float pointer that is not 4-byte aligned.  No workspace.  The gradient towards the matrices
+ * is svbrdf_rectify_photos_grad_matrices below; there is none towards the images.
  * ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect it by symbol presence. */
 #define SVBRDF_RECTIFY_F32_PLANAR 0
 #define SVBRDF_RECTIFY_U8_INTERLEAVED 1
 SVBRDF_API int svbrdf_rectify_photos(const void *src, int src_format, int P, int Hs, int Ws, const float *matrices, int Hd,
                                      int Wd, int k, const float *lut, float clip_lo, float clip_hi, float *out,
                                      float *weights_out, void *stream);
+
+/* THE GRADIENT OF svbrdf_rectify_photos' VALUES TOWARDS THE MATRICES, ONE launch: grad_matrices[p, n] = d (sum over `out`
+ * of grad_values * out) / d m_n of photo p, for photometric refinement of a registration (move a photograph's corners until
+ * its rectification agrees with a rendering).  src, src_format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi: the
+ * forward's arguments, unchanged.  grad_values: DEVICE float32 [P,3,Hd,Wd], the gradient towards `out`.  grad_matrices:
+ * DEVICE float32 [P,9], written whole.
+ * Definition.  Per sub-sample (i, j) of pixel (x, y) of photo p, everything up to `val` is the forward's as it stands: xs,
+ * ys, X, Y, Z, u, v, valid; the clamp; x0, y0, fx, fy, x1, y1; the taps a, b, c, d per channel; and the pixel's `ok`, which
+ * is true where the forward's weight is 1 (every sub-sample valid and every tap of every sub-sample passing the tap rule).
+ * The gradient is that of the forward's expression with the cell (x0, y0), `valid` and `ok` held constant: at an integer u
+ * the right-hand derivative, and 0 at u = Ws-1, where the clamped x1 = x0 (likewise v).  With g_ch = grad_values[p,ch,y,x],
+ * every line one individually rounded float32 operation (no fused multiply-add, IEEE division):
+ *   per channel:  ba = b - a;  dc = d - c;  du = ba + fy (dc - ba);  dv = bot - top      (top, bot: the forward's)
+ *   gu = ((g0 du0 + g1 du1) + g2 du2) * (1/k^2);   gv = ((g0 dv0 + g1 dv1) + g2 dv2) * (1/k^2)
+ *   rz = 1 / Z;   pu = gu rz;   pv = gv rz;   pz = -((pu u) + (pv v))
+ *   the nine terms:  pu xs, pu ys, pu,   pv xs, pv ys, pv,   pz xs, pz ys, pz
+ * grad_matrices[p, n] is the sum of term n over all sub-samples of all pixels of photo p whose `ok` holds.  A pixel whose
+ * `ok` is false contributes nothing -- a select, not a multiplication: a NaN in grad_values under it changes no bit.  A
+ * non-finite g under an ok pixel makes the sums it enters non-finite.  A matrix under which no sub-sample is valid (NaN,
+ * +-inf, 1e30, m8 = 0) gives an all-zero row.  Every load address lies inside the source whatever `matrices` holds, as in
+ * the forward.  No gradient towards `src`; none of the weights, which are piecewise constant.
+ * The sum: one launch, no float atomics, bitwise the same in every launch and whatever else runs.  A workgroup covers the
+ * forward's 64 x 4 tile.  A thread adds its k^2 sub-samples in (j, i) order into nine float32 accumulators (k^2 - 1
+ * additions; +0 for a pixel that is not ok or lies beyond the grid); a butterfly over the wave's 64 lanes (lane ^ 32, 16, 8,
+ * 4, 2, 1: 6 additions) and (w0 + w1) + (w2 + w3) over the four waves (2 additions) give the workgroup's nine words, which
+ * go to the workspace with plain stores; behind an agent-scope release a per-photo integer ticket names the photo's last
+ * workgroup, which adds the photo's partials in FLOAT64 -- lane l the workgroups l, l + 64, ... in index order
+ * (x fastest, then y), then the same butterfly over the 64 lane sums -- and rounds ONCE to float32.
+ * SVBRDF_RECTIFY_GRAD_DEPTH bounds the float32 additions any single term passes through: 15 + 6 + 2 = 23 <= 24.  So
+ * with A_n the sum of |term n| over the photo,  |grad_matrices[p, n] - exact sum of the float32 terms| <=
+ * (SVBRDF_RECTIFY_GRAD_DEPTH + 1) * 2^-24 * A_n  (the additions and the one final rounding).
+ * `workspace`: svbrdf_rectify_grad_workspace_bytes(P, Hd, Wd) bytes (0 for sizes outside the limits), 8-byte aligned,
+ * zeroed once by the caller and left zeroed by every completed call: a second call needs no memset.
+ * Error codes before any launch: the forward's, with grad_matrices in the place of `out` and grad_values among the
+ * 4-byte-aligned float pointers; SVBRDF_ERR_NULL for grad_values or workspace; SVBRDF_ERR_ALIGN for a workspace off 8
+ * bytes; SVBRDF_ERR_WORKSPACE for one that is too small.
+ * ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect the two by symbol presence. */
+#define SVBRDF_RECTIFY_GRAD_DEPTH 24
+SVBRDF_API size_t svbrdf_rectify_grad_workspace_bytes(int P, int Hd, int Wd);
+SVBRDF_API int svbrdf_rectify_photos_grad_matrices(const void *src, int src_format, int P, int Hs, int Ws,
+                                                   const float *matrices, int Hd, int Wd, int k, const float *lut,
+                                                   float clip_lo, float clip_hi, const float *grad_values,
+                                                   float *grad_matrices, void *workspace, size_t workspace_bytes,
+                                                   void *stream);
 
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd

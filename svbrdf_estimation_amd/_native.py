@@ -16,6 +16,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SVBRDF_HIP_LIB: load another build of the same ABI (ablation/experiment builds of tools/); default in-tree
 _SO = os.environ.get("SVBRDF_HIP_LIB") or os.path.join(_HERE, "lib", "libsvbrdf_hip.so")
 ABI_VERSION = 8
+# SVBRDF_RECTIFY_GRAD_DEPTH of include/svbrdf_hip.h: the float32 additions a term of svbrdf_rectify_photos_grad_matrices'
+# sums passes through at most (the tests' error bound is built on it)
+RECTIFY_GRAD_DEPTH = 24
 
 _lock = threading.Lock()
 _lib = None
@@ -102,6 +105,10 @@ SIGNATURES = {
     "svbrdf_photo_fit_adam_steps": (_int, _LOSS_FIT_STEPS),
     # src, format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi, out, weights_out, stream
     "svbrdf_rectify_photos": (_int, [_fp, _int, _int, _int, _int, _fp, _int, _int, _int, _fp, _float, _float, _fp, _fp, _fp]),
+    "svbrdf_rectify_grad_workspace_bytes": (_size, [_int] * 3),
+    # src, format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi, grad_values, grad_matrices, ws, bytes, stream
+    "svbrdf_rectify_photos_grad_matrices": (_int, [_fp, _int, _int, _int, _int, _fp, _int, _int, _int, _fp, _float, _float,
+                                                   _fp, _fp, _fp, _size, _fp]),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
     "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
     "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
@@ -732,6 +739,23 @@ def mix_materials(svbrdf0, svbrdf1, alpha):
     a, b, w = svbrdf0.contiguous(), svbrdf1.contiguous(), alpha.contiguous().view(-1)
     out = torch.empty_like(a)
     _call("svbrdf_mix_materials", a.device, a.data_ptr(), b.data_ptr(), w.data_ptr(), out.data_ptr(), B, H, W)
+    return out
+
+
+def rectify_grad_matrices(src, fmt, P, Hs, Ws, matrices, Hd, Wd, k, lut, lo, hi, grad_values):
+    """svbrdf_rectify_photos_grad_matrices, ONE launch: the gradient of ``capture.rectify``'s values towards its float32
+    ``[P,9]`` device matrices, from ``grad_values`` float32 ``[P,3,Hd,Wd]`` contiguous on the device of ``src``; the other
+    arguments as ``capture.rectify`` hands them to the forward.  The scratch is the loss entries' (one buffer per device
+    and stream, zeroed once, left zeroed by every call).  -> float32 ``[P,9]``"""
+    _require_device_f32(grad_values, "grad_values")
+    if tuple(grad_values.shape) != (P, 3, Hd, Wd) or not grad_values.is_contiguous() or grad_values.device != src.device:
+        raise ValueError("grad_values must be contiguous [%d,3,%d,%d] on %s" % (P, Hd, Wd, src.device))
+    nbytes = _load().svbrdf_rectify_grad_workspace_bytes(P, Hd, Wd)
+    ws = _workspace(src.device, nbytes)
+    out = torch.empty((P, 9), dtype=torch.float32, device=src.device)
+    _call("svbrdf_rectify_photos_grad_matrices", src.device, src.data_ptr(), fmt, P, Hs, Ws, matrices.data_ptr(), Hd, Wd, k,
+          None if lut is None else lut.data_ptr(), lo, hi, grad_values.data_ptr(), out.data_ptr(), ws.data_ptr(),
+          ws.numel() * 8)
     return out
 
 

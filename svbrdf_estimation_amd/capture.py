@@ -22,12 +22,23 @@ edge, so the patch corners are the centres of the grid's corner pixels, ``(0, 0)
 in the reference's corner order top-left, bottom-left, bottom-right, top-right.  (The reference's ``get_homography`` stretches
 the ``W`` x ``H`` image over ``[0, W] x [0, H]`` instead, half a pixel off at each edge; what is kept here is the camera.)
 
-No gradient flows through the resampling, neither towards the images nor towards the matrices.  There is no CPU path.
+Gradients.  ``rectify`` is differentiable towards its MATRICES: if ``matrices`` is a tensor that requires grad, the returned
+values carry a ``grad_fn`` whose backward is ONE more launch (svbrdf_rectify_photos_grad_matrices,
+csrc/svbrdf_capture_grad.hip), so a registration can be refined photometrically -- ``corner_matrices`` makes the matrices
+from the four corner positions differentiably, and an optimiser holds the eight corner coordinates:
+
+    corners = torch.tensor(clicked, dtype=torch.float64, requires_grad=True)          # [P,4,2], source pixels
+    photos, weights = capture.rectify(images_u8, capture.corner_matrices(corners, 256), 256, lut=capture.gamma_lut())
+    ((photos - rendering).abs() * weights[:, None]).sum().div(weights.sum()).backward()        # corners.grad
+
+No gradient flows towards the images, the weights are piecewise constant (marked non-differentiable), and there is no double
+backward.  There is no CPU path.
 """
 import math
 
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native
 
@@ -88,6 +99,31 @@ def patch_homography(corners, size, dtype=np.float32):
         corners = corners[:, :2] / corners[:, 2:3]
     grid = np.array([[0.0, 0.0], [0.0, H - 1.0], [W - 1.0, H - 1.0], [W - 1.0, 0.0]])
     return _homography(grid, corners).astype(dtype)
+
+
+def corner_matrices(corners, size):
+    """``patch_homography`` for torch tensors, differentiable: ``corners`` ``[...,4,2]`` (x, y) in source pixels, in the
+    reference's order top-left, bottom-left, bottom-right, top-right -> float64 ``[...,3,3]`` (m8 = 1) on the corners'
+    device, through one batched ``torch.linalg.solve`` of the same 8x8 system.  The eight corner coordinates are what an
+    optimiser should hold: they are in pixels and well conditioned; the nine matrix entries are neither, and scaling a
+    matrix changes nothing (``rectify``'s gradient is orthogonal to it)."""
+    H, W = _size(size)
+    if H < 2 or W < 2:
+        raise ValueError("a grid of %dx%d has no four distinct corner centres" % (H, W))
+    if not isinstance(corners, torch.Tensor) or corners.shape[-2:] != (4, 2):
+        raise ValueError("corners must be a tensor [...,4,2]")
+    c = corners.to(torch.float64)
+    lead = c.shape[:-2]
+    grid = torch.tensor([[0.0, 0.0], [0.0, H - 1.0], [W - 1.0, H - 1.0], [W - 1.0, 0.0]], dtype=torch.float64, device=c.device)
+    x, y = grid[:, 0].expand(lead + (4,)), grid[:, 1].expand(lead + (4,))
+    u, v = c[..., 0], c[..., 1]
+    one, zero = torch.ones_like(u), torch.zeros_like(u)
+    rows_u = torch.stack((x, y, one, zero, zero, zero, -u * x, -u * y), dim=-1)         # [...,4,8]
+    rows_v = torch.stack((zero, zero, zero, x, y, one, -v * x, -v * y), dim=-1)
+    A = torch.stack((rows_u, rows_v), dim=-2).reshape(lead + (8, 8))                    # rows 2k, 2k + 1 as _homography's
+    b = c.reshape(lead + (8, 1))
+    h = torch.linalg.solve(A, b)[..., 0]
+    return torch.cat((h, torch.ones_like(h[..., :1])), dim=-1).reshape(lead + (3, 3))
 
 
 def _camera(camera_pos, sensor_size):
@@ -174,6 +210,10 @@ def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights
     ``photos``: a device tensor, uint8 ``[...,Hs,Ws,3]`` (interleaved, what an image decoder returns) or float32
     ``[...,3,Hs,Ws]``; the leading dimensions ``[B,S]`` or ``[P]`` (or none) are kept.  ``matrices``: ``[...,3,3]`` with the
     same leading dimensions, or one ``[3,3]`` for all; tensor or array, on any device (see the module's conventions).
+    If ``matrices`` is a tensor that requires grad, the values carry a ``grad_fn``: its backward is one launch of
+    svbrdf_rectify_photos_grad_matrices and returns the gradient in the shape, dtype and device of ``matrices`` (one matrix
+    for all: the sum over the photos).  It is the gradient of the values with the tap cell and the weights held constant.
+    There is no gradient towards ``photos``, the weights are non-differentiable, and there is no double backward.
     ``lut``: float32 [256], required for uint8 sources (``gamma_lut()``, ``srgb_lut()``, a camera response) and refused for
     float ones.  ``clip`` = (lo, hi): a tap with a channel <= lo or >= hi is invalid (codes for uint8 sources, values for
     float ones; None: off).  ``samples``: k of the k x k sub-samples per pixel, 1, 2 or 4.
@@ -219,13 +259,51 @@ def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights
     if P < 1 or Hs < 1 or Ws < 1:
         raise ValueError("photos must not be empty, got %s" % (tuple(photos.shape),))
     src = photos.contiguous()
-    mats = _device_matrices(matrices, lead, photos.device)
-    out = torch.empty(lead + (3, Hd, Wd), dtype=torch.float32, device=photos.device)
-    weights = torch.empty(lead + (Hd, Wd), dtype=torch.float32, device=photos.device) if want_weights else None
-    _native._call("svbrdf_rectify_photos", photos.device, src.data_ptr(), fmt, P, int(Hs), int(Ws), mats.data_ptr(), Hd, Wd,
-                  int(samples), None if lut is None else lut.data_ptr(), lo, hi, out.data_ptr(),
+    args = (fmt, P, int(Hs), int(Ws), Hd, Wd, int(samples), lo, hi)
+    if isinstance(matrices, torch.Tensor) and matrices.requires_grad and torch.is_grad_enabled():
+        return _RectifyMatrices.apply(matrices, src, lut, args, lead, want_weights)
+    return _launch_rectify(src, _device_matrices(matrices, lead, photos.device), lut, args, lead, want_weights)
+
+
+def _launch_rectify(src, mats, lut, args, lead, want_weights):
+    """the forward's one launch on checked arguments -> (values, weights or None)"""
+    fmt, P, Hs, Ws, Hd, Wd, k, lo, hi = args
+    out = torch.empty(lead + (3, Hd, Wd), dtype=torch.float32, device=src.device)
+    weights = torch.empty(lead + (Hd, Wd), dtype=torch.float32, device=src.device) if want_weights else None
+    _native._call("svbrdf_rectify_photos", src.device, src.data_ptr(), fmt, P, Hs, Ws, mats.data_ptr(), Hd, Wd, k,
+                  None if lut is None else lut.data_ptr(), lo, hi, out.data_ptr(),
                   None if weights is None else weights.data_ptr())
     return out, weights
+
+
+class _RectifyMatrices(torch.autograd.Function):
+    """``rectify`` for matrices that require grad.  forward: the same launch.  backward: ONE launch of
+    svbrdf_rectify_photos_grad_matrices on ``grad_output.contiguous()`` with the forward's saved arguments; the gradient
+    comes back in the shape, dtype and device of ``matrices`` (one matrix for all: the sum over the photos, added in
+    float64).  Nothing towards the photos; the weights are non-differentiable; no double backward."""
+
+    @staticmethod
+    def forward(ctx, matrices, src, lut, args, lead, want_weights):
+        mats = _device_matrices(matrices.detach(), lead, src.device)
+        out, weights = _launch_rectify(src, mats, lut, args, lead, want_weights)
+        ctx.save_for_backward(src, mats, lut)
+        ctx.args, ctx.like = args, (matrices.shape, matrices.device, matrices.dtype)
+        ctx.shared = matrices.dim() == (2 if matrices.shape[-2:] == (3, 3) else 1)
+        if weights is not None:
+            ctx.mark_non_differentiable(weights)
+        return out, weights
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_weights=None):
+        src, mats, lut = ctx.saved_tensors
+        fmt, P, Hs, Ws, Hd, Wd, k, lo, hi = ctx.args
+        g = grad_out.to(torch.float32).contiguous().reshape(P, 3, Hd, Wd)
+        gm = _native.rectify_grad_matrices(src, fmt, P, Hs, Ws, mats, Hd, Wd, k, lut, lo, hi, g)
+        shape, device, dtype = ctx.like
+        if ctx.shared:
+            gm = gm.to(torch.float64).sum(dim=0)
+        return gm.reshape(shape).to(device=device, dtype=dtype), None, None, None, None, None
 
 
 def to_perspective(renderings, camera_pos, sensor_size, t=1.0, samples=1):

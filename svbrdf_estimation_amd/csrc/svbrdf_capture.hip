@@ -38,36 +38,14 @@
 // per workgroup (1 KiB).  Neighbouring destination pixels hit neighbouring source texels, so the gather leans on L2: the
 // source is not tiled through LDS.  No atomics, no scratch, no second pass.  It includes svbrdf_kernels.hip with
 // SVBRDF_TU = 4 for the host-side helpers only (fail, aligned, launch_status): none of its kernels, none of its entries.
+// The tap rule, the launch shape and the argument checks are in svbrdf_capture_device.h, shared with svbrdf_capture_grad.hip
+// (the gradient towards the matrices).
 #define SVBRDF_TU 4
 #include "svbrdf_kernels.hip"
 
+#include "svbrdf_capture_device.h"
+
 namespace {
-
-constexpr int kRectifyTileW = 64;       // one wave = one row segment
-constexpr int kRectifyTileH = 4;        // four waves per workgroup
-constexpr int kRectifyMaxDim = 32768;   // Hs, Ws, Hd, Wd: (float)(Ws - 1) is exact and every index fits an int
-
-struct RectifyClip {
-    float lo_f, hi_f;       // float sources: a tap is invalid at or below lo_f, at or above hi_f, or if not finite
-    int lo_i, hi_i;         // uint8 sources: the same thresholds as integers (floor(lo), ceil(hi), within [-1, 256])
-};
-
-// one tap of one channel -> its value, and `ok` cleared if the tap rule refuses it
-template <bool U8>
-__device__ __forceinline__ float rectify_tap(const void *src, size_t index, const float *s_lut, const RectifyClip &clip,
-                                             bool &ok)
-{
-    if (U8) {
-        const int code = static_cast<const unsigned char *>(src)[index];
-        ok = ok && code > clip.lo_i && code < clip.hi_i;
-        return s_lut[code];
-    }
-    const float t = static_cast<const float *>(src)[index];
-    // (t > -inf and t < +inf already refuse NaN and the infinities; the finiteness test is written out for thresholds
-    // that are themselves finite on one side only)
-    ok = ok && t > clip.lo_f && t < clip.hi_f && fabsf(t) < __builtin_inff();
-    return t;
-}
 
 template <bool U8, int K>
 __global__ __launch_bounds__(kRectifyTileW * kRectifyTileH) void k_rectify(
@@ -163,32 +141,12 @@ int svbrdf_rectify_photos(const void *src, int src_format, int P, int Hs, int Ws
                           void *stream)
 {
     const char *who = "svbrdf_rectify_photos";
-    char text[200];
-    const auto bad = [&](int code, const char *what) {
-        std::snprintf(text, sizeof(text), "%s: %s", who, what);
-        return fail(code, text);
-    };
-    if (src_format != SVBRDF_RECTIFY_F32_PLANAR && src_format != SVBRDF_RECTIFY_U8_INTERLEAVED)
-        return bad(SVBRDF_ERR_DIMS, "src_format must be SVBRDF_RECTIFY_F32_PLANAR (0) or SVBRDF_RECTIFY_U8_INTERLEAVED (1)");
+    const int rc = rectify_check(who, "out", src, src_format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi, out,
+                                 weights_out);
+    if (rc) return rc;
     const bool u8 = src_format == SVBRDF_RECTIFY_U8_INTERLEAVED;
-    if (!src || !matrices || !out) return bad(SVBRDF_ERR_NULL, "src, matrices and out are required");
-    if (u8 && !lut) return bad(SVBRDF_ERR_NULL, "uint8 sources need the 256-entry lut");
-    if (k != 1 && k != 2 && k != 4) return bad(SVBRDF_ERR_DIMS, "k must be 1, 2 or 4 (k x k sub-samples per pixel)");
-    if (P < 1 || Hs < 1 || Ws < 1 || Hd < 1 || Wd < 1) return bad(SVBRDF_ERR_DIMS, "P, Hs, Ws, Hd, Wd must be at least 1");
-    if (P > 65535) return bad(SVBRDF_ERR_DIMS, "P exceeds 65535 (grid.z)");
-    if (Hs > kRectifyMaxDim || Ws > kRectifyMaxDim || Hd > kRectifyMaxDim || Wd > kRectifyMaxDim)
-        return bad(SVBRDF_ERR_DIMS, "Hs, Ws, Hd, Wd must not exceed 32768");
-    if (clip_lo != clip_lo || clip_hi != clip_hi) return bad(SVBRDF_ERR_DIMS, "clip_lo and clip_hi must not be NaN");
-    if (!aligned(matrices, 4) || !aligned(out, 4) || !aligned(weights_out, 4) || !aligned(lut, 4) || (!u8 && !aligned(src, 4)))
-        return bad(SVBRDF_ERR_ALIGN, "float pointers must be 4-byte aligned");
-    RectifyClip clip;
-    clip.lo_f = clip_lo;
-    clip.hi_f = clip_hi;
-    // code <= clip_lo <=> code <= floor(clip_lo), code >= clip_hi <=> code >= ceil(clip_hi), for integer codes: exact
-    clip.lo_i = (int)std::floor(std::fmin(std::fmax((double)clip_lo, -1.0), 256.0));
-    clip.hi_i = (int)std::ceil(std::fmin(std::fmax((double)clip_hi, -1.0), 256.0));
-    const dim3 grid((unsigned)((Wd + kRectifyTileW - 1) / kRectifyTileW), (unsigned)((Hd + kRectifyTileH - 1) / kRectifyTileH),
-                    (unsigned)P);
+    const RectifyClip clip = rectify_clip(clip_lo, clip_hi);
+    const dim3 grid = rectify_grid(P, Hd, Wd);
     const hipStream_t st = static_cast<hipStream_t>(stream);
     if (u8) launch_rectify<true>(k, grid, st, src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
     else launch_rectify<false>(k, grid, st, src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);

@@ -2,7 +2,8 @@
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
                                [--fit-exposure] [--fit-pose [--pose-lr 0.002]] [--fused-step [--steps-per-launch K]]
-                               [--captured [--sensor 640x480] [--clip 250]] [--smooth LAMBDA]
+                               [--captured [--sensor 640x480] [--clip 250] [--fit-registration [--corner-noise PX]]]
+                               [--smooth LAMBDA]
 
 Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
 each from ``synthesis.render_inputs`` (the scene table is what that call draws from torch's global generator: the same seed
@@ -42,6 +43,17 @@ refused.  The material of this mode is band limited (the generator's maps at an 
 of per-pixel white noise survive no resampling.  The second fit runs on the rectified photographs WITH their weights through the same path as the first
 (``--fused-step`` included); with ``--fit-pose`` its camera positions start from ``capture.camera_from_corners`` instead of
 from the perturbed truth.  The share of zero weights and both final map errors are printed at the end.
+
+``--fit-registration`` (only with ``--captured``): two more fits, on photographs whose four patch corners are GIVEN off by up
+to ``--corner-noise`` source pixels per coordinate (somebody clicked them).  The first leaves them as given: every
+photograph sits shifted against the others on the grid, and the fit averages that into its maps.  The second refines them:
+every ``--registration-every`` map steps it renders the current maps under the scene table (K1, detached), takes
+``--registration-steps`` Adam steps on the eight corner coordinates of every photograph with
+``sum w |log(R + eps) - log(rect + eps)| / sum w`` in stock torch ops through the differentiable ``capture.rectify``
+(``capture.corner_matrices``; forward and backward one launch each; dividing by ``sum w`` keeps a rectangle that shrinks out
+of the image from looking like progress), and rectifies again.  The mean corner error is printed at every stage and both
+final map errors at the end.  Whether alternating with maps that are still wrong converges is not known in general: the
+tool records what it does.  Not with ``--steps-per-launch``.
 
 ``--smooth LAMBDA``: a smoothness prior across pixels on diffuse, roughness and specular (``fitting.smoothness`` with LAMBDA on
 those nine planes, 0 on the normals): the objective is the photo loss + the prior, the loss printed stays the photo term.
@@ -85,6 +97,12 @@ def main():
     ap.add_argument("--captured", action="store_true", help="fit a second time, on 8-bit perspective photographs rectified onto the grid")
     ap.add_argument("--sensor", default="640x480", help="with --captured: the camera's sensor, WIDTHxHEIGHT pixels")
     ap.add_argument("--clip", type=int, default=250, help="with --captured: codes of this value or more are clipped highlights")
+    ap.add_argument("--fit-registration", action="store_true",
+                    help="with --captured: the patch corners are given a few pixels off and refined against renderings of the maps")
+    ap.add_argument("--corner-noise", type=float, default=2.0, metavar="PX", help="with --fit-registration: source pixels per coordinate")
+    ap.add_argument("--registration-every", type=int, default=20, help="map steps between two registration stages")
+    ap.add_argument("--registration-steps", type=int, default=5, help="Adam steps on the corners per stage")
+    ap.add_argument("--registration-lr", type=float, default=0.1, help="Adam learning rate of the corners, source pixels")
     ap.add_argument("--smooth", type=float, default=None, metavar="LAMBDA",
                     help="smoothness prior across pixels on diffuse, roughness and specular (normals stay at 0); with "
                          "--steps-per-launch K it is K launches, not one")
@@ -98,6 +116,8 @@ def main():
     if args.steps_per_launch is not None and (args.fit_exposure or args.fit_pose):
         ap.error("--steps-per-launch updates the maps only: positions and gains would have to be updated between the steps of "
                  "a launch, from a gradient summed over all pixels (a grid barrier) -- use --fused-step without it")
+    if args.fit_registration and (not args.captured or args.steps_per_launch is not None):
+        ap.error("--fit-registration refines the corners of --captured photographs between single map steps")
     assert torch.cuda.is_available(), "needs a ROCm device"
     dev = torch.device("cuda:0")
     B, H, S = args.batch, args.size, args.photos
@@ -119,7 +139,7 @@ def main():
     if not args.captured:
         return fit(args, dev, truth, photos, table, hidden)
     on_grid = fit(args, dev, truth, photos, table, hidden)
-    rectified, weights, cameras = ingest(args, dev, photos, table)
+    rectified, weights, cameras, images, corners = ingest(args, dev, photos, table)
     seen = weights.unsqueeze(2).expand_as(photos) > 0
     print("--- the same fit on the captured photographs: %s sensor, gamma 2.2, 8 bits, rectified with 2 x 2 sub-samples; "
           "%.2f %% of the weights are zero, %.2f %% of the pixels are seen by no photograph; mean |rectified - on the grid| %.5f "
@@ -129,6 +149,51 @@ def main():
     captured = fit(args, dev, truth, rectified, table, hidden, weights, cameras)
     print("final mean |d,r,s - truth|: on the grid %.5f, captured %.5f (zero weights: %.2f %%)" % (
         on_grid, captured, 100.0 * (weights == 0).float().mean().item()))
+    if not args.fit_registration:
+        return
+    noise = args.corner_noise * (2.0 * synth.uniform01(args.seed + 4000, corners.shape) - 1.0)
+    results = []
+    for refine in (False, True):
+        reg = Registration(args, images, corners, corners + noise, H)
+        print("--- the captured fit with every corner coordinate given up to %g source pixels off (mean corner error %.3f px), %s"
+              % (args.corner_noise, reg.error(), "refined every %d map steps (%d Adam steps, lr %g)" % (
+                  args.registration_every, args.registration_steps, args.registration_lr) if refine else "left as given"))
+        shifted, w = reg.rectify()
+        results.append((fit(args, dev, truth, shifted, table, hidden, w, cameras, reg if refine else None), reg.error()))
+    print("final mean |d,r,s - truth|: true corners %.5f; corners %g px off, as given %.5f (corner error %.3f px), refined %.5f "
+          "(corner error %.3f px)" % (captured, args.corner_noise, results[0][0], results[0][1], results[1][0], results[1][1]))
+
+
+class Registration:
+    """--fit-registration: the corners of every captured photograph as an Adam parameter, float64 [B,S,4,2] on the host"""
+
+    EPS = 0.01
+
+    def __init__(self, args, images, true_corners, start_corners, H):
+        self.args, self.images, self.H = args, images, H
+        self.true = torch.from_numpy(true_corners)
+        self.corners = torch.from_numpy(start_corners).clone().requires_grad_(True)
+        self.opt = torch.optim.Adam([self.corners], lr=args.registration_lr)
+        self.lut = capture.gamma_lut()
+
+    def error(self):
+        return (self.corners.detach() - self.true).norm(dim=-1).mean().item()
+
+    def rectify(self, grad=False):
+        M = capture.corner_matrices(self.corners, self.H)
+        return capture.rectify(self.images, M if grad else M.detach(), self.H, lut=self.lut, clip=(0, self.args.clip), samples=2)
+
+    def refine(self, maps, scenes):
+        """one stage: a few Adam steps on the corners against the rendering of `maps` under `scenes` -> (photos, weights)"""
+        with torch.no_grad():
+            log_r = (_native.render_fwd(maps.detach().contiguous(), scenes.detach().contiguous()).clamp_(0.0, 1.0) + self.EPS).log()
+        for _ in range(self.args.registration_steps):
+            self.opt.zero_grad(set_to_none=True)
+            rect, w = self.rectify(grad=True)
+            loss = (w.unsqueeze(2) * (log_r - (rect + self.EPS).log()).abs()).sum() / (3.0 * w.sum())
+            loss.backward()
+            self.opt.step()
+        return self.rectify()
 
 
 def band_limited_maps(seed, B, H, cell=8):
@@ -143,7 +208,8 @@ def band_limited_maps(seed, B, H, cell=8):
 
 def ingest(args, dev, photos, table):
     """--captured: the photographs as a camera at each photo's position delivers them -- perspective, gamma 2.2, 8 bits --
-    and back onto the grid -> (photos [B,S,3,H,W], weights [B,S,H,W], the camera positions recovered from the corners)"""
+    and back onto the grid -> (photos [B,S,3,H,W], weights [B,S,H,W], the camera positions recovered from the corners, the
+    8-bit images [B,S,h,w,3], the corners [B,S,4,2] in their pixels)"""
     sensor = tuple(int(v) for v in args.sensor.lower().split("x"))
     B, S, H = photos.shape[0], photos.shape[1], photos.shape[-1]
     cams = table[..., :3].cpu().numpy().astype(np.float64)
@@ -154,7 +220,7 @@ def ingest(args, dev, photos, table):
     matrices = np.stack([capture.patch_homography(c, (H, H)) for c in corners]).reshape(B, S, 3, 3)
     rectified, weights = capture.rectify(images, matrices, H, lut=capture.gamma_lut(), clip=(0, args.clip), samples=2)
     recovered = np.stack([capture.camera_from_corners(c, sensor) for c in corners]).reshape(B, S, 3)
-    return rectified, weights, torch.from_numpy(recovered).float().to(dev)
+    return rectified, weights, torch.from_numpy(recovered).float().to(dev), images, np.stack(corners).reshape(B, S, 4, 2)
 
 
 def map_error(x, truth, unseen):
@@ -167,8 +233,9 @@ def map_error(x, truth, unseen):
     return err, text
 
 
-def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None):
-    """one fit of perturbed maps to `photos` (with `weights`, if given) -> the final mean |d,r,s - truth|"""
+def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None, registration=None):
+    """one fit of perturbed maps to `photos` (with `weights`, if given) -> the final mean |d,r,s - truth|.  `registration`: a
+    Registration whose stage replaces `photos` and `weights` every --registration-every steps."""
     B, H, S = args.batch, args.size, args.photos
     unseen = None if weights is None else weights.amax(dim=1, keepdim=True) == 0      # [B,1,H,W]: no photograph sees it
     lam = None if args.smooth is None else [0.0, args.smooth, args.smooth, args.smooth]
@@ -209,6 +276,14 @@ def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None):
             if t_last is not None:
                 step_ms.append(1e3 * (now - t_last) / args.print_every)
             t_last = now
+        if registration is not None and step and step % args.registration_every == 0:
+            with torch.no_grad():
+                scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
+                if log_e is not None:
+                    scenes = torch.cat((scenes[..., :6], scenes[..., 6:] * log_e.exp()), dim=-1)
+            photos, weights = registration.refine(x, scenes)
+            unseen = weights.amax(dim=1, keepdim=True) == 0
+            print("step %4d  registration stage: mean corner error %.3f px" % (step, registration.error()))
         if fit is not None and opt is None:
             loss = fit.step(photos, table, weights)
         elif fit is not None:
