@@ -192,7 +192,15 @@ SVBRDF_API int svbrdf_head_loss_fwd_bwd_host_scenes(const float *encoded9, const
  * pointer takes the same one-pixel-per-lane path: same results), eps in [1e-9, 1e9], and the scratch of
  * svbrdf_rendering_loss_workspace_bytes() with its zero-once / left-zeroed contract.  No gradient w.r.t. photos or scenes.
  * `_host_scenes`: the B*S rows in HOST memory travel by value in the launch's argument block
- * (B*S <= SVBRDF_HOST_SCENES_MAX_ROWS, SVBRDF_ERR_DIMS beyond); bitwise the results of the device-table entry. */
+ * (B*S <= SVBRDF_HOST_SCENES_MAX_ROWS, SVBRDF_ERR_DIMS beyond); bitwise the results of the device-table entry.
+ * Limits of S, for every photo entry below as well: forward-only (grad NULL) S <= 1706 -- the item's table is staged in LDS --,
+ * SVBRDF_ERR_DIMS beyond; with the gradient any S.
+ * ACCURACY OF THE LOSS AT LARGE S (every photo entry; measured on an MI355X at 17 x 17, tests/test_gpu_many_photos.py,
+ * profiles/r24_many_photos.txt): a thread adds the 3 S terms of its pixel one after the other in float32, so loss_out can be
+ * off by up to (3 S + 16) 2^-24 of the mean |term| -- 7.7e-5 relative at S = 425, 3.1e-4 at S = 1706.  Measured: within 1e-6
+ * of a float64 evaluation at every S <= 383 and for 12-map inputs at every S (1e-7 typical); 1.0e-6 to 2.0e-6 for the head
+ * entries in five of the cases tried at S = 425, 1278, 1706 and 1707 (the float32 oracle itself: 2e-8).  The gradients do not
+ * go through that sum and keep their bounds. */
 SVBRDF_API int svbrdf_photo_loss_fwd_bwd(const float *input, const float *photos, const float *scenes,
                                          const float *xrow, float eps, float *loss_out, float *grad_input,
                                          void *workspace, size_t workspace_bytes, int B, int S, int H, int W,
@@ -290,7 +298,7 @@ SVBRDF_API int svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes(const float *
  * bytes = the 65 words of svbrdf_rendering_loss_workspace_bytes plus B S 3 accumulator words, under the same contract:
  * zeroed once by the caller, left zeroed by every completed call (a NaN report included), so one buffer zeroed at that
  * size serves every fused loss.  Error codes before any launch as the weighted entries'; S <= 1278 (the per-workgroup
- * sums live in LDS).  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect the three by symbol presence. */
+ * sums live in LDS; the loss at such S: "ACCURACY OF THE LOSS AT LARGE S" at svbrdf_photo_loss_fwd_bwd).  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect the three by symbol presence. */
 SVBRDF_API size_t svbrdf_photo_exposure_workspace_bytes(int B, int S, int H, int W);
 SVBRDF_API int svbrdf_photo_loss_exposure_fwd_bwd(const float *input, const float *photos, const float *weights,
                                                   int weight_planes, const float *exposure, const float *scenes,
@@ -323,7 +331,8 @@ SVBRDF_API int svbrdf_head_photo_loss_exposure_fwd_bwd(const float *encoded9, co
  * The scene table is in device memory (no by-value form).  `workspace`: svbrdf_photo_scene_grad_workspace_bytes(B, S, H, W)
  * bytes = the 65 words of svbrdf_rendering_loss_workspace_bytes plus B S 9 accumulator words, under the same contract:
  * zeroed once by the caller, left zeroed by every completed call (a NaN report included).  Error codes before any launch
- * as the exposure entries'; S <= 425 (the per-workgroup sums live in LDS).  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect
+ * as the exposure entries'; S <= 425 (the per-workgroup sums live in LDS; the loss at such S: "ACCURACY OF THE LOSS AT LARGE
+ * S" at svbrdf_photo_loss_fwd_bwd).  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect
  * the three by symbol presence. */
 SVBRDF_API size_t svbrdf_photo_scene_grad_workspace_bytes(int B, int S, int H, int W);
 SVBRDF_API int svbrdf_photo_loss_scene_grad_fwd_bwd(const float *input, const float *photos, const float *weights,

@@ -42,11 +42,14 @@ GROUPS = (slice(0, 6), slice(6, 9))    # positions | colours
 _RENDERINGS = {}
 
 
-def dual_renderings(maps, scenes, f64):
+def dual_renderings(maps, scenes, f64, batched=False):
     """-> (rad [B,S,3,H,W], d rad / d row [B,S,9,3,H,W] float64) of oracle.eager_torch.render_scene with each scene row a dual
-    number; they depend on the maps and the table only, so the weight layouts of a case share them (kept per session)"""
+    number; they depend on the maps and the table only, so the weight layouts of a case share them (kept per session).
+    `batched`: per item one torch.vmap over the rows and the nine unit tangents of torch.func.jvp of the same function
+    instead of B S 9 eager renders -- for tables of hundreds of rows (tests/many_photos_checks.py); the same bits
+    (tests/test_many_photos_cpu.py holds the two against each other), kept apart all the same."""
     maps, scenes = np.ascontiguousarray(maps, np.float32), np.ascontiguousarray(scenes, np.float32)
-    key = (hashlib.sha1(maps.tobytes()).hexdigest(), hashlib.sha1(scenes.tobytes()).hexdigest(), bool(f64))
+    key = (hashlib.sha1(maps.tobytes()).hexdigest(), hashlib.sha1(scenes.tobytes()).hexdigest(), bool(f64), bool(batched))
     if key in _RENDERINGS:
         return _RENDERINGS[key]
     dtype = torch.float64 if f64 else torch.float32
@@ -58,6 +61,12 @@ def dual_renderings(maps, scenes, f64):
     rad = np.empty((B, S, 3, H, W), np.float64 if f64 else np.float32)
     drad = np.empty((B, S, 9, 3, H, W), np.float64)
     for b in range(B):
+        if batched:
+            render = lambda row: eager_torch.render_scene(maps_t[b], row, **args)[0]
+            one = lambda row, tangent: torch.func.jvp(render, (row,), (tangent,))
+            primal, tangent = torch.vmap(torch.vmap(one, in_dims=(None, 0)), in_dims=(0, None))(sc[b], torch.eye(9, dtype=dtype))
+            rad[b], drad[b] = primal[:, 8].numpy(), tangent.numpy()       # (the loop keeps the primal of its last tangent)
+            continue
         for s in range(S):
             for k in range(9):
                 with fwAD.dual_level():
@@ -69,7 +78,7 @@ def dual_renderings(maps, scenes, f64):
     return rad, drad
 
 
-def pose_terms(maps, photos, scenes, weights, f64, eps=EPS):
+def pose_terms(maps, photos, scenes, weights, f64, eps=EPS, batched=False):
     """-> (t [B,S,9,3,H,W] float64, delta [B,S,3,H,W]): the terms of d loss / d scenes on the 12-channel `maps`, evaluated in
     fp32 or fp64 on the same float32-valued inputs (pixel row, pi and the clamp with their float32 values, as the C
     oracle's float64 instantiation has them)"""
@@ -79,7 +88,7 @@ def pose_terms(maps, photos, scenes, weights, f64, eps=EPS):
     else:
         ph = photo_checks.excused_photos(photos, weights)
         w = photo_checks.broadcast_weights(weights, S).astype(np.float64)[:, :, None]
-    rad, drad = dual_renderings(maps, scenes, f64)
+    rad, drad = dual_renderings(maps, scenes, f64, batched)
     e = np.float64(np.float32(eps)) if f64 else np.float32(eps)
     a, bb = rad + e, (ph.astype(np.float64) if f64 else ph) + e
     with np.errstate(invalid="ignore", divide="ignore"):
@@ -92,11 +101,11 @@ class PoseReference:
     """the oracle's values of one case, computed once: `ref` (photo_checks.Reference: loss, map gradient, ties), G32 / G64
     [B,S,9], the bound's A and T, and the conditions on the inputs"""
 
-    def __init__(self, x, photos, scenes, eps=EPS, head=False, weights=None):
+    def __init__(self, x, photos, scenes, eps=EPS, head=False, weights=None, batched=False):
         self.scenes = np.ascontiguousarray(scenes, np.float32)
         self.ref = photo_checks.Reference(x, photos, self.scenes, eps, head=head, weights=weights)
-        t32, d32 = pose_terms(self.ref.maps, photos, self.scenes, weights, False, eps)
-        t64, d64 = pose_terms(self.ref.maps, photos, self.scenes, weights, True, eps)
+        t32, d32 = pose_terms(self.ref.maps, photos, self.scenes, weights, False, eps, batched)
+        t64, d64 = pose_terms(self.ref.maps, photos, self.scenes, weights, True, eps, batched)
         self.G32, self.G64 = t32.sum(axis=(3, 4, 5)), t64.sum(axis=(3, 4, 5))
         self.A = np.abs(t64).sum(axis=(3, 4, 5))
         ph = np.asarray(photos, np.float32) if weights is None else photo_checks.excused_photos(photos, weights)
