@@ -4,13 +4,12 @@
 // or create_graph=True to its renderer; these kernels exist because render() there is dtype-agnostic and twice
 // differentiable as a property of being built from torch ops (renderers.py:67-104).  Frozen since round 4: nothing is added
 // here, and the code lives in a file and a translation unit of its own so that edits cannot move the schedule or the
-// compile time of the kernels that matter (svbrdf_kernels.hip: K1-K4; csrc/Makefile).
+// compile time of the kernels that matter (svbrdf_main.hip and the K3 units: K1-K4; csrc/Makefile).
 //
-// The shared per-pixel device code (geometry(), pixel_coords(), load_scene(), make_vconst(): float32, exact-rounded) and
-// the host-side argument checks come from svbrdf_kernels.hip, included with SVBRDF_TU = 4: that selects none of its
-// kernels and none of its C ABI entry points, only the inline device functions and host helpers.
-#define SVBRDF_TU 4
-#include "svbrdf_kernels.hip"
+// The shared per-pixel device code (geometry(), pixel_coords(), load_scene(), make_vconst(): float32, exact-rounded) comes
+// from svbrdf_device.h and the host-side argument checks from svbrdf_host.h.
+#include "svbrdf_device.h"
+#include "svbrdf_host.h"
 
 // ------------------------------------------------------------------------------------------
 // float64 maps.  The reference's render() is dtype-agnostic (renderers.py:67-104), but what it does with double maps is

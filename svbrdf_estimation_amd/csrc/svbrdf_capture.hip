@@ -23,7 +23,7 @@
 // Arithmetic.  Every operation above is ONE individually rounded float32 operation: the unit is built with the Makefile's
 // HIPFLAGS (-ffp-contract=off: no FMA is formed; -fno-fast-math), and no fmaf() is written here.  The two quotients are the
 // language's plain `/`: hipcc's default for float division is the correctly rounded IEEE sequence (v_div_scale /
-// v_div_fmas / v_div_fixup, denormals kept), which the flags above leave in place -- div_rn of svbrdf_kernels.hip is NOT
+// v_div_fmas / v_div_fixup, denormals kept), which the flags above leave in place -- div_rn of svbrdf_device.h is NOT
 // used: it is exact only for operands of moderate magnitude, and M is the caller's.  tests/test_capture_cpu.py holds the
 // compiled kernels to that (two v_div_fixup_f32 per sub-sample, no v_fma / v_mad / v_rcp-only quotient).
 //
@@ -36,13 +36,11 @@
 // 256-byte row segment.  The photo index is blockIdx.z; its nine matrix entries are wave-uniform loads from the [P,9]
 // table (scalar loads; nothing is stored through the scalar unit).  The uint8 kernels stage the 256-entry table in LDS once
 // per workgroup (1 KiB).  Neighbouring destination pixels hit neighbouring source texels, so the gather leans on L2: the
-// source is not tiled through LDS.  No atomics, no scratch, no second pass.  It includes svbrdf_kernels.hip with
-// SVBRDF_TU = 4 for the host-side helpers only (fail, aligned, launch_status): none of its kernels, none of its entries.
+// source is not tiled through LDS.  No atomics, no scratch, no second pass.  It includes svbrdf_host.h for the
+// host-side helpers (fail, aligned, launch_status).
 // The tap rule, the launch shape and the argument checks are in svbrdf_capture_device.h, shared with svbrdf_capture_grad.hip
 // (the gradient towards the matrices).
-#define SVBRDF_TU 4
-#include "svbrdf_kernels.hip"
-
+#include "svbrdf_host.h"
 #include "svbrdf_capture_device.h"
 
 namespace {

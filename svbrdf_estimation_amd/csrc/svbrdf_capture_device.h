@@ -3,8 +3,7 @@
 // rule, the entries' argument checks, and -- as functions that k_homography_grad calls -- a sub-sample's geometry with the
 // clamped-in-float addressing and a tap's index.  k_rectify keeps its own statements of those two: its six kernels' machine
 // code moves when they go behind a function (profiles/r23_capture_grad_codehash.txt), and it is the text that describes
-// the definition.  No kernel and no entry point.  The including unit has svbrdf_kernels.hip in front (SVBRDF_TU = 4: fail,
-// aligned).
+// the definition.  No kernel and no entry point.  The including unit has svbrdf_host.h in front (fail, aligned).
 #ifndef SVBRDF_CAPTURE_DEVICE_H
 #define SVBRDF_CAPTURE_DEVICE_H
 

@@ -31,8 +31,7 @@
 //      zeroed once by the caller and left zeroed by every completed call.
 // SVBRDF_RECTIFY_GRAD_DEPTH = 24 (include/svbrdf_hip.h) bounds the float32 additions any single term passes through: K^2 - 1 <= 15, 6 and 2 make 23.
 // No float32 sum crosses a workgroup.  Which workgroup finishes depends on timing; what it computes does not.
-#define SVBRDF_TU 4
-#include "svbrdf_kernels.hip"
+#include "svbrdf_host.h"
 #include "svbrdf_capture_device.h"
 
 namespace {

@@ -1,0 +1,10 @@
+// The forward+adjoint MixedLoss / head-fused kernels k_rendering_loss{,_inl}<GRAD, L1 or HEAD set> and their launcher, in
+// a unit of their own for its scheduler set (csrc/Makefile: SCHED_ADJOINT_EXTRA).
+#include "svbrdf_k3_kernels.h"
+
+void svbrdf_internal_launch_k3_adjoint_extra(SVBRDF_K3_ADJOINT_ARGS)
+{
+    launch_k3<true, 1>(with_l1 != 0, head != 0, rows, dim3(gx, gy, 1), lds_bytes,
+                       static_cast<hipStream_t>(stream), input, target, scenes, xrow, eps, inv_count, loss_scale, fixed_scale,
+                       L1Params{l1_sum_scale, l1_grad_scale, l1_eps}, grad_input, ws, loss_out, B, S, H, W);
+}

@@ -2,7 +2,7 @@
 //
 //   L = mean_{b,s,c,i,j} | log(render(scene[b,s], input[b]) + eps) - log(photo[b,s] + eps) |
 //
-// K3 (svbrdf_kernels.hip) compares the renderings of two sets of maps; this kernel compares the renderings of ONE set
+// K3 (svbrdf_device.h) compares the renderings of two sets of maps; this kernel compares the renderings of ONE set
 // of maps with given photographs -- the inverse-rendering use of the engine, where ground-truth maps do not exist.  Per
 // pixel it loads the 12 input planes once, loops the S scenes in registers, shades the input with K3's own primitives
 // (dots / lobe / shade_loss / shade_bwd: tied-roughness fast path and three-lobe path), takes the target side of every
@@ -134,7 +134,7 @@ void launch_photo(const float *rows, dim3 grid, size_t lds_bytes, hipStream_t st
     }
 }
 
-// Argument checks, grid and fixed-point scale: K3's own (plan_loss in svbrdf_kernels.hip; no L1 term here).  The launch
+// Argument checks, grid and fixed-point scale: K3's own (plan_loss in svbrdf_host.h; no L1 term here).  The launch
 // is counted by the main unit's counter through launch_status() (svbrdf_internal_launch_status).
 // `head`: input and grad_input are the 9 encoded planes (svbrdf_head_photo_loss_fwd_bwd*), same checks.
 // `weighted`: the same plan (a weight in [0, 1] keeps a term within plan_loss's bound of 32, so the fixed-point scale

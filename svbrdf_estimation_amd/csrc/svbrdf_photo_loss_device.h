@@ -2,12 +2,11 @@
 // loops, the set-up of a pixel, the end of a launch with per-scene sums and the launchers' checks.  svbrdf_photo_loss.hip
 // (which describes the flow), svbrdf_photo_exposure.hip and, through the pose and fit headers, every fit unit include it.
 //
-// The shared inline device code and the host-side argument checks come from svbrdf_kernels.hip, included with
-// SVBRDF_TU = 4 as svbrdf_aux_f64.hip does: none of its kernels, none of its entry points.
+// K3's own device code comes from svbrdf_device.h and the host-side argument checks from svbrdf_host.h, as for every unit.
 #ifndef SVBRDF_PHOTO_LOSS_DEVICE_H
 #define SVBRDF_PHOTO_LOSS_DEVICE_H
-#define SVBRDF_TU 4
-#include "svbrdf_kernels.hip"
+#include "svbrdf_device.h"
+#include "svbrdf_host.h"
 
 namespace {
 

@@ -12,7 +12,7 @@ Keeps the reference's plugin interface (development/multiImage_pytorch/renderers
     kernel K1 and returned as a CPU tensor (forward only; see ``_HostStaging``).  Without a usable ROCm device the
     call raises ``NativeLibraryError`` -- there is no CPU implementation.
 The arithmetic (renderers.py:8-104) runs in the hand-written HIP kernels K1 (forward) and
-K2 (analytic backward, forward recomputed in registers) of csrc/svbrdf_kernels.hip.
+K2 (analytic backward, forward recomputed in registers) of csrc/svbrdf_device.h (kernels: csrc/svbrdf_main.hip).
 
 Extension (not in the reference): ``render_many(scene_table, svbrdf)`` renders S scenes per
 map in one launch, reading the maps once.

@@ -153,7 +153,7 @@ LOSS_BEYOND_RTOL = {("s425", None, True): 1.21e-6, ("s1278", None, True): 1.42e-
 
 
 def fixed_point_exponent(B, S, H, W):
-    """k of plan_loss (csrc/svbrdf_kernels.hip): the partial sums are kept in units of 2^-k, k = 24 unless a slot's worst case
+    """k of plan_loss (csrc/svbrdf_host.h): the partial sums are kept in units of 2^-k, k = 24 unless a slot's worst case
     -- |dlog| <= 32 per term: count 32 / 64 terms' worth from its workgroups and 32 * 256 * 3 S from one more -- could then
     reach 2^47"""
     count = float(B) * S * 3.0 * float(H) * W
@@ -165,7 +165,7 @@ def fixed_point_exponent(B, S, H, W):
 
 
 def rule_in_source(text):
-    """the rule as csrc/svbrdf_kernels.hip states it -> (start exponent, the worst-case expression, the loop's condition and
+    """the rule as csrc/svbrdf_host.h states it -> (start exponent, the worst-case expression, the loop's condition and
     step) with the blanks squeezed out: what the restatement restates"""
     m = re.search(r"int k = (\d+);\s*const double l1_share = [^;]+;\s*const double worst_per_slot = ([^;]+);\s*"
                   r"while \(([^\n]+)\) ([^;]+);\s*out->fixed_scale = \(float\)std::ldexp\(1\.0, k\);", text)

@@ -276,7 +276,7 @@ def test_source_holds_no_inline_assembly_and_no_fma():
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert not re.search(r"\basm\b|\b(__builtin_)?fmaf?\(|\bfma_\(|\brcp_\(|\bdiv_rn\(|atomic", code)
     assert code.count("fminf(fmaxf(") == 2 and code.index("fminf(fmaxf(") < code.index("(int)x0f")
-    assert '#define SVBRDF_TU 4\n#include "svbrdf_kernels.hip"' in src
+    assert "int fail(" in unit_build.assert_includes_shared_header("svbrdf_capture", "svbrdf_host.h")
 
 
 @needs_hipcc

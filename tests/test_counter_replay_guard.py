@@ -4,30 +4,20 @@ taken from -- the sha256 of the kernel's instruction bytes in the shipped librar
 CPU only: hipcc cross-compiles, the hash is read out of the .so's offload bundle (svbrdf_estimation_amd/_codehash.py)."""
 import json
 import os
-import subprocess
 
 import pytest
 
+import unit_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 LIB = os.path.join(ROOT, "svbrdf_estimation_amd", "lib", "libsvbrdf_hip.so")
 RECORD = os.path.join(ROOT, "profiles", "k3_hbm_traffic.json")
 
 
-def _make_var(name):
-    return subprocess.check_output(["make", "-s", "-C", CSRC, "print-" + name], text=True).strip().split()
-
-
 def _build_adjoint_unit(tmp, tag, extra):
-    """the RenderingLoss forward+adjoint translation unit alone, Makefile flags + `extra`, linked into a .so of its own (the
-    hasher only needs the unit's offload bundle)"""
-    obj, so = str(tmp / (tag + ".o")), str(tmp / ("lib" + tag + ".so"))
-    cmd = (_make_var("HIPCC") + _make_var("HIPFLAGS") + _make_var("SCHED_ADJOINT") + ["-DSVBRDF_TU=1"] + extra +
-           ["-c", "-o", obj, os.path.join(CSRC, "svbrdf_kernels.hip")])
-    cmd = [c.replace("../../include", os.path.join(ROOT, "include")) for c in cmd]
-    subprocess.check_call(cmd, cwd=CSRC, stderr=subprocess.DEVNULL)
-    subprocess.check_call(_make_var("HIPCC") + ["--offload-arch=gfx950", "-fPIC", "-shared", "-o", so, obj], stderr=subprocess.DEVNULL)
-    return so
+    """the RenderingLoss forward+adjoint unit alone, Makefile flags + `extra`, as a .so of its own (the hasher only needs
+    the unit's offload bundle)"""
+    return unit_build.build_unit_library(tmp / tag, "svbrdf_k3_adjoint", "SCHED_ADJOINT", extra)
 
 
 def test_record_is_keyed_to_the_shipped_kernel_and_replayed_for_it():

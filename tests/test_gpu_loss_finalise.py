@@ -1,4 +1,4 @@
-"""The end of a fused-loss launch (svbrdf_kernels.hip, loss_arrive): every workgroup adds its fixed-point partial sum to one of
+"""The end of a fused-loss launch (svbrdf_device.h, loss_arrive): every workgroup adds its fixed-point partial sum to one of
 64 slot words with a returning atomic that also counts arrivals; the completer of a slot re-zeroes it and adds the slot's sum
 to the tail word, which counts completed slots the same way; the completer of the last slot writes the loss and re-zeroes the
 tail word.  Nothing is read back, so every grid shape has to come out right from the two returns alone:

@@ -2,7 +2,7 @@
 
 The by-value-table kernels fetch the launch's scalars once at wave entry, request render 0's scene row in front of the
 plane loads, and every fused-loss kernel sums a wave's partial loss with lane swaps and DPP rotations instead of
-ds_bpermute (rendering_loss_body, wave_sum_k3 in svbrdf_kernels.hip).  The device-table kernels keep the ordinary
+ds_bpermute (rendering_loss_body, wave_sum_k3 in svbrdf_device.h).  The device-table kernels keep the ordinary
 prologue, so the two forms check each other: same inputs, same bits.  Against the oracle and the reference fixture the
 bounds are the suite's own (tests/tolerances.py).
 

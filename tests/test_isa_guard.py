@@ -15,16 +15,16 @@ kernel k_rendering_loss_inl<GRAD=1,L1=0,HEAD=0> (and, more loosely, the MixedLos
 """
 import os
 import re
-import subprocess
 import sys
 
 import pytest
+
+import unit_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 # a toolchain test: without hipcc there is nothing to compile (the GPU parity tests, by contrast, FAIL without a GPU)
 pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs /opt/rocm/bin/hipcc (cross-compiles gfx950)")
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 HEADLINE = "k_rendering_loss_inlILb1ELb0ELb0"
 
 # budgets: measured values of the shipped build + a small margin (tools/isa_stats.py prints the current ones).
@@ -40,31 +40,23 @@ UNTIED_EXTRA_SCRATCH_MAX = {"mixed": 16, "head": 0}       # MixedLoss three-lobe
 TIED_EXTRA_SCRATCH_MAX = {"mixed": 6, "head": 0}        # device-table MixedLoss kernel: 5 spill accesses per trip
 
 
-def _make_var(name):
-    out = subprocess.check_output(["make", "-s", "-C", CSRC, "print-" + name], text=True)
-    return out.strip().split()
-
-
-def _compile_tu(tmp, tu, sched_var):
-    out = str(tmp / ("tu%d.s" % tu))
-    cmd = (_make_var("HIPCC") + _make_var("HIPFLAGS") + _make_var(sched_var) +
-           ["-DSVBRDF_TU=%d" % tu, "-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "svbrdf_kernels.hip")])
-    cmd = [c.replace("../../include", os.path.join(ROOT, "include")) for c in cmd]
-    subprocess.check_call(cmd, cwd=CSRC, stderr=subprocess.DEVNULL)
-    with open(out) as f:
-        return f.read()
-
-
 @pytest.fixture(scope="module")
 def adjoint_asm(tmp_path_factory):
-    """assembly of the RenderingLoss forward+adjoint translation unit (SVBRDF_TU=1), the Makefile's own flags"""
-    return _compile_tu(tmp_path_factory.mktemp("isa1"), 1, "SCHED_ADJOINT")
+    """assembly of the RenderingLoss forward+adjoint unit (svbrdf_k3_adjoint.hip), the Makefile's own flags"""
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa1"), "svbrdf_k3_adjoint", "SCHED_ADJOINT")
 
 
 @pytest.fixture(scope="module")
 def adjoint_extra_asm(tmp_path_factory):
-    """assembly of the MixedLoss / head-fused forward+adjoint translation unit (SVBRDF_TU=3)"""
-    return _compile_tu(tmp_path_factory.mktemp("isa3"), 3, "SCHED_ADJOINT_EXTRA")
+    """assembly of the MixedLoss / head-fused forward+adjoint unit (svbrdf_k3_adjoint_extra.hip)"""
+    return unit_build.compile_unit_asm(tmp_path_factory.mktemp("isa3"), "svbrdf_k3_adjoint_extra", "SCHED_ADJOINT_EXTRA")
+
+
+@pytest.mark.parametrize("unit, sched_var", [("svbrdf_main", "SCHED_MAIN"), ("svbrdf_k3_adjoint", "SCHED_ADJOINT"),
+                                             ("svbrdf_k3_adjoint_extra", "SCHED_ADJOINT_EXTRA")])
+def test_makefile_builds_the_unit_into_the_library(unit, sched_var):
+    """what the fixtures above compile is what ships: the one pattern rule, HIPFLAGS, the unit's own scheduler set"""
+    unit_build.assert_makefile_builds(unit, sched_var)
 
 
 def test_headline_kernel_resources(adjoint_asm):
@@ -115,8 +107,10 @@ def test_plane_loads_are_issued_back_to_back(adjoint_asm, adjoint_extra_asm):
 def test_no_inline_asm_memory_instructions_in_the_kernel_source():
     """VERDICT round 4 (fragility i): no load or store may be issued by inline asm outside the compiler's s_waitcnt
     bookkeeping.  The source may use asm only as an optimisation barrier (empty template)."""
-    with open(os.path.join(CSRC, "svbrdf_kernels.hip")) as f:
-        src = f.read()
+    src = unit_build.read_csrc("svbrdf_device.h", "svbrdf_k3_kernels.h", "svbrdf_host.h", "svbrdf_main.hip",
+                               "svbrdf_k3_adjoint.hip", "svbrdf_k3_adjoint_extra.hip")
+    for name in ("rendering_loss_body", "k_rendering_loss_inl", "plan_loss", "k_mix_materials", "launch_k3<true, 0>", "launch_k3<true, 1>"):
+        assert name in src, name        # (the three units and three headers hold the K1-K4 source between them)
     for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', src):
         assert m.group(1) == "", "inline asm with instructions: %r" % m.group(1)
 
@@ -159,19 +153,10 @@ def test_mixed_and_head_fused_variants_budget(adjoint_extra_asm):
 
 
 def test_dot_products_are_not_contracted(tmp_path):
-    """numerics contract (svbrdf_kernels.hip header): dot3 = three separately rounded products summed (p0+p1)+p2.
+    """numerics contract (svbrdf_device.h header): dot3 = three separately rounded products summed (p0+p1)+p2.
     The probe kernel is dot3 and nothing else; with the product build flags it must compile to 3 v_mul + 2 v_add
     and no FMA (an -ffp-contract=fast toolchain default would fuse two of the products)."""
-    import isa_stats
-    src = tmp_path / "probe.hip"
-    src.write_text('#define SVBRDF_ISA_PROBE 1\n#include "%s"\n' % os.path.join(CSRC, "svbrdf_kernels.hip"))
-    out = str(tmp_path / "probe.s")
-    cmd = (_make_var("HIPCC") + _make_var("HIPFLAGS") + _make_var("SCHED_MAIN") +
-           ["-DSVBRDF_TU=0", "-S", "--cuda-device-only", "-o", out, str(src)])
-    cmd = [c.replace("../../include", os.path.join(ROOT, "include")) for c in cmd]
-    subprocess.check_call(cmd, cwd=CSRC, stderr=subprocess.DEVNULL)
-    _, _, whole, _, ins, _ = isa_stats.analyse(open(out).read(), "svbrdf_isa_probe_dot3")
-    mns = [mn for _, _, mn, _ in ins if mn and mn.startswith("v_") and not mn.startswith("v_mov")]
+    mns, fma = unit_build.dot3_probe_instructions(tmp_path, "svbrdf_main", "SCHED_MAIN")
     muls = [m for m in mns if m.startswith("v_mul_f32")]
     adds = [m for m in mns if m.startswith("v_add_f32")]
-    assert len(muls) == 3 and len(adds) == 2 and whole["fma"] == 0, mns
+    assert len(muls) == 3 and len(adds) == 2 and fma == 0, mns

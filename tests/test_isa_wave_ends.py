@@ -1,6 +1,6 @@
 """Compile-time guard of the straight-line code at the two ends of a fused-loss wave (CPU test: hipcc cross-compiles
 gfx950 without a GPU).  tests/test_isa_guard.py pins the scene loops; nothing there looks at what runs before the first
-loop and after the last, which is where three serialisations were taken out (rendering_loss_body, svbrdf_kernels.hip):
+loop and after the last, which is where three serialisations were taken out (rendering_loss_body, svbrdf_device.h):
 
   * the launch's scalars are fetched together at wave entry: one `s_waitcnt lgkmcnt(0)` between wave entry and the first
     plane load of the by-value headline kernel (SVBRDF_K3_ENTRY_FETCH);
@@ -12,31 +12,21 @@ Each figure is compared with the same unit compiled in the same test run with th
 code from before the change -- and none of them may move a scene loop: same loops, same counts per trip.
 """
 import os
-import subprocess
 import sys
 
 import pytest
 
+import unit_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 pytestmark = pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs /opt/rocm/bin/hipcc (cross-compiles gfx950)")
-CSRC = os.path.join(ROOT, "svbrdf_estimation_amd", "csrc")
 HEADLINE = "k_rendering_loss_inlILb1ELb0ELb0"
 SWITCHES_OFF = ["-DSVBRDF_K3_ENTRY_FETCH=0", "-DSVBRDF_K3_EARLY_SCENE=0", "-DSVBRDF_K3_DPP_SUM=0"]
 
 
-def _make_var(name):
-    return subprocess.check_output(["make", "-s", "-C", CSRC, "print-" + name], text=True).strip().split()
-
-
-def _compile_unit1(tmp, tag, extra):
-    out = str(tmp / (tag + ".s"))
-    cmd = (_make_var("HIPCC") + _make_var("HIPFLAGS") + _make_var("SCHED_ADJOINT") + ["-DSVBRDF_TU=1"] + extra +
-           ["-S", "--cuda-device-only", "-o", out, os.path.join(CSRC, "svbrdf_kernels.hip")])
-    cmd = [c.replace("../../include", os.path.join(ROOT, "include")) for c in cmd]
-    subprocess.check_call(cmd, cwd=CSRC, stderr=subprocess.DEVNULL)
-    with open(out) as f:
-        return f.read()
+def _compile_unit1(tmp, extra):
+    return unit_build.compile_unit_asm(tmp, "svbrdf_k3_adjoint", "SCHED_ADJOINT", extra)
 
 
 def _facts(text):
@@ -62,7 +52,7 @@ def _facts(text):
 @pytest.fixture(scope="module")
 def facts(tmp_path_factory):
     tmp = tmp_path_factory.mktemp("isa_ends")
-    new, old = _facts(_compile_unit1(tmp, "new", [])), _facts(_compile_unit1(tmp, "switches_off", SWITCHES_OFF))
+    new, old = _facts(_compile_unit1(tmp, [])), _facts(_compile_unit1(tmp, SWITCHES_OFF))
     for k in ("entry_waits", "late_scalar_loads", "bpermute", "before_first_loop", "after_last_loop", "vgprs", "scratch"):
         print("%-20s switches off %4d   this build %4d" % (k, old[k], new[k]))
     return new, old

@@ -56,8 +56,8 @@ def test_inputs_meet_the_conditions(kind, name, layout, head):
 def test_fixed_point_exponent_of_every_case():
     """plan_loss's rule, restated: k = 24 below S = 330 at 17 x 17 with B = 2, and 23 / 23 / 22 / 21 at S = 383 / 425 / 1278 /
     1706 (B = 1) -- and the source still states the rule that is restated here"""
-    assert mp.rule_in_source(unit_build.read_csrc("svbrdf_kernels.hip")) == mp.RULE
-    text = unit_build.read_csrc("svbrdf_kernels.hip")
+    assert mp.rule_in_source(unit_build.read_csrc("svbrdf_host.h")) == mp.RULE
+    text = unit_build.read_csrc("svbrdf_device.h")
     assert "constexpr int kLossSlots = %d;" % mp.LOSS_SLOTS in text and "constexpr int kLossThreads = %d;" % mp.LOSS_THREADS in text
     assert "constexpr int kLossCountShift = %d;" % mp.COUNT_SHIFT in text
     k = lambda B, S: mp.fixed_point_exponent(B, S, 17, 17)

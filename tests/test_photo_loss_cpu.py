@@ -44,7 +44,7 @@ def test_library_exports_the_photo_loss_and_abi_8(lib):
         assert "SVBRDF_API int %s(" % name in header
 
 
-# all nine fused-loss entry points share one set of argument checks (plan_loss in csrc/svbrdf_kernels.hip); the mixed and
+# all nine fused-loss entry points share one set of argument checks (plan_loss in csrc/svbrdf_host.h); the mixed and
 # head K3 entries take `l1_weight, eps_l1` after `eps`
 LOSS_ENTRIES = ENTRIES + ("svbrdf_head_photo_loss_fwd_bwd", "svbrdf_head_photo_loss_fwd_bwd_host_scenes",
                           "svbrdf_rendering_loss_fwd_bwd")
@@ -228,27 +228,33 @@ def _isa_stats():
 def test_makefile_builds_the_unit_into_the_library():
     unit_build.assert_makefile_builds("svbrdf_photo_loss", "SCHED_PHOTO")
     assert "-ffp-contract=off" in unit_build.make_var("HIPFLAGS")
-    # K3's source is not touched by the feature's translation unit: its header only includes it, with SVBRDF_TU = 4
-    header = unit_build.assert_includes_shared_header("svbrdf_photo_loss", "svbrdf_photo_loss_device.h")
-    assert '#define SVBRDF_TU 4\n#include "svbrdf_kernels.hip"' in header
+    # K3's source is not touched by the feature's translation unit: its header only includes K3's device code and the host checks
+    unit_build.assert_includes_shared_header("svbrdf_photo_loss", "svbrdf_photo_loss_device.h")
+    assert "rendering_loss_body" in unit_build.assert_includes_shared_header("svbrdf_photo_loss_device.h", "svbrdf_device.h")
+    assert "plan_loss" in unit_build.assert_includes_shared_header("svbrdf_photo_loss_device.h", "svbrdf_host.h")
     import re
     for m in re.finditer(r'asm\s+volatile\s*\(\s*"([^"]*)"', unit_build.read_csrc("svbrdf_photo_loss.hip", "svbrdf_photo_loss_device.h")):
         assert m.group(1) == "", "inline asm with instructions: %r" % m.group(1)
 
 
 def test_units_share_code_through_headers_only():
-    """the layout of csrc/, stated once: no .hip file includes another .hip file except svbrdf_kernels.hip (shared code
-    lives in headers; no file is compiled "minus its kernels"), and no guard macro of that kind is left anywhere"""
+    """the layout of csrc/, stated once: no .hip file includes another .hip file (shared code lives in headers; no file is
+    compiled "minus its kernels"), no guard macro of that kind is left anywhere, and a header holds no entry point and --
+    but for the K3 kernel templates, which three units instantiate -- no kernel"""
     import re
     names = sorted(os.listdir(CSRC))
     units = [n for n in names if n.endswith(".hip")]
-    assert len(units) >= 9, units
+    assert len(units) >= 12, units
     for name in units:
         included = re.findall(r'^\s*#\s*include\s*"([^"]+\.hip)"', unit_build.read_csrc(name), flags=re.M)
-        assert all(i == "svbrdf_kernels.hip" for i in included), (name, included)
+        assert not included, (name, included)
     for name in names:
         if os.path.isfile(os.path.join(CSRC, name)):
-            assert "SHARED_ONLY" not in unit_build.read_csrc(name), name
+            text = unit_build.read_csrc(name)
+            assert "SHARED_ONLY" not in text and "SVBRDF_TU" not in text, name
+            if name.endswith(".h"):
+                assert 'extern "C" {' not in text, name
+                assert "__global__" not in text or name == "svbrdf_k3_kernels.h", name
 
 
 @needs_hipcc
@@ -291,12 +297,7 @@ def test_kernel_resources_and_scene_loops(photo_asm):
 def test_geometry_path_holds_no_contracted_fma(tmp_path):
     """numerics contract: dot3 -- the coords -> NH path -- is three separately rounded products summed (p0+p1)+p2 in THIS
     unit's build too (its own flag set): the probe kernel must compile to 3 v_mul + 2 v_add and no FMA."""
-    isa_stats = _isa_stats()
-    src = tmp_path / "probe.hip"
-    src.write_text('#define SVBRDF_ISA_PROBE 1\n#include "%s"\n' % os.path.join(CSRC, "svbrdf_photo_loss.hip"))
-    text = unit_build.compile_unit_asm(tmp_path, str(src), "SCHED_PHOTO")
-    _, _, whole, _, ins, _ = isa_stats.analyse(text, "svbrdf_isa_probe_dot3")
-    mns = [mn for _, _, mn, _ in ins if mn and mn.startswith("v_") and not mn.startswith("v_mov")]
+    mns, fma = unit_build.dot3_probe_instructions(tmp_path, "svbrdf_photo_loss", "SCHED_PHOTO")
     muls = [m for m in mns if m.startswith("v_mul_f32")]
     adds = [m for m in mns if m.startswith("v_add_f32")]
-    assert len(muls) == 3 and len(adds) == 2 and whole["fma"] == 0, mns
+    assert len(muls) == 3 and len(adds) == 2 and fma == 0, mns

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Run-time check of what K3's load stagger assumes (svbrdf_kernels.hip, SVBRDF_K3_STAGGER): that the dispatcher places a
+"""Run-time check of what K3's load stagger assumes (svbrdf_device.h, SVBRDF_K3_STAGGER): that the dispatcher places a
 launch's workgroups BREADTH-FIRST -- workgroups 0..255 one per CU, 256..511 the CUs' second slots, and so on -- so that
 "linear workgroup index >> 8" is "which of a CU's four workgroup slots", and the first four layers (1024 workgroups = 256
 CUs x 4) are all resident from the start.  If placement were depth-first the stagger would be a pure delay.
