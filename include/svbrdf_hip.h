@@ -550,6 +550,79 @@ SVBRDF_API int svbrdf_rectify_photos_grad_matrices(const void *src, int src_form
                                                    float *grad_matrices, void *workspace, size_t workspace_bytes,
                                                    void *stream);
 
+/* svbrdf_rectify_photos BEHIND A LENS, ONE launch: a homography is exact only for a pinhole camera, and a phone's lens bends
+ * straight lines by several pixels towards the frame's edge.  The gather needs the FORWARD distortion model, ideal pixel ->
+ * distorted pixel, a closed-form polynomial: it stands between the forward's quotient and its tap cell, nothing iterates.
+ *   lens         DEVICE float32 [P,9] per photo: fx, fy, cx, cy, k1, k2, p1, p2, k3 -- OpenCV's camera matrix entries and its
+ *                distortion vector in OpenCV's order, so a calibration can be pasted in.  `matrices` then map a destination
+ *                pixel to IDEAL (undistorted) source pixel coordinates.
+ * Every other argument is svbrdf_rectify_photos'.  Per sub-sample, everything up to u = X / Z, v = Y / Z is the forward's as
+ * it stands.  Then, every line ONE individually rounded float32 operation, no fused multiply-add, IEEE `/`:
+ *   xn = (u - cx) / fx          yn = (v - cy) / fy
+ *   xx = xn xn   yy = yn yn   xy = xn yn   r2 = xx + yy
+ *   rad  = 1 + r2 (k1 + r2 (k2 + r2 k3))
+ *   mono = 1 + r2 (3 k1 + r2 (5 k2 + r2 (7 k3)))          d(r rad)/dr: the radial map has not folded back
+ *   t  = 2 xy
+ *   tx = (p1 t) + (p2 (r2 + 2 xx))      ty = (p1 (r2 + 2 yy)) + (p2 t)
+ *   xd = (xn rad) + tx                   yd = (yn rad) + ty
+ *   ud = (xd fx) + cx                    vd = (yd fy) + cy
+ *   valid  <=>  Z > 0  and  fx > 0  and  fy > 0  and  mono > 0  and  0 <= ud <= Ws-1  and  0 <= vd <= Hs-1   (false for NaN)
+ * (3 k1, 5 k2, 7 k3, 2 xx, 2 yy are rounded products of their own; a focal length of 0 or below makes every sub-sample
+ * invalid: with a negative one the polynomial alone would map back into the frame.)  From here on it is the forward's text
+ * with (ud, vd) in the place of (u, v): the select to 0 if not valid, the clamp in float before the conversion to int, cell,
+ * taps, tap rule, bilinear value, the sub-sample sum in (j, i) order times 1/k^2, values and weight 0 for a pixel with any
+ * invalid sub-sample.  Every load address lies inside the source WHATEVER `matrices` and `lens` hold (NaN, +-inf, 1e30, a
+ * focal length of 0 or below: such sub-samples are invalid, nothing else happens).
+ * Why mono: under strong barrel distortion the polynomial maps far-off ideal points back into the frame; without the guard
+ * a destination pixel outside the camera's view would get a confident, wrong value.
+ * With the null lens (1, 1, 0, 0, 0, 0, 0, 0, 0) every added statement is exact: values and weights are svbrdf_rectify_photos'
+ * bit for bit.  Results are a pure function of the arguments: bit for bit the numpy float32 restatement of
+ * tests/capture_lens_checks.py.  Six kernels <uint8, k>, the forward's launch shape, no atomics, no scratch, no workspace.
+ * Error codes before any launch: svbrdf_rectify_photos', then SVBRDF_ERR_NULL for a NULL lens, SVBRDF_ERR_ALIGN for one off
+ * 4 bytes.
+ * ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect it by symbol presence. */
+SVBRDF_API int svbrdf_rectify_photos_lens(const void *src, int src_format, int P, int Hs, int Ws, const float *matrices,
+                                          const float *lens, int Hd, int Wd, int k, const float *lut, float clip_lo,
+                                          float clip_hi, float *out, float *weights_out, void *stream);
+
+/* THE GRADIENT OF svbrdf_rectify_photos_lens' VALUES TOWARDS THE MATRICES AND THE LENS, ONE launch:
+ * grad_matrices[p, n] = d (sum over `out` of grad_values * out) / d m_n of photo p THROUGH the lens's Jacobian, and
+ * grad_lens[p, n] the same towards lens entry n (fx, fy, cx, cy, k1, k2, p1, p2, k3), both DEVICE float32 [P,9], written
+ * whole.  The forward's arguments unchanged; grad_values DEVICE float32 [P,3,Hd,Wd].
+ * Definition.  Per sub-sample everything up to the taps and the pixel's `ok` is the forward's.  The gradient is that of the
+ * forward's expression with the cell, `valid` (mono's sign included) and `ok` held constant.  Every line one individually
+ * rounded float32 operation (no fused multiply-add, IEEE division; 2 k2, 3 k3, 2 p1, 6 p1, 2 p2, 6 p2, 2 xx, 2 yy are rounded
+ * products of their own):
+ *   gud, gvd = svbrdf_rectify_photos_grad_matrices' gu, gv, formed at the cell and fractions of (ud, vd)
+ *   a = gud fx;   b = gvd fy;   q = k1 + (r2 ((2 k2) + ((3 k3) r2)))
+ *   jxx = ((rad + ((2 xx) q)) + ((2 p1) yn)) + ((6 p2) xn)                              d xd / d xn
+ *   jxy = ((t q) + ((2 p1) xn)) + ((2 p2) yn)                                           d xd / d yn = d yd / d xn
+ *   jyy = ((rad + ((2 yy) q)) + ((6 p1) yn)) + ((2 p2) xn)                              d yd / d yn
+ *   gxn = (a jxx) + (b jxy);   gyn = (a jxy) + (b jyy);   gu = gxn / fx;   gv = gyn / fy
+ *   rz = 1 / Z;   pu = gu rz;   pv = gv rz;   pz = -((pu u) + (pv v))                   (u, v: the pinhole quotients)
+ *   the nine matrix terms:  pu xs, pu ys, pu,   pv xs, pv ys, pv,   pz xs, pz ys, pz
+ *   s = (a xn) + (b yn);   s1 = s r2;   s2 = s1 r2;   s3 = s2 r2
+ *   the nine lens terms:  fx: (gud xd) - (gu xn)     fy: (gvd yd) - (gv yn)     cx: gud - gu     cy: gvd - gv
+ *                         k1: s1     k2: s2     p1: (a t) + (b (r2 + (2 yy)))     p2: (a (r2 + (2 xx))) + (b t)     k3: s3
+ * A pixel whose `ok` is false contributes nothing -- a select: a NaN in grad_values under it changes no bit.  A matrix or a
+ * lens row under which no sub-sample is valid gives all-zero rows in both outputs.  With the null lens the nine matrix
+ * sums are svbrdf_rectify_photos_grad_matrices' bit for bit.  Every load address lies inside the source, as in the forward.
+ * The sum is svbrdf_rectify_photos_grad_matrices' with eighteen words per workgroup instead of nine: k^2 - 1 thread
+ * additions, the 64-lane butterfly, (w0 + w1) + (w2 + w3), write-through vector stores, a drain, the per-photo integer
+ * ticket; the last workgroup adds the partials in float64 in index order and rounds ONCE.  No float atomic, bitwise the same
+ * in every launch.  SVBRDF_RECTIFY_GRAD_DEPTH bounds it as it bounds the other:  |sum_n - exact sum of the float32 terms|
+ * <= (SVBRDF_RECTIFY_GRAD_DEPTH + 1) * 2^-24 * A_n.
+ * `workspace`: svbrdf_rectify_lens_grad_workspace_bytes(P, Hd, Wd) bytes (the tickets and eighteen words per tile; 0 for
+ * sizes outside the limits), 8-byte aligned, zeroed once by the caller and left zeroed by every completed call.
+ * Error codes before any launch: svbrdf_rectify_photos_grad_matrices', then the forward's for `lens`; SVBRDF_ERR_NULL for
+ * grad_lens, SVBRDF_ERR_ALIGN for one off 4 bytes.
+ * ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect the two by symbol presence. */
+SVBRDF_API size_t svbrdf_rectify_lens_grad_workspace_bytes(int P, int Hd, int Wd);
+SVBRDF_API int svbrdf_rectify_photos_lens_grad(const void *src, int src_format, int P, int Hs, int Ws, const float *matrices,
+                                               const float *lens, int Hd, int Wd, int k, const float *lut, float clip_lo,
+                                               float clip_hi, const float *grad_values, float *grad_matrices,
+                                               float *grad_lens, void *workspace, size_t workspace_bytes, void *stream);
+
 /* data[i] *= scale_dev[0] for i < n, on the device and without a host sync; when the
  * scalar is exactly 1.0 the kernel exits without touching `data`.  Used by the autograd
  * wrapper to apply the upstream gradient of the loss (the chain rule through

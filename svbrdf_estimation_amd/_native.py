@@ -109,6 +109,14 @@ SIGNATURES = {
     # src, format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi, grad_values, grad_matrices, ws, bytes, stream
     "svbrdf_rectify_photos_grad_matrices": (_int, [_fp, _int, _int, _int, _int, _fp, _int, _int, _int, _fp, _float, _float,
                                                    _fp, _fp, _fp, _size, _fp]),
+    # src, format, P, Hs, Ws, matrices, lens, Hd, Wd, k, lut, clip_lo, clip_hi, out, weights_out, stream
+    "svbrdf_rectify_photos_lens": (_int, [_fp, _int, _int, _int, _int, _fp, _fp, _int, _int, _int, _fp, _float, _float, _fp, _fp,
+                                          _fp]),
+    "svbrdf_rectify_lens_grad_workspace_bytes": (_size, [_int] * 3),
+    # src, format, P, Hs, Ws, matrices, lens, Hd, Wd, k, lut, clip_lo, clip_hi, grad_values, grad_matrices, grad_lens, ws,
+    # bytes, stream
+    "svbrdf_rectify_photos_lens_grad": (_int, [_fp, _int, _int, _int, _int, _fp, _fp, _int, _int, _int, _fp, _float, _float,
+                                               _fp, _fp, _fp, _fp, _size, _fp]),
     "svbrdf_scale_inplace": (_int, [_fp, _fp, _size, _fp]),
     "svbrdf_debug_check_arith": (_int, [_u64, ctypes.c_uint, _float, _float, _fp, _fp]),
     "svbrdf_mix_materials": (_int, [_fp] * 4 + [_int] * 3 + [_fp]),
@@ -757,6 +765,24 @@ def rectify_grad_matrices(src, fmt, P, Hs, Ws, matrices, Hd, Wd, k, lut, lo, hi,
           None if lut is None else lut.data_ptr(), lo, hi, grad_values.data_ptr(), out.data_ptr(), ws.data_ptr(),
           ws.numel() * 8)
     return out
+
+
+def rectify_lens_grad(src, fmt, P, Hs, Ws, matrices, lens, Hd, Wd, k, lut, lo, hi, grad_values):
+    """svbrdf_rectify_photos_lens_grad, ONE launch: the gradient of ``capture.rectify(..., lens=)``'s values towards its
+    float32 ``[P,9]`` device matrices (through the lens's Jacobian) and towards its float32 ``[P,9]`` device lens rows, from
+    ``grad_values`` float32 ``[P,3,Hd,Wd]`` contiguous on the device of ``src``.  The scratch is ``rectify_grad_matrices``'
+    (one buffer per device and stream, zeroed once, left zeroed by every call).  -> (float32 ``[P,9]``, float32 ``[P,9]``)"""
+    _require_device_f32(grad_values, "grad_values")
+    if tuple(grad_values.shape) != (P, 3, Hd, Wd) or not grad_values.is_contiguous() or grad_values.device != src.device:
+        raise ValueError("grad_values must be contiguous [%d,3,%d,%d] on %s" % (P, Hd, Wd, src.device))
+    nbytes = _load().svbrdf_rectify_lens_grad_workspace_bytes(P, Hd, Wd)
+    ws = _workspace(src.device, nbytes)
+    gm = torch.empty((P, 9), dtype=torch.float32, device=src.device)
+    gl = torch.empty((P, 9), dtype=torch.float32, device=src.device)
+    _call("svbrdf_rectify_photos_lens_grad", src.device, src.data_ptr(), fmt, P, Hs, Ws, matrices.data_ptr(), lens.data_ptr(),
+          Hd, Wd, k, None if lut is None else lut.data_ptr(), lo, hi, grad_values.data_ptr(), gm.data_ptr(), gl.data_ptr(),
+          ws.data_ptr(), ws.numel() * 8)
+    return gm, gl
 
 
 def clock_probe(out, ticks=300000, stream=None):

@@ -33,6 +33,22 @@ from the four corner positions differentiably, and an optimiser holds the eight 
 
 No gradient flows towards the images, the weights are piecewise constant (marked non-differentiable), and there is no double
 backward.  There is no CPU path.
+
+Lens distortion.  A homography is exact only for a pinhole camera; a hand-held phone bends straight lines by several pixels
+towards the frame's edge.  ``rectify(..., lens=)`` takes OpenCV's ``fx, fy, cx, cy, k1, k2, p1, p2, k3`` per photo
+(``lens_table``; ``pinhole_lens`` gives this module's camera with zero coefficients) and applies the FORWARD model, ideal
+pixel -> distorted pixel, inside the same one launch (svbrdf_rectify_photos_lens, csrc/svbrdf_capture_lens.hip): a
+closed-form polynomial between the homography and the taps, no iteration.  The matrices then map to IDEAL coordinates.
+Corners clicked in a photograph are DISTORTED coordinates, while ``patch_homography`` / ``corner_matrices`` need ideal ones:
+
+    ideal = capture.undistort_points(clicked, lens)                  # Newton on the host, float64
+    M = capture.patch_homography(ideal, (256, 256))
+    photos, weights = capture.rectify(images_u8, M, 256, lut=capture.gamma_lut(), lens=lens)
+
+If ``matrices`` and/or ``lens`` require grad the backward is ONE launch (svbrdf_rectify_photos_lens_grad,
+csrc/svbrdf_capture_lens_grad.hip) that returns both gradients, the matrices' through the lens's Jacobian.  Refine ONE
+coefficient per stage (k1 beside the corners): k1 and k2 trade off against each other on a patch that covers the middle
+of the frame.  ``to_perspective`` stays pinhole: rendering INTO a distorted camera needs the inverse map per pixel.
 """
 import math
 
@@ -186,6 +202,89 @@ def perspective_matrix(camera_pos, sensor_size, size, t=1.0, dtype=np.float32):
     return np.linalg.inv(blend).astype(dtype)
 
 
+# ------------------------------------------------------------------------------------------------ lens distortion
+
+def lens_table(fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, k3=0.0):
+    """float32 [9]: ``fx, fy, cx, cy, k1, k2, p1, p2, k3`` -- OpenCV's camera matrix entries and its distortion vector in
+    OpenCV's order -- as ``rectify(..., lens=)`` takes it"""
+    return torch.tensor([fx, fy, cx, cy, k1, k2, p1, p2, k3], dtype=torch.float64).to(torch.float32)
+
+
+def pinhole_lens(sensor_size):
+    """float32 [9]: the intrinsics of this module's camera (``_camera``: focal length = width / 2, principal point at the
+    sensor's centre (width / 2, height / 2)) with zero distortion coefficients, for ``sensor_size`` = (width, height)"""
+    K, _, _ = _camera((0.0, 0.0, 1.0), sensor_size)
+    return lens_table(K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+
+
+def _lens_f64(lens):
+    lens = np.asarray(lens.detach().cpu() if isinstance(lens, torch.Tensor) else lens, np.float64)
+    if lens.shape != (9,):
+        raise ValueError("lens must be [9]: fx, fy, cx, cy, k1, k2, p1, p2, k3")
+    return lens
+
+
+def _distort_normalised(xn, yn, lens):
+    """(xd, yd, mono, jxx, jxy, jyy) of the polynomial at normalised coordinates, float64"""
+    _, _, _, _, k1, k2, p1, p2, k3 = lens
+    xx, yy, xy = xn * xn, yn * yn, xn * yn
+    r2 = xx + yy
+    rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+    mono = 1.0 + r2 * (3.0 * k1 + r2 * (5.0 * k2 + r2 * (7.0 * k3)))
+    xd = xn * rad + (p1 * 2.0 * xy + p2 * (r2 + 2.0 * xx))
+    yd = yn * rad + (p1 * (r2 + 2.0 * yy) + p2 * 2.0 * xy)
+    q = k1 + r2 * (2.0 * k2 + 3.0 * k3 * r2)
+    jxx = rad + 2.0 * xx * q + 2.0 * p1 * yn + 6.0 * p2 * xn
+    jxy = 2.0 * xy * q + 2.0 * p1 * xn + 2.0 * p2 * yn
+    jyy = rad + 2.0 * yy * q + 6.0 * p1 * yn + 2.0 * p2 * xn
+    return xd, yd, mono, jxx, jxy, jyy
+
+
+def distort_points(points, lens):
+    """Ideal (pinhole) pixel coordinates ``[...,2]`` (x, y) -> where the lens puts them, numpy float64 on the host: OpenCV's
+    forward model, xn = (x - cx) / fx, r2 = xn^2 + yn^2, xd = xn (1 + k1 r2 + k2 r2^2 + k3 r2^3) + 2 p1 xn yn + p2 (r2 +
+    2 xn^2), yd likewise with p1 (r2 + 2 yn^2) + 2 p2 xn yn, x' = xd fx + cx."""
+    lens = _lens_f64(lens)
+    pts = np.asarray(points, np.float64)
+    if pts.shape[-1:] != (2,):
+        raise ValueError("points must be [...,2]")
+    fx, fy, cx, cy = lens[:4]
+    xd, yd = _distort_normalised((pts[..., 0] - cx) / fx, (pts[..., 1] - cy) / fy, lens)[:2]
+    return np.stack((xd * fx + cx, yd * fy + cy), axis=-1)
+
+
+def undistort_points(points, lens):
+    """The inverse of ``distort_points``: distorted pixel coordinates ``[...,2]`` (corners clicked in a photograph) -> ideal
+    ones (what ``patch_homography`` / ``corner_matrices`` need), numpy float64 on the host.  Newton iteration with the
+    polynomial's 2x2 Jacobian from the point itself; it stops at a step below 1e-12 px or after 50 iterations, and raises
+    ``ValueError`` if it did not converge or ended where the radial map has folded back (mono <= 0)."""
+    lens = _lens_f64(lens)
+    pts = np.asarray(points, np.float64)
+    if pts.shape[-1:] != (2,):
+        raise ValueError("points must be [...,2]")
+    fx, fy, cx, cy = lens[:4]
+    tx, ty = (pts[..., 0] - cx) / fx, (pts[..., 1] - cy) / fy
+    xn, yn = tx.copy(), ty.copy()
+    converged = False
+    with np.errstate(all="ignore"):
+        for _ in range(50):
+            xd, yd, _, jxx, jxy, jyy = _distort_normalised(xn, yn, lens)
+            ex, ey = xd - tx, yd - ty
+            det = jxx * jyy - jxy * jxy
+            dx, dy = (jyy * ex - jxy * ey) / det, (jxx * ey - jxy * ex) / det
+            xn, yn = xn - dx, yn - dy
+            step = np.max(np.hypot(dx * fx, dy * fy)) if pts.size else 0.0
+            if not np.isfinite(step):
+                break
+            if step < 1e-12:
+                converged = True
+                break
+        mono = _distort_normalised(xn, yn, lens)[2]
+    if not converged or not np.all(mono > 0.0):
+        raise ValueError("undistort_points did not converge inside the lens's monotonic range")
+    return np.stack((xn * fx + cx, yn * fy + cy), axis=-1)
+
+
 # ------------------------------------------------------------------------------------------------ the launch
 
 def _device_matrices(matrices, lead, device):
@@ -204,7 +303,21 @@ def _device_matrices(matrices, lead, device):
     return m.reshape(P, 9).to(device=device, dtype=torch.float32).contiguous()
 
 
-def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights=True):
+def _device_lens(lens, lead, device):
+    """``lens`` (tensor or array, [...,9] with the photos' leading dimensions, or one [9] for all) -> contiguous float32 [P,9]
+    on ``device``"""
+    P = int(np.prod(lead)) if lead else 1
+    t = lens if isinstance(lens, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(lens)))
+    if t.shape[-1:] != (9,):
+        raise ValueError("lens must be [...,9] (fx, fy, cx, cy, k1, k2, p1, p2, k3), got %s" % (tuple(t.shape),))
+    if t.dim() == 1:
+        t = t.expand(P, 9)
+    elif tuple(t.shape[:-1]) != tuple(lead):
+        raise ValueError("lens %s does not match the photos' leading dimensions %s" % (tuple(t.shape), tuple(lead)))
+    return t.reshape(P, 9).to(device=device, dtype=torch.float32).contiguous()
+
+
+def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights=True, lens=None):
     """Source photographs through one homography each onto a ``size`` = (H, W) (or int) grid, ONE launch.
 
     ``photos``: a device tensor, uint8 ``[...,Hs,Ws,3]`` (interleaved, what an image decoder returns) or float32
@@ -220,7 +333,13 @@ def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights
     -> (photos ``[...,3,H,W]``, weights ``[...,H,W]``) float32 on the source's device: what ``PhotoLoss.forward(..., weights)``
     and ``PhotoFit.step`` accept.  A pixel with any invalid sub-sample -- outside the source, behind the horizon, a NaN or
     clipped tap -- has values 0 and weight 0, every other weight 1.  ``want_weights=False``: -> (photos, None), the weight
-    plane is never written."""
+    plane is never written.
+    ``lens``: None (a pinhole camera: the launch above), or ``[...,9]`` with the photos' leading dimensions, or one ``[9]`` for
+    all (``lens_table``): the lens's forward model is applied between the homography and the taps inside the one launch
+    (svbrdf_rectify_photos_lens), and ``matrices`` map to IDEAL source coordinates (``undistort_points`` takes clicked
+    corners there).  A sub-sample where the radial map has folded back is invalid.  If ``matrices`` and/or ``lens`` require
+    grad, the backward is one launch of svbrdf_rectify_photos_lens_grad and returns the gradient in the shape, dtype and
+    device of each input that asked (a shared matrix or a shared lens: the sum over the photos in float64)."""
     if not isinstance(photos, torch.Tensor):
         raise TypeError("photos must be a torch.Tensor")
     if not photos.is_cuda:
@@ -260,6 +379,14 @@ def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights
         raise ValueError("photos must not be empty, got %s" % (tuple(photos.shape),))
     src = photos.contiguous()
     args = (fmt, P, int(Hs), int(Ws), Hd, Wd, int(samples), lo, hi)
+    if lens is not None:
+        wants = [isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled() for t in (matrices, lens)]
+        if any(wants):
+            as_tensor = [t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t)))
+                         for t in (matrices, lens)]
+            return _RectifyLens.apply(as_tensor[0], as_tensor[1], src, lut, args, lead, want_weights)
+        return _launch_rectify_lens(src, _device_matrices(matrices, lead, photos.device),
+                                    _device_lens(lens, lead, photos.device), lut, args, lead, want_weights)
     if isinstance(matrices, torch.Tensor) and matrices.requires_grad and torch.is_grad_enabled():
         return _RectifyMatrices.apply(matrices, src, lut, args, lead, want_weights)
     return _launch_rectify(src, _device_matrices(matrices, lead, photos.device), lut, args, lead, want_weights)
@@ -304,6 +431,55 @@ class _RectifyMatrices(torch.autograd.Function):
         if ctx.shared:
             gm = gm.to(torch.float64).sum(dim=0)
         return gm.reshape(shape).to(device=device, dtype=dtype), None, None, None, None, None
+
+
+def _launch_rectify_lens(src, mats, lens, lut, args, lead, want_weights):
+    """the lens forward's one launch on checked arguments -> (values, weights or None)"""
+    fmt, P, Hs, Ws, Hd, Wd, k, lo, hi = args
+    out = torch.empty(lead + (3, Hd, Wd), dtype=torch.float32, device=src.device)
+    weights = torch.empty(lead + (Hd, Wd), dtype=torch.float32, device=src.device) if want_weights else None
+    _native._call("svbrdf_rectify_photos_lens", src.device, src.data_ptr(), fmt, P, Hs, Ws, mats.data_ptr(), lens.data_ptr(),
+                  Hd, Wd, k, None if lut is None else lut.data_ptr(), lo, hi, out.data_ptr(),
+                  None if weights is None else weights.data_ptr())
+    return out, weights
+
+
+class _RectifyLens(torch.autograd.Function):
+    """``rectify(..., lens=)`` for matrices and/or a lens that require grad.  forward: the same launch.  backward: ONE launch
+    of svbrdf_rectify_photos_lens_grad on ``grad_output.contiguous()`` with the forward's saved arguments; each gradient
+    comes back in the shape, dtype and device of its input (one matrix or one lens for all: the sum over the photos, added
+    in float64), None for an input that did not ask.  Nothing towards the photos; the weights are non-differentiable; no
+    double backward."""
+
+    @staticmethod
+    def forward(ctx, matrices, lens, src, lut, args, lead, want_weights):
+        mats = _device_matrices(matrices.detach(), lead, src.device)
+        rows = _device_lens(lens.detach(), lead, src.device)
+        out, weights = _launch_rectify_lens(src, mats, rows, lut, args, lead, want_weights)
+        ctx.save_for_backward(src, mats, rows, lut)
+        ctx.args = args
+        ctx.like = tuple((t.shape, t.device, t.dtype) for t in (matrices, lens))
+        ctx.shared = (matrices.dim() == (2 if matrices.shape[-2:] == (3, 3) else 1), lens.dim() == 1)
+        if weights is not None:
+            ctx.mark_non_differentiable(weights)
+        return out, weights
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, _grad_weights=None):
+        src, mats, rows, lut = ctx.saved_tensors
+        fmt, P, Hs, Ws, Hd, Wd, k, lo, hi = ctx.args
+        g = grad_out.to(torch.float32).contiguous().reshape(P, 3, Hd, Wd)
+        grads = _native.rectify_lens_grad(src, fmt, P, Hs, Ws, mats, rows, Hd, Wd, k, lut, lo, hi, g)
+        back = []
+        for n, (grad, (shape, device, dtype), shared) in enumerate(zip(grads, ctx.like, ctx.shared)):
+            if not ctx.needs_input_grad[n]:
+                back.append(None)
+                continue
+            if shared:
+                grad = grad.to(torch.float64).sum(dim=0)
+            back.append(grad.reshape(shape).to(device=device, dtype=dtype))
+        return back[0], back[1], None, None, None, None, None
 
 
 def to_perspective(renderings, camera_pos, sensor_size, t=1.0, samples=1):

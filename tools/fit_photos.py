@@ -2,7 +2,8 @@
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
                                [--fit-exposure] [--fit-pose [--pose-lr 0.002]] [--fused-step [--steps-per-launch K]]
-                               [--captured [--sensor 640x480] [--clip 250] [--fit-registration [--corner-noise PX]]]
+                               [--captured [--sensor 640x480] [--clip 250] [--fit-registration [--corner-noise PX]]
+                                [--lens K1[,K2] [--fit-lens [--lens-lr 0.01]]]]
                                [--smooth LAMBDA]
 
 Ground-truth maps come from the tests' deterministic generator (tests/synth.py); their photographs and the light / view of
@@ -55,6 +56,31 @@ of the image from looking like progress), and rectifies again.  The mean corner 
 final map errors at the end.  Whether alternating with maps that are still wrong converges is not known in general: the
 tool records what it does.  Not with ``--steps-per-launch``.
 
+``--lens K1[,K2]`` (only with ``--captured``): the camera has a lens.  ``ingest`` bends every camera image with the lens
+``capture.pinhole_lens(sensor)`` + (k1, k2) on the host before quantisation -- a float64 ``capture.undistort_points`` grid per
+sensor pixel feeds a ``grid_sample`` of the pinhole image; a demo's synthesis, no hot path -- and the corner positions it
+hands on are ``capture.distort_points`` of the true ones: what somebody would click.  Two more fits: one rectified IGNORING
+the lens (the clicked corners into ``patch_homography``, no ``lens=``), one with the true lens (``undistort_points`` of the
+clicked corners, ``capture.rectify(..., lens=)``).  The map error is reported three ways: ignoring the lens, with the true
+lens, and with the pinhole image as before.
+
+A negative K1 may be written ``--lens -0.18,0.04`` or ``--lens=-0.18,0.04``.  A camera at a grazing angle sees a patch
+corner thousands of pixels outside its sensor; the polynomial throws such a point further than Newton comes back from (it
+describes the lens inside the frame only) and nobody clicks there: those corners keep the ideal position this synthesis
+knows, and how many did is printed beside the figure they enter.
+With ``--fit-registration`` the registration fits then run on the bent images with the lens known: the corners given off
+are the ideal ones, and every stage's rectification and its gradient go through ``lens=``.
+
+``--fit-lens`` (with ``--lens`` and ``--fit-registration``): the lens's k1 is NOT known.  The registration fits hold the
+CLICKED corners -- distorted coordinates, given off by ``--corner-noise`` -- as their parameter; the ideal corners that
+``corner_matrices`` needs are ``undistort_points`` of them under the current lens, recomputed at every step, with the
+gradient carried through the implicit inverse (one Newton step in torch ops around the host's solution: d ideal / d clicked
+is the inverse of the polynomial's 2x2 Jacobian, d ideal / d k1 that inverse times -d distorted / d k1).  k1 starts at 0
+and is refined in the registration stage alongside the corners: ONE coefficient shared by all photographs of the camera,
+in its own Adam group (``--lens-lr``); k2 stays as given (k1 and k2 trade off against each other on a patch that covers the
+middle of the frame: one coefficient per stage).  The fit "as given" keeps k1 = 0.  k1 is printed at every stage and the
+three map errors at the end.  Nothing about the alternation's convergence is asserted: the tool records what it does.
+
 ``--smooth LAMBDA``: a smoothness prior across pixels on diffuse, roughness and specular (``fitting.smoothness`` with LAMBDA on
 those nine planes, 0 on the normals): the objective is the photo loss + the prior, the loss printed stays the photo term.
 Without it a pixel that no photograph sees -- every weight 0, as under ``--captured`` -- has an all-zero gradient and stays at
@@ -103,10 +129,19 @@ def main():
     ap.add_argument("--registration-every", type=int, default=20, help="map steps between two registration stages")
     ap.add_argument("--registration-steps", type=int, default=5, help="Adam steps on the corners per stage")
     ap.add_argument("--registration-lr", type=float, default=0.1, help="Adam learning rate of the corners, source pixels")
+    ap.add_argument("--lens", default=None, metavar="K1[,K2]",
+                    help="with --captured: the camera's radial distortion coefficients (a negative K1: --lens -0.18,0.04 or --lens=-0.18,0.04)")
+    ap.add_argument("--fit-lens", action="store_true", help="with --lens and --fit-registration: k1 from 0, refined beside the corners")
+    ap.add_argument("--lens-lr", type=float, default=0.01, help="with --fit-lens: Adam learning rate of k1")
     ap.add_argument("--smooth", type=float, default=None, metavar="LAMBDA",
                     help="smoothness prior across pixels on diffuse, roughness and specular (normals stay at 0); with "
                          "--steps-per-launch K it is K launches, not one")
-    args = ap.parse_args()
+    argv = sys.argv[1:]
+    for n in range(len(argv) - 1):          # argparse takes "-0.18,0.04" for an option: hand it over as --lens=-0.18,0.04
+        if argv[n] == "--lens" and argv[n + 1][:1] == "-" and argv[n + 1][1:2].isdigit():
+            argv[n:n + 2] = ["--lens=" + argv[n + 1]]
+            break
+    args = ap.parse_args(argv)
     if args.smooth is not None and not (args.smooth >= 0.0 and args.smooth < float("inf")):
         ap.error("--smooth must be finite and >= 0")
     if args.steps_per_launch is not None and not args.fused_step:
@@ -118,6 +153,10 @@ def main():
                  "a launch, from a gradient summed over all pixels (a grid barrier) -- use --fused-step without it")
     if args.fit_registration and (not args.captured or args.steps_per_launch is not None):
         ap.error("--fit-registration refines the corners of --captured photographs between single map steps")
+    if args.lens is not None and not args.captured:
+        ap.error("--lens bends the camera images of --captured")
+    if args.fit_lens and (args.lens is None or not args.fit_registration):
+        ap.error("--fit-lens refines k1 in the registration stage: it needs --lens and --fit-registration")
     assert torch.cuda.is_available(), "needs a ROCm device"
     dev = torch.device("cuda:0")
     B, H, S = args.batch, args.size, args.photos
@@ -139,7 +178,7 @@ def main():
     if not args.captured:
         return fit(args, dev, truth, photos, table, hidden)
     on_grid = fit(args, dev, truth, photos, table, hidden)
-    rectified, weights, cameras, images, corners = ingest(args, dev, photos, table)
+    rectified, weights, cameras, images, corners, ideal, _ = ingest(args, dev, photos, table)
     seen = weights.unsqueeze(2).expand_as(photos) > 0
     print("--- the same fit on the captured photographs: %s sensor, gamma 2.2, 8 bits, rectified with 2 x 2 sub-samples; "
           "%.2f %% of the weights are zero, %.2f %% of the pixels are seen by no photograph; mean |rectified - on the grid| %.5f "
@@ -149,19 +188,43 @@ def main():
     captured = fit(args, dev, truth, rectified, table, hidden, weights, cameras)
     print("final mean |d,r,s - truth|: on the grid %.5f, captured %.5f (zero weights: %.2f %%)" % (
         on_grid, captured, 100.0 * (weights == 0).float().mean().item()))
+    lens, beyond = None, None
+    if args.lens is not None:
+        sensor = tuple(int(v) for v in args.sensor.lower().split("x"))
+        coeff = [float(v) for v in args.lens.split(",")] + [0.0]
+        lens = capture.pinhole_lens(sensor).double().numpy()
+        lens[4], lens[5] = coeff[0], coeff[1]
+        errors = []
+        for use in (False, True):
+            bent, w, _, images, corners, _, beyond = ingest(args, dev, photos, table, lens, use)
+            how = "IGNORING the lens"
+            if use:
+                how = "with the true lens (%d of %d clicked corners lie beyond Newton's reach and keep their known ideal position)" % (
+                    int(beyond.sum()), beyond.size)
+            print("--- the captured fit through a lens k1 = %g, k2 = %g, rectified %s; %.2f %% of the weights are zero; mean "
+                  "|rectified - on the grid| %.5f where the weight is 1" % (
+                      lens[4], lens[5], how, 100.0 * (w == 0).float().mean().item(),
+                      (bent - photos)[w.unsqueeze(2).expand_as(photos) > 0].abs().mean().item()))
+            errors.append(fit(args, dev, truth, bent, table, hidden, w, cameras))
+        print("final mean |d,r,s - truth|: ignoring the lens %.5f, with the true lens %.5f, the pinhole image %.5f" % (
+            errors[0], errors[1], captured))
+        captured = errors[1]
     if not args.fit_registration:
         return
+    if lens is not None and not args.fit_lens:
+        corners = ideal                                        # the registration fits know the lens: ideal corners
     noise = args.corner_noise * (2.0 * synth.uniform01(args.seed + 4000, corners.shape) - 1.0)
     results = []
     for refine in (False, True):
-        reg = Registration(args, images, corners, corners + noise, H)
+        reg = Registration(args, images, corners, corners + noise, H, lens, (ideal, beyond) if args.fit_lens else None)
         print("--- the captured fit with every corner coordinate given up to %g source pixels off (mean corner error %.3f px), %s"
               % (args.corner_noise, reg.error(), "refined every %d map steps (%d Adam steps, lr %g)" % (
                   args.registration_every, args.registration_steps, args.registration_lr) if refine else "left as given"))
         shifted, w = reg.rectify()
         results.append((fit(args, dev, truth, shifted, table, hidden, w, cameras, reg if refine else None), reg.error()))
     print("final mean |d,r,s - truth|: true corners %.5f; corners %g px off, as given %.5f (corner error %.3f px), refined %.5f "
-          "(corner error %.3f px)" % (captured, args.corner_noise, results[0][0], results[0][1], results[1][0], results[1][1]))
+          "(corner error %.3f px)%s" % (captured, args.corner_noise, results[0][0], results[0][1], results[1][0], results[1][1],
+                                        reg.lens_text()))
 
 
 class Registration:
@@ -169,19 +232,63 @@ class Registration:
 
     EPS = 0.01
 
-    def __init__(self, args, images, true_corners, start_corners, H):
+    def __init__(self, args, images, true_corners, start_corners, H, lens=None, unknown=None):
+        """`lens`: float64 [9] of the camera, or None.  `unknown` None: the lens is known and the corners are ideal
+        coordinates.  `unknown` = (ideal, beyond), --fit-lens: the corners are the CLICKED, distorted ones, k1 starts at 0 as a
+        parameter of its own Adam group, and the ideal corners follow from both at every step (`ideal_of`); `ideal` [B,S,4,2]
+        are the true corners' ideal positions, which the corners marked in `beyond` (no Newton from where the polynomial
+        throws them) keep, moved by what their parameter has moved."""
         self.args, self.images, self.H = args, images, H
+        self.lens = None if lens is None else torch.from_numpy(np.array(lens, np.float64))
         self.true = torch.from_numpy(true_corners)
         self.corners = torch.from_numpy(start_corners).clone().requires_grad_(True)
-        self.opt = torch.optim.Adam([self.corners], lr=args.registration_lr)
+        groups = [{"params": [self.corners]}]
+        self.k1 = None
+        if unknown is not None:
+            self.true_k1 = float(lens[4])
+            self.lens[4] = 0.0
+            self.k1 = torch.zeros((), dtype=torch.float64, requires_grad=True)
+            self.known, self.beyond = torch.from_numpy(unknown[0]), torch.from_numpy(unknown[1])
+            groups.append({"params": [self.k1], "lr": args.lens_lr})
+        self.opt = torch.optim.Adam(groups, lr=args.registration_lr)
         self.lut = capture.gamma_lut()
 
     def error(self):
         return (self.corners.detach() - self.true).norm(dim=-1).mean().item()
 
+    def lens_text(self):
+        return "" if self.k1 is None else "; k1 %.5f (truth %g)" % (self.k1.item(), self.true_k1)
+
+    def ideal_of(self, lens):
+        """--fit-lens: the ideal corners of the clicked ones under `lens` (a tensor [9] that may require grad), differentiable
+        towards both.  The host solves x0 = undistort_points(clicked, lens); one Newton step around it in torch ops,
+        x0 - J^-1 (distort(x0, lens) - clicked) with J the polynomial's Jacobian at x0 as a constant, has x0's value and the
+        implicit inverse's gradients."""
+        moved = self.corners - self.true                            # what the parameter has moved, with its gradient
+        kept = self.known + moved
+        x0, failed = ideal_corners(self.corners.detach().numpy(), lens.detach().numpy(), kept.detach().numpy())
+        failed = torch.from_numpy(failed) | self.beyond
+        l = lens.detach().numpy()
+        xn, yn = (x0[..., 0] - l[2]) / l[0], (x0[..., 1] - l[3]) / l[1]
+        _, _, _, jxx, jxy, jyy = capture._distort_normalised(xn, yn, l)
+        a, b, c, d = jxx, jxy * l[0] / l[1], jxy * l[1] / l[0], jyy  # d (ud, vd) / d (u, v) in pixels
+        det = a * d - b * c
+        inv = torch.from_numpy(np.stack((np.stack((d, -b), -1), np.stack((-c, a), -1)), -2) / det[..., None, None])
+        r = distort_torch(torch.from_numpy(x0), lens) - self.corners
+        step = (inv * r[..., None, :]).sum(dim=-1)
+        return torch.where(failed[..., None], kept, torch.from_numpy(x0) - step)
+
     def rectify(self, grad=False):
-        M = capture.corner_matrices(self.corners, self.H)
-        return capture.rectify(self.images, M if grad else M.detach(), self.H, lut=self.lut, clip=(0, self.args.clip), samples=2)
+        lens, corners = self.lens, self.corners
+        if self.k1 is not None:
+            pick = torch.zeros(9, dtype=torch.float64)
+            pick[4] = 1.0
+            lens = lens + pick * self.k1
+            corners = self.ideal_of(lens)
+        M = capture.corner_matrices(corners, self.H)
+        if not grad:
+            M, lens = M.detach(), None if lens is None else lens.detach()
+        return capture.rectify(self.images, M, self.H, lut=self.lut, clip=(0, self.args.clip), samples=2, lens=lens)
 
     def refine(self, maps, scenes):
         """one stage: a few Adam steps on the corners against the rendering of `maps` under `scenes` -> (photos, weights)"""
@@ -206,21 +313,75 @@ def band_limited_maps(seed, B, H, cell=8):
     return maps.contiguous()
 
 
-def ingest(args, dev, photos, table):
+def ideal_corners(clicked, lens, fallback):
+    """capture.undistort_points per corner -> (ideal [...,2], failed [...] bool).  A camera at a grazing angle sees a patch
+    corner thousands of pixels outside its sensor; the polynomial throws such a point further than Newton comes back from (it
+    describes the lens inside the frame only), and nobody clicks there: those corners take `fallback`'s position."""
+    clicked, fallback = np.asarray(clicked, np.float64), np.asarray(fallback, np.float64)
+    out = fallback.copy().reshape(-1, 2)
+    failed = np.zeros(len(out), bool)
+    for n, point in enumerate(clicked.reshape(-1, 2)):
+        try:
+            out[n] = capture.undistort_points(point, lens)
+        except ValueError:
+            failed[n] = True
+    return out.reshape(clicked.shape), failed.reshape(clicked.shape[:-1])
+
+
+def distort_torch(points, lens):
+    """capture.distort_points in torch ops, differentiable towards `points` [...,2] and `lens` [9]"""
+    fx, fy, cx, cy, k1, k2, p1, p2, k3 = lens.unbind()
+    xn, yn = (points[..., 0] - cx) / fx, (points[..., 1] - cy) / fy
+    xx, yy, xy = xn * xn, yn * yn, xn * yn
+    r2 = xx + yy
+    rad = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+    xd = xn * rad + (p1 * 2.0 * xy + p2 * (r2 + 2.0 * xx))
+    yd = yn * rad + (p1 * (r2 + 2.0 * yy) + p2 * 2.0 * xy)
+    return torch.stack((xd * fx + cx, yd * fy + cy), dim=-1)
+
+
+def bend(seen, lens):
+    """--lens: the pinhole images [B,S,3,h,w] as the lens delivers them.  Every sensor pixel is a DISTORTED position; its ideal
+    position (capture.undistort_points, float64 on the host) is where the pinhole image is read, bilinearly, zeros outside."""
+    h, w = seen.shape[-2:]
+    yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+    ideal = capture.undistort_points(np.stack((xx, yy), axis=-1), lens)
+    grid = torch.from_numpy(np.stack((2.0 * ideal[..., 0] / (w - 1) - 1.0, 2.0 * ideal[..., 1] / (h - 1) - 1.0), axis=-1)).float()
+    flat = seen.reshape((-1,) + tuple(seen.shape[-3:]))
+    out = torch.nn.functional.grid_sample(flat, grid.to(seen.device)[None].expand(flat.shape[0], h, w, 2), mode="bilinear",
+                                          padding_mode="zeros", align_corners=True)
+    return out.reshape(seen.shape)
+
+
+def ingest(args, dev, photos, table, lens=None, use_lens=True):
     """--captured: the photographs as a camera at each photo's position delivers them -- perspective, gamma 2.2, 8 bits --
     and back onto the grid -> (photos [B,S,3,H,W], weights [B,S,H,W], the camera positions recovered from the corners, the
-    8-bit images [B,S,h,w,3], the corners [B,S,4,2] in their pixels)"""
+    8-bit images [B,S,h,w,3], the corners [B,S,4,2] in their pixels as handed on, their ideal positions, and which of them
+    lie beyond Newton's reach [B,S,4]).  `lens` (float64 [9]): the images are bent with it before
+    quantisation and the corners handed on are where the lens puts them; the rectification then either ignores the lens
+    (those corners into patch_homography) or, `use_lens`, undoes it (their ideal positions, and lens= in the one launch)."""
     sensor = tuple(int(v) for v in args.sensor.lower().split("x"))
     B, S, H = photos.shape[0], photos.shape[1], photos.shape[-1]
     cams = table[..., :3].cpu().numpy().astype(np.float64)
     seen = capture.to_perspective(photos, cams, sensor)                                  # [B,S,3,sensor h,sensor w]
+    if lens is not None:
+        seen = bend(seen, lens)
     codes = (seen.clamp(0.0, 1.0).cpu().double().pow(1.0 / 2.2) * 255.0).round().to(torch.uint8)
     images = codes.permute(0, 1, 3, 4, 2).contiguous().to(dev)                           # what an image decoder returns: HWC
     corners = [capture.camera_corners(c, sensor) for c in cams.reshape(-1, 3)]
-    matrices = np.stack([capture.patch_homography(c, (H, H)) for c in corners]).reshape(B, S, 3, 3)
-    rectified, weights = capture.rectify(images, matrices, H, lut=capture.gamma_lut(), clip=(0, args.clip), samples=2)
     recovered = np.stack([capture.camera_from_corners(c, sensor) for c in corners]).reshape(B, S, 3)
-    return rectified, weights, torch.from_numpy(recovered).float().to(dev), images, np.stack(corners).reshape(B, S, 4, 2)
+    shown = corners if lens is None else [capture.distort_points(c, lens) for c in corners]
+    beyond = np.zeros((len(corners), 4), bool)
+    used = shown
+    if lens is not None:
+        solved = [ideal_corners(d, lens, c) for d, c in zip(shown, corners)]
+        beyond = np.stack([f for _, f in solved])
+        used = [c for c, _ in solved] if use_lens else shown
+    matrices = np.stack([capture.patch_homography(c, (H, H)) for c in used]).reshape(B, S, 3, 3)
+    rectified, weights = capture.rectify(images, matrices, H, lut=capture.gamma_lut(), clip=(0, args.clip), samples=2,
+                                         lens=lens if use_lens else None)
+    return (rectified, weights, torch.from_numpy(recovered).float().to(dev), images, np.stack(shown).reshape(B, S, 4, 2),
+            np.stack(corners).reshape(B, S, 4, 2), beyond.reshape(B, S, 4))
 
 
 def map_error(x, truth, unseen):
@@ -283,7 +444,7 @@ def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None, reg
                     scenes = torch.cat((scenes[..., :6], scenes[..., 6:] * log_e.exp()), dim=-1)
             photos, weights = registration.refine(x, scenes)
             unseen = weights.amax(dim=1, keepdim=True) == 0
-            print("step %4d  registration stage: mean corner error %.3f px" % (step, registration.error()))
+            print("step %4d  registration stage: mean corner error %.3f px%s" % (step, registration.error(), registration.lens_text()))
         if fit is not None and opt is None:
             loss = fit.step(photos, table, weights)
         elif fit is not None:
