@@ -190,7 +190,8 @@ SVBRDF_API int svbrdf_head_loss_fwd_bwd_host_scenes(const float *encoded9, const
  * in `input` or `photos`, or a photo value at or below -eps (where torch.log gives NaN or -inf), gives loss_out[0] = NaN
  * with the scratch still left zeroed; bitwise run-to-run reproducible; error codes, 4-byte alignment rule (every aligned
  * pointer takes the same one-pixel-per-lane path: same results), eps in [1e-9, 1e9], and the scratch of
- * svbrdf_rendering_loss_workspace_bytes() with its zero-once / left-zeroed contract.  No gradient w.r.t. photos or scenes.
+ * svbrdf_rendering_loss_workspace_bytes() with its zero-once / left-zeroed contract.  No gradient w.r.t. photos or scenes
+ * (photos: svbrdf_[head_]photo_loss_photo_grad_fwd_bwd below; scenes: the scene-gradient entries).
  * `_host_scenes`: the B*S rows in HOST memory travel by value in the launch's argument block
  * (B*S <= SVBRDF_HOST_SCENES_MAX_ROWS, SVBRDF_ERR_DIMS beyond); bitwise the results of the device-table entry.
  * Limits of S, for every photo entry below as well: forward-only (grad NULL) S <= 1706 -- the item's table is staged in LDS --,
@@ -256,7 +257,7 @@ SVBRDF_API int svbrdf_head_photo_loss_fwd_bwd_host_scenes(const float *encoded9,
  * unweighted entries': PyTorch's sub-gradient conventions, bitwise run-to-run reproducibility, the scratch contract, the
  * error codes before any launch (`weights` is required: SVBRDF_ERR_NULL; 4-byte aligned: SVBRDF_ERR_ALIGN; every aligned
  * pointer gives the same results), the eps range and the `_host_scenes` limit.  No gradient w.r.t. weights, photos or
- * scenes.  ADDED TO ABI VERSION 8 WITHOUT A BUMP, like the head entries above: detect the four by symbol presence. */
+ * scenes (photos: svbrdf_[head_]photo_loss_photo_grad_fwd_bwd below).  ADDED TO ABI VERSION 8 WITHOUT A BUMP, like the head entries above: detect the four by symbol presence. */
 SVBRDF_API int svbrdf_photo_loss_weighted_fwd_bwd(const float *input, const float *photos, const float *weights,
                                                   int weight_planes, const float *scenes, const float *xrow, float eps,
                                                   float *loss_out, float *grad_input, void *workspace,
@@ -293,7 +294,8 @@ SVBRDF_API int svbrdf_head_photo_loss_weighted_fwd_bwd_host_scenes(const float *
  *    `exposure` in float32; an all-ones exposure gives those entries' results on the table as it is.
  *  - grad_exposure is summed in integers (fixed point 2^-24 per wave of 64 pixels): bitwise reproducible run to run.  A
  *    zero-weight plane gives exactly (+-)0 in its photo's three entries.
- *  - NO GRADIENT WITH RESPECT TO LIGHT OR CAMERA POSITIONS here (the scene-gradient entries below have it), nor to weights or photos.
+ *  - NO GRADIENT WITH RESPECT TO LIGHT OR CAMERA POSITIONS here (the scene-gradient entries below have it), nor to weights or photos
+ *    (photos: svbrdf_[head_]photo_loss_photo_grad_fwd_bwd below, without an exposure).
  * The scene table is in device memory (no by-value form).  `workspace`: svbrdf_photo_exposure_workspace_bytes(B, S, H, W)
  * bytes = the 65 words of svbrdf_rendering_loss_workspace_bytes plus B S 3 accumulator words, under the same contract:
  * zeroed once by the caller, left zeroed by every completed call (a NaN report included), so one buffer zeroed at that
@@ -344,6 +346,46 @@ SVBRDF_API int svbrdf_head_photo_loss_scene_grad_fwd_bwd(const float *encoded9, 
                                                          int weight_planes, const float *scenes, const float *xrow,
                                                          float eps, float *loss_out, float *grad_encoded9,
                                                          float *grad_scenes, void *workspace, size_t workspace_bytes,
+                                                         int B, int S, int H, int W, void *stream);
+
+/* The photo losses with the gradient towards the PHOTOGRAPHS, still ONE launch: what the gradient entries of
+ * svbrdf_rectify_photos take as `grad_values`, so that the homographies and the lens of a capture are fitted against the
+ * loss the maps are fitted with.  With w, p' and N as in the weighted entries (w = 1, p' = photo when `weights` is NULL,
+ * and then weight_planes must be 0) and delta = log(render + eps) - log(p' + eps):
+ *   loss_out[0] = (1/N) sum w | delta |
+ *   grad_input  = d loss / d input, or NULL: the forward-only scene loop (loss + grad_photos; what a registration stage
+ *                 launches, the maps being constants there)
+ *   grad_photos = d loss / d photos [B,S,3,H,W] (REQUIRED) = -(w/N) sign(delta) / (photo + eps), upstream gradient 1.0
+ *  - loss_out and grad_input / grad_encoded9 EQUAL BIT FOR BIT those of svbrdf_[head_]photo_loss[_weighted]_fwd_bwd on the
+ *    same arguments; with grad_input NULL the loss equals the forward-only twin's bit for bit.
+ *  - Every element of grad_photos is +m, -m or 0.  The magnitude m = (w fl(1/N)) / fl(photo + eps) is a pure function of w,
+ *    N, eps and that one photo value: fl(1/N) is the double quotient rounded to float32, then one float32 multiply, one
+ *    float32 add and one IEEE float32 division, each individually rounded (4 roundings; no fused multiply-add).  The
+ *    kernel divides by fl(photo + eps) 2^-10 and scales by 2^-10: a power of two commutes with the rounding.
+ *  - The sign is -sign(delta) as the kernel's own log of the quotient decides it -- the sign the map adjoint of the same
+ *    launch uses -- with torch's sign(0) = 0: equal operands, or a quotient that rounds to exactly 1, give exactly 0.
+ *  - A weight of exactly 0 gives exactly (+-)0 whatever the photo holds there (NaN, +-inf, a value at or below -eps): a
+ *    select, 0 * NaN is never formed.
+ *  - Elements are independent: another photo value changes its own element and the loss, and no other bit of grad_photos.
+ *  - A term whose delta is NaN gives a NaN element: non-finite maps at that pixel, a photo value that is NaN or at or
+ *    below -eps under w > 0, a weight outside [0, 1] or NaN (its pixel's three elements).  Every other element keeps its
+ *    value even when loss_out[0] is NaN.  Under a +inf photo with w > 0 the element is 0 or NaN, nothing more is specified.
+ *  - NO GRADIENT WITH RESPECT TO WEIGHTS, and none towards scenes or an exposure in these entries.
+ * The scene table is in device memory (no by-value form).  `workspace`: svbrdf_rendering_loss_workspace_bytes with its
+ * zero-once / left-zeroed contract, left zeroed in every case above.  Error codes before any launch as the weighted
+ * entries': grad_photos NULL gives SVBRDF_ERR_NULL, every pointer 4-byte aligned (every aligned pointer gives the same
+ * results).  Limits of S are the twin loops': S <= 1706 with grad_input NULL, any S with it.  HBM traffic
+ * (12 + 3 S + P + 12 + 3 S) * 4 bytes per pixel for the maps entry ((9 + 3 S + P + 9 + 3 S) * 4 for the head entry; without
+ * grad_input its planes less), plain stores.  ADDED TO ABI VERSION 8 WITHOUT A BUMP: detect the two by symbol presence. */
+SVBRDF_API int svbrdf_photo_loss_photo_grad_fwd_bwd(const float *input, const float *photos, const float *weights,
+                                                    int weight_planes, const float *scenes, const float *xrow, float eps,
+                                                    float *loss_out, float *grad_input, float *grad_photos,
+                                                    void *workspace, size_t workspace_bytes, int B, int S, int H, int W,
+                                                    void *stream);
+SVBRDF_API int svbrdf_head_photo_loss_photo_grad_fwd_bwd(const float *encoded9, const float *photos, const float *weights,
+                                                         int weight_planes, const float *scenes, const float *xrow,
+                                                         float eps, float *loss_out, float *grad_encoded9,
+                                                         float *grad_photos, void *workspace, size_t workspace_bytes,
                                                          int B, int S, int H, int W, void *stream);
 
 /* One STEP of a fit of the maps to photographs, ONE launch: the (weighted) photo loss at the maps as they are, its gradient

@@ -96,6 +96,9 @@ SIGNATURES = {
     "svbrdf_photo_scene_grad_workspace_bytes": (_size, [_int] * 4),
     "svbrdf_photo_loss_scene_grad_fwd_bwd": (_int, _LOSS_SG),
     "svbrdf_head_photo_loss_scene_grad_fwd_bwd": (_int, _LOSS_SG),
+    # input, photos, weights, planes, scenes, xrow, eps, loss, grad (or NULL), grad_photos, ws, bytes: _LOSS_SG's list
+    "svbrdf_photo_loss_photo_grad_fwd_bwd": (_int, _LOSS_SG),
+    "svbrdf_head_photo_loss_photo_grad_fwd_bwd": (_int, _LOSS_SG),
     "svbrdf_photo_fit_adam_scalars": (_int, [_float] * 3 + [_int, _fp]),
     "svbrdf_photo_fit_adam_step": (_int, _LOSS_FIT),
     "svbrdf_photo_fit_adam_step_scene_grad": (_int, _LOSS_FIT_SG),
@@ -554,7 +557,7 @@ def _checked_weights(weights, device, B, S, H, W):
 
 
 def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weights=None, exposure=None,
-               want_exposure_grad=False, want_scene_grad=False):
+               want_exposure_grad=False, want_scene_grad=False, want_photo_grad=False):
     """Fused photo loss (svbrdf_photo_loss_fwd_bwd*): mean |log(render(scenes[b,s], input[b]) + eps) - log(photos[b,s] + eps)|
     and d loss/d input in ONE launch.  input [B,12,H,W] and photos [B,S,3,H,W] device fp32; scenes [B,S,9] fp32 on the
     maps' device, or on the HOST (at most host_scenes_max_rows() rows ride in the launch's argument block, a larger table
@@ -574,9 +577,18 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
     svbrdf_*photo_loss_scene_grad_fwd_bwd entries, still ONE launch, with or without ``weights``, forward + adjoint with the
     table in device memory like the exposure entries.  Returns (loss, grad or None, grad_scenes [B,S,9]): d loss/d scenes,
     camera xyz | light xyz | light rgb.  Loss and map gradient equal the entries' without it bit for bit.  A colour that is
-    NaN, infinite or <= 0 gives a NaN loss; a NaN loss comes with an all-NaN grad_scenes."""
+    NaN, infinite or <= 0 gives a NaN loss; a NaN loss comes with an all-NaN grad_scenes.
+
+    ``want_photo_grad=True`` (without ``exposure`` and without ``want_scene_grad``): the
+    svbrdf_*photo_loss_photo_grad_fwd_bwd entries, still ONE launch, with or without ``weights``, table in device memory (a
+    host table is uploaded).  Returns (loss, grad or None, grad_photos [B,S,3,H,W]): d loss/d photos =
+    -(w/N) sign(delta) / (photos + eps) for upstream gradient 1.  Loss and map gradient equal the entries' without it bit for
+    bit; ``want_grad=False`` runs the forward-only scene loop (loss and grad_photos: what a registration stage needs)."""
     if want_scene_grad and exposure is not None:
         raise ValueError("want_scene_grad takes no exposure: multiply the table's colour columns by the gains instead")
+    if want_photo_grad and (exposure is not None or want_scene_grad):
+        raise ValueError("want_photo_grad takes neither an exposure nor want_scene_grad: those combinations are the composed "
+                         "definition's (losses.composed_photo_loss); a constant gain multiplies the table's colour columns")
     _require_device_f32(input, "input")
     _require_device_f32(photos, "photos")
     if photos.device != input.device:
@@ -616,6 +628,15 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
             photos.contiguous(), scenes, (ctypes.c_float(eps),), True, B, S, H, W, extra or (None, 0),
             (grad_scenes.data_ptr(),), "svbrdf_photo_scene_grad_workspace_bytes")
         return loss, (grad if want_grad else None), grad_scenes
+    if want_photo_grad:
+        if on_host:
+            scenes = upload_scene_table(scenes, input.device)
+        photos = photos.contiguous()
+        grad_photos = torch.empty_like(photos)
+        loss, grad = _fused_loss_call(
+            ("svbrdf_head_photo_loss" if head else "svbrdf_photo_loss") + "_photo_grad_fwd_bwd", input.contiguous(), photos,
+            scenes, (ctypes.c_float(eps),), want_grad, B, S, H, W, extra or (None, 0), (grad_photos.data_ptr(),))
+        return loss, grad, grad_photos
     entry = stem + "_fwd_bwd" + ("_host_scenes" if on_host else "")
     return _fused_loss_call(entry, input.contiguous(), photos.contiguous(), scenes, (ctypes.c_float(eps),), want_grad,
                             B, S, H, W, extra)

@@ -199,6 +199,33 @@ __device__ __forceinline__ void pose_bwd(const VConst &K, const PoseRender &pr, 
     for (int k = 0; k < 3; ++k) out[6 + k] = Q[k];
 }
 
+// PGRAD (the photo-gradient kernels of svbrdf_photo_grad_photos.hip; no kernel of svbrdf_photo_loss.hip sets it):
+// d loss / d photo[b,s,c,i,j] = -(w / N) sign(delta) / (photo + eps) for upstream gradient 1, stored where the photo value
+// was loaded from, on another base.  The resource of the render whose terms are being formed (photo_scene_loop advances its
+// base one pass behind the photos' own); an empty one without PGRAD.
+template <bool PGRAD>
+__device__ __forceinline__ PlaneBuf photo_grad_buf(float *render_base, size_t plane, size_t pix)
+{
+    if (PGRAD) return plane_buf(render_base, 3, plane, pix);
+    return PlaneBuf{};
+}
+// One element.  The magnitude m = (w fl(1/N)) / fl(photo + eps): `per_count` is the numerator (w / N as the adjoint holds it,
+// or 1/N), `bt` the denominator in the loss kernels' units (photo_terms: fl(photo + eps) 2^-10 exactly), so m is ONE IEEE
+// division and an exact power-of-two scale -- a pure function of w, N, eps and this photo value, each operation rounded
+// once.  The sign is the sign of `lg` = log2(bt / b) = -delta / ln 2 as the loss and the map adjoint of the same launch
+// hold it: lg == 0 (equal operands, a quotient that rounds to 1, a zero weight -- whatever the photo holds: m is then
+// not selected) gives `zero`, which is w * 0: (+-)0, or NaN for the NaN of a weight outside [0, 1].  A NaN or infinite lg
+// (non-finite maps, a photo that is NaN, infinite or <= -eps under w > 0) gives NaN through the FMA; a finite one adds
+// (+-)0.  Stored once and never read again: a plain store.
+template <bool WEIGHTED>
+__device__ __forceinline__ void photo_grad_store(const PlaneBuf &gb, int k, float lg, float per_count, float bt, float zero)
+{
+    const float m = __builtin_amdgcn_ldexpf(per_count / bt, kLossScaleExp);
+    const float sel = lg == 0.0f ? (WEIGHTED ? zero : 0.0f) : __builtin_copysignf(m, lg);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, fma_(lg, 0.0f, sel)), gb.rsrc, gb.lane_bytes,
+                                          k * gb.plane_bytes, 0);
+}
+
 // one (pixel, scene), tied roughness: loss_pixel_scene with the target shading replaced by the photo's three values.
 // WEIGHTED: `w` is the render's checked weight and `inv_count` already carries it (w / N, folded once per render); a
 // weight of exactly 0 selects every term to exactly 0 -- whatever the photo holds, NaN included: 0 * NaN is never
@@ -207,12 +234,14 @@ __device__ __forceinline__ void pose_bwd(const VConst &K, const PoseRender &pr, 
 // (+-)0), collected for render `s` in front of the adjoint: the three q are dead before its registers are needed.
 // POSE: behind the adjoint, the bars pose_bwd needs from the same registers (shade_bwd's own expressions: the compiler
 // forms them once).
-template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false, bool POSE = false>
+// PGRAD: the three elements of grad_photos of this render, each stored as soon as its lg is known (photo_grad_store).
+template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false, bool POSE = false, bool PGRAD = false>
 __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
                                                   float s10, float eps, float inv_count, float &lsum, Grad &acc,
                                                   [[maybe_unused]] float w = 1.0f,
                                                   [[maybe_unused]] const ExpoLoop *xl = nullptr, [[maybe_unused]] int s = 0,
-                                                  [[maybe_unused]] const PoseRender *pr = nullptr)
+                                                  [[maybe_unused]] const PoseRender *pr = nullptr,
+                                                  [[maybe_unused]] const PlaneBuf *gb = nullptr)
 {
     static_assert(!POSE || WITH_GRAD, "the scene-gradient kernels are forward + adjoint");
     const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
@@ -238,6 +267,7 @@ __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g
         const bool differ = WEIGHTED ? (b[k] != bt[k] && w != 0.0f) : (b[k] != bt[k]);
         const float lg = differ ? log2_(bt[k] * ib[k]) : 0.0f;
         add_term<WEIGHTED>(w, lg, lsum);
+        if (PGRAD) photo_grad_store<WEIGHTED>(*gb, k, lg, inv_count, bt[k], w * 0.0f);
         g_rad[k] = loss_grad_of_b(K, lg, inv_count * ib[k]);
         if (EXPO) {
             const float share = fma_(-ec, ib[k], 1.0f);     // rad / (rad + eps)
@@ -270,13 +300,14 @@ __device__ __forceinline__ void photo_pixel_scene(const VConst &K, const Geom &g
 
 // independent roughness channels: loss_pixel_scene_by_channel with the photo as the target side (POSE: the bar of p and
 // the three Q beside the channels' adjoint)
-template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false, bool POSE = false>
+template <bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false, bool POSE = false, bool PGRAD = false>
 __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
                                                              float s10, float eps, float inv_count, float &lsum, Grad &acc,
                                                              [[maybe_unused]] float w = 1.0f,
                                                              [[maybe_unused]] const ExpoLoop *xl = nullptr,
                                                              [[maybe_unused]] int s = 0,
-                                                             [[maybe_unused]] const PoseRender *pr = nullptr)
+                                                             [[maybe_unused]] const PoseRender *pr = nullptr,
+                                                             [[maybe_unused]] const PlaneBuf *gb = nullptr)
 {
     const Dots di = dots(K, g, mi);
     const float ec = __builtin_amdgcn_ldexpf(eps, kLossScaleExp);
@@ -319,6 +350,14 @@ __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, co
                 g_p = fma_(g_F, mi.oms[k], g_p);
             }
         }
+        if (PGRAD) {
+            // behind the channel's adjoint, where its lobe is dead, and held there: the division's temporaries on top of the
+            // lobe's cost the weighted maps kernel ten VGPRs spilled to scratch around this loop.  (The forward-only loop
+            // has the registers, and the barriers cost it 18 of them: free placement there.)
+            if (WITH_GRAD) __builtin_amdgcn_sched_barrier(0);
+            photo_grad_store<WEIGHTED>(*gb, k, lg, inv_count, bt, w * 0.0f);
+            if (WITH_GRAD) __builtin_amdgcn_sched_barrier(0);
+        }
     }
     if (WITH_GRAD) {
         float g_NH = (sN * 2.0f) * di.NH;
@@ -334,13 +373,24 @@ __device__ __forceinline__ void photo_pixel_scene_by_channel(const VConst &K, co
     }
 }
 
-template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false>
+template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false, bool PGRAD = false>
 __device__ __forceinline__ void photo_pixel_scene_any(const VConst &K, const Geom &g, const MapK &mi, const float ph[3],
                                                       float s10, float eps, float inv_count, float &lsum, Grad &acc,
                                                       [[maybe_unused]] float w_raw = 1.0f,
-                                                      [[maybe_unused]] const ExpoLoop *xl = nullptr, [[maybe_unused]] int s = 0)
+                                                      [[maybe_unused]] const ExpoLoop *xl = nullptr, [[maybe_unused]] int s = 0,
+                                                      [[maybe_unused]] const PlaneBuf *gb = nullptr)
 {
-    if (WEIGHTED) {
+    if (PGRAD) {        // (a branch of its own: the calls below stand as they stood before the flag)
+        static_assert(!PGRAD || !EXPO, "the photo-gradient kernels take no exposure");
+        const float w = WEIGHTED ? checked_weight(w_raw) : 1.0f;
+        const float icw = WEIGHTED ? inv_count * w : inv_count;
+        if (NL == 3)
+            photo_pixel_scene_by_channel<WITH_GRAD, DEFER & 3, WEIGHTED, false, false, PGRAD>(K, g, mi, ph, s10, eps, icw, lsum, acc,
+                                                                                              w, nullptr, 0, nullptr, gb);
+        else
+            photo_pixel_scene<WITH_GRAD, DEFER, WEIGHTED, false, false, PGRAD>(K, g, mi, ph, s10, eps, icw, lsum, acc, w, nullptr,
+                                                                               0, nullptr, gb);
+    } else if (WEIGHTED) {
         if (EXPO) w_raw = xl->live ? w_raw : 0.0f;
         const float w = checked_weight(w_raw);
         const float icw = inv_count * w;        // the weight folded into 1/N once per render
@@ -399,14 +449,18 @@ __device__ __forceinline__ void load_photo_weight(const float *__restrict__ rend
     else load_photo(pp, plane, pix, P);
 // EXPO (forward + adjoint only): the colour of every render is scaled by its gains in front of its geometry
 // (expo_scale), and the render's three q go to the workgroup's sums behind its shading (expo_collect).
-template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false>
+// PGRAD: `gp` is the base of grad_photos of the render that is being SHADED -- `pp` already points at the next one -- so it
+// advances at the end of a pass, one pass behind `pp`: wave-uniform scalar arithmetic, one buffer resource per render as
+// load_photo makes.  In the forward-only loop the store belongs to the render whose values stand in `pa`.
+template <int NL, bool WITH_GRAD, int DEFER, bool WEIGHTED = false, bool EXPO = false, bool PGRAD = false>
 __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float y, const float *__restrict__ scp,
                                                   const float *sc_lds, const float *__restrict__ pp, size_t plane,
                                                   size_t pix, int S, float eps, float inv_count, Grad &acc,
                                                   [[maybe_unused]] const float *__restrict__ wp = nullptr,
                                                   [[maybe_unused]] size_t wstride = 0, [[maybe_unused]] float poison = 0.0f,
                                                   [[maybe_unused]] const ExpoLoop *xl = nullptr,
-                                                  [[maybe_unused]] const float *__restrict__ gain = nullptr)
+                                                  [[maybe_unused]] const float *__restrict__ gain = nullptr,
+                                                  [[maybe_unused]] float *__restrict__ gp = nullptr)
 {
     static_assert(!EXPO || WITH_GRAD, "the exposure kernels are forward + adjoint");
     constexpr int ST = 9;
@@ -449,6 +503,13 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
             SVBRDF_PHOTO_LOAD(P_NEXT, W_NEXT)                                                                      \
             __builtin_amdgcn_sched_barrier(0);                                                                     \
             G_NEXT = geometry<true>(K, cur, x, y);                                                                 \
+            if (PGRAD) {                                                                                           \
+                const PlaneBuf gbuf = photo_grad_buf<PGRAD>(gp, plane, pix);                                       \
+                photo_pixel_scene_any<NL, WITH_GRAD, DEFER, WEIGHTED, EXPO, PGRAD>(K, G_CUR, mi, P_CUR, s10, eps,  \
+                                                                                   inv_count, lsum, acc, W_CUR,    \
+                                                                                   xl, (SI), &gbuf);               \
+                gp += ((SI) + 1 < S) ? render : 0;                                                                 \
+            } else                                                                                                 \
             photo_pixel_scene_any<NL, WITH_GRAD, DEFER, WEIGHTED, EXPO>(K, G_CUR, mi, P_CUR, s10, eps, inv_count,  \
                                                                         lsum, acc, W_CUR, xl, (SI));               \
             SVBRDF_PHOTO_PIN(P_NEXT, W_NEXT)                                                                       \
@@ -472,6 +533,12 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
             __builtin_amdgcn_sched_barrier(0);      // (the scheduler otherwise sinks the three loads to their first use)
             load_scene(sc_lds + (s + 1 < S ? s + 1 : s) * 9, sc);
             g_next = geometry<true>(K, sc, x, y);
+            if (PGRAD) {
+                const PlaneBuf gbuf = photo_grad_buf<PGRAD>(gp, plane, pix);
+                photo_pixel_scene_any<NL, WITH_GRAD, DEFER, WEIGHTED, false, PGRAD>(K, g, mi, pa, s10, eps, inv_count, lsum, acc,
+                                                                                    wa, nullptr, 0, &gbuf);
+                gp += (s + 1 < S) ? render : 0;
+            } else
             photo_pixel_scene_any<NL, WITH_GRAD, DEFER, WEIGHTED>(K, g, mi, pa, s10, eps, inv_count, lsum, acc, wa);
             SVBRDF_PHOTO_PIN(pb, wb)
 #pragma unroll

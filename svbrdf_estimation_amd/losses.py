@@ -292,11 +292,18 @@ class _FusedPhotoLoss(torch.autograd.Function):
         need_in = ctx.needs_input_grad[0]
         need_s = ctx.needs_input_grad[2]            # the scene table's gradient: a device table, no exposure (_forward)
         need_e = exposure is not None and ctx.needs_input_grad[6]
+        need_p = ctx.needs_input_grad[1]            # the photos' gradient: no exposure, no table gradient (_forward)
         # (for backward(create_graph=True) only: references, no copies)
         ctx.save_for_backward(input, photos, *(() if exposure is None else (exposure,)), *((scenes,) if need_s else ()))
         ctx.second_order = (None if need_s else scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head),
                             weights)
-        if need_s:
+        if need_p:
+            # the photo-gradient kernels: map and photo gradient out of the ONE launch; a detached input runs the
+            # forward-only scene loop (loss + grad_photos)
+            loss, grad, grad_p = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights,
+                                                    want_photo_grad=True)
+            ctx.grads = (grad, None, None, grad_p)
+        elif need_s:
             # the scene-gradient kernels: map and table gradient out of the ONE launch
             loss, grad, grad_s = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights,
                                                     want_scene_grad=True)
@@ -320,22 +327,24 @@ class _FusedPhotoLoss(torch.autograd.Function):
             input, photos, *rest = ctx.saved_tensors
             table = rest.pop() if scenes is None else None
             exposure = rest
-            need = [ctx.needs_input_grad[0], bool(exposure) and ctx.needs_input_grad[6], table is not None]
+            need = [ctx.needs_input_grad[0], bool(exposure) and ctx.needs_input_grad[6], table is not None,
+                    ctx.needs_input_grad[1]]
             with torch.enable_grad():
                 x = input.to(torch.float64)
                 e = exposure[0].to(torch.float64) if exposure else None
                 loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes if table is None else table, eps,
                                            weights, e)
-                wanted = [t for t, n in zip((input, exposure[0] if exposure else None, table), need) if n]
+                wanted = [t for t, n in zip((input, exposure[0] if exposure else None, table, photos), need) if n]
                 grads = list(torch.autograd.grad(loss, wanted, grad_loss.to(torch.float64).reshape(()), create_graph=True))
             g_in = grads.pop(0).to(input.dtype) if need[0] else None
             g_e = grads.pop(0).to(exposure[0].dtype) if need[1] else None
             g_s = grads.pop(0) if need[2] else None
-            return g_in, None, g_s, None, None, None, g_e
+            g_p = grads.pop(0) if need[3] else None
+            return g_in, g_p, g_s, None, None, None, g_e
         grads = _hand_over_gradients(ctx, grad_loss, "Trying to backward through the fused photo loss a second time: its "
                                      "gradient buffer was handed to the first backward.  Specify retain_graph=True for "
                                      "the first one.")
-        return (grads[0], None, (grads[2] if len(grads) > 2 else None), None, None, None,
+        return (grads[0], (grads[3] if len(grads) > 3 else None), (grads[2] if len(grads) > 2 else None), None, None, None,
                 (grads[1] if len(grads) > 1 else None))
 
 
@@ -483,20 +492,22 @@ def _check_fused_photo_inputs(loss_name, input_name, input, photos):
 class _PhotoLossModule(nn.Module):
     """What PhotoLoss and HeadPhotoLoss share: the constructor and the routing of a call."""
 
-    def __init__(self, renderer, eps=0.1, normalize="count"):
+    def __init__(self, renderer, eps=0.1, normalize="count", differentiable_photos=False):
         super().__init__()
         if normalize not in _NORMALIZE:
             raise ValueError("normalize must be one of %s, got %r" % (_NORMALIZE, normalize))
         self.renderer = renderer
         self.eps = eps
         self.normalize = normalize
+        self.differentiable_photos = bool(differentiable_photos)
 
     def uses_fused_kernel(self):
         return RenderingLoss(self.renderer).uses_fused_kernel()
 
     def _forward_decoded(self, encoded9, photos, scenes, weights, exposure=None):
         """the head losses' composed definition: PhotoLoss, which normalises by itself, on the decoded maps"""
-        return PhotoLoss(self.renderer, self.eps, self.normalize)(decode_head(encoded9), photos, scenes, weights, exposure)
+        return PhotoLoss(self.renderer, self.eps, self.normalize, self.differentiable_photos)(
+            decode_head(encoded9), photos, scenes, weights, exposure)
 
     def _forward(self, x, photos, scenes, weights, head, exposure=None):
         """The one routing of both modules; ``x``: the 12 maps, or with ``head`` the 9 encoded channels.  A plugin renderer
@@ -506,8 +517,12 @@ class _PhotoLossModule(nn.Module):
         colour columns by the exposure with one torch op and runs the forward-only kernel of the loss without exposure,
         which computes the same loss bit for bit (there is no forward-only exposure kernel: not on the hot path).  A float32
         ``[B,S,9]`` scene table that requires grad takes the scene-gradient kernel (csrc/svbrdf_photo_pose.hip): loss, map
-        gradient and d loss/d table in one launch; a table that does not takes exactly the paths above."""
-        photos = PhotoLoss._check(x, photos, channels=9 if head else 12)
+        gradient and d loss/d table in one launch; a table that does not takes exactly the paths above.
+        ``differentiable_photos`` with photos that require grad: the photo-gradient kernel
+        (csrc/svbrdf_photo_grad_photos.hip), a constant exposure folded into the table's colour columns; together with a table
+        or an exposure that requires grad, the composed definition."""
+        photos = PhotoLoss._check(x, photos, channels=9 if head else 12, differentiable=self.differentiable_photos)
+        need_p = self.differentiable_photos and photos.requires_grad and torch.is_grad_enabled()
         weights = _check_weights(weights, x, photos)
         exposure = _check_exposure(exposure, x, photos)
         B, S = photos.shape[0], photos.shape[1]
@@ -522,7 +537,16 @@ class _PhotoLossModule(nn.Module):
                 if head:
                     return self._forward_decoded(x.to(torch.float64), photos, table, weights, exposure)   # promoted in front of the decode
                 loss = composed_photo_loss(x.to(torch.float64), photos, table.to(x.device), self.eps, weights, exposure)  # float64 K1 / K2
+            elif need_p and (table.requires_grad or (exposure is not None and exposure.requires_grad)):
+                # no kernel forms the photos' gradient beside the table's or the exposure's: the composed definition,
+                # differentiable in all of them (float32 K1 / K2, or render_table for the table)
+                loss = composed_photo_loss(decode_head(x) if head else x, photos, table.to(x.device), self.eps, weights, exposure)
             else:
+                if need_p and exposure is not None:
+                    # the photo-gradient kernel takes no exposure: a constant gain multiplies the colour columns
+                    table = table.to(x.device)
+                    table = torch.cat((table[..., :6], table[..., 6:] * exposure.detach()), dim=-1)
+                    exposure = None
                 if table.requires_grad and torch.is_grad_enabled():
                     # the scene-gradient kernel takes a device table and no exposure: the gains multiply the colour columns
                     # in front of it (the exposure kernels' one float32 multiply), and autograd chains the table's
@@ -548,8 +572,8 @@ class PhotoLoss(_PhotoLossModule):
 
     -- fitting maps to captured or synthesised photos, self-supervised training on the input photos themselves.
     ``forward(input [B,12,H,W], photos [B,S,3,H,W] or [B,3,H,W] (S = 1), scenes)`` returns a 0-dim tensor, differentiable
-    w.r.t. ``input``, w.r.t. ``exposure`` and w.r.t. ``scenes`` when that is a tensor (both below); never w.r.t. the photos
-    or the weights.  ``scenes``: the light / view of every photo, a ``[B,S,9]`` float32 tensor (host or device;
+    w.r.t. ``input``, w.r.t. ``exposure`` and w.r.t. ``scenes`` when that is a tensor (both below), w.r.t. the photos when
+    constructed with ``differentiable_photos=True`` (below); never w.r.t. the weights.  ``scenes``: the light / view of every photo, a ``[B,S,9]`` float32 tensor (host or device;
     camera xyz | light xyz | light rgb) or a nested list ``scenes[b][s]`` of ``environment.Scene``-like objects.
 
     With this package's ``LocalRenderer`` and float32 maps on a ROCm device it is ONE fused HIP kernel (forward and the
@@ -585,10 +609,20 @@ class PhotoLoss(_PhotoLossModule):
     (``renderers.render_table``, which float64, ``backward(create_graph=True)`` and a table on the host side of a double
     input take).  With ``exposure=`` as well the gains multiply the colour columns in front of the kernel and get their
     gradient by the chain rule.  A colour that is NaN, infinite or <= 0 gives a NaN loss and an all-NaN table gradient.
-    Scene OBJECTS and a plugin renderer have no gradient towards light or camera positions."""
+    Scene OBJECTS and a plugin renderer have no gradient towards light or camera positions.
+
+    ``differentiable_photos=True`` (constructor; the default keeps the error for photos that require grad): photos that
+    require grad get ``d loss/d photos = -(w/N) sign(delta) / (photos + eps)`` -- what ``capture.rectify``'s gradients
+    towards its homographies and its lens take, so ``rectify(...)``, this loss and ``backward()`` are one chain.  With this
+    package's ``LocalRenderer`` and float32 tensors the loss, ``d loss/d input`` and ``d loss/d photos`` come out of ONE
+    launch (csrc/svbrdf_photo_grad_photos.hip), loss and map gradient bit for bit those without it; a detached input runs
+    the cheaper forward-only form (loss and photo gradient: a registration stage).  A constant ``exposure`` is folded into
+    the table's colour columns.  These take ``composed_photo_loss`` instead, which is differentiable in the photos
+    through ``weighted_log_l1``: float64 on any side, a plugin renderer, ``backward(create_graph=True)``, and photos that
+    require grad together with a table or an exposure that requires grad."""
 
     @staticmethod
-    def _check(input, photos, channels=12):
+    def _check(input, photos, channels=12, differentiable=False):
         if not isinstance(input, torch.Tensor) or not isinstance(photos, torch.Tensor):
             raise TypeError("input and photos must be tensors")
         if input.dim() != 4 or input.shape[1] != channels:
@@ -598,7 +632,7 @@ class PhotoLoss(_PhotoLossModule):
         if photos.dim() != 5 or photos.shape[0] != input.shape[0] or photos.shape[2] != 3 \
                 or photos.shape[3:] != input.shape[2:]:
             raise ValueError("photos must be [B,S,3,H,W] (or [B,3,H,W]) with the input's B, H and W")
-        if photos.requires_grad:
+        if photos.requires_grad and not differentiable:
             raise RuntimeError("PhotoLoss has no gradient w.r.t. the photos: pass photos.detach()")
         if photos.device != input.device:
             raise ValueError("input and photos must be on the same device")
@@ -699,8 +733,9 @@ class HeadPhotoLoss(_PhotoLossModule):
     network against photographs needs.  ``forward(encoded9 [B,9,H,W], photos [B,S,3,H,W] or [B,3,H,W] (S = 1), scenes)``
     with ``encoded9`` the generator's output after tanh (any finite value: no clamp of its own) and photos / scenes as
     ``PhotoLoss.forward`` takes them; a 0-dim tensor, differentiable w.r.t. ``encoded9``, w.r.t.
-    ``exposure`` and w.r.t. a ``[B,S,9]`` ``scenes`` tensor that requires grad, as ``PhotoLoss`` documents both; never w.r.t.
-    the photos or the weights.
+    ``exposure`` and w.r.t. a ``[B,S,9]`` ``scenes`` tensor that requires grad, as ``PhotoLoss`` documents both, w.r.t. the
+    photos with ``differentiable_photos=True`` as ``PhotoLoss`` documents it (the same ONE launch, 9 channels); never w.r.t.
+    the weights.
 
     With this package's ``LocalRenderer`` and float32 tensors on a ROCm device the head decode, the renderings, the loss
     and the gradient w.r.t. the NINE encoded channels are ONE fused HIP kernel (csrc/svbrdf_photo_loss.hip: 9 planes in,

@@ -2,7 +2,8 @@
 
     python tools/fit_photos.py [--size 256] [--batch 2] [--photos 9] [--steps 200] [--lr 0.01] [--noise] [--seed 1]
                                [--fit-exposure] [--fit-pose [--pose-lr 0.002]] [--fused-step [--steps-per-launch K]]
-                               [--captured [--sensor 640x480] [--clip 250] [--fit-registration [--corner-noise PX]]
+                               [--captured [--sensor 640x480] [--clip 250] [--fit-registration [--corner-noise PX]
+                                [--fused-registration]]
                                 [--lens K1[,K2] [--fit-lens [--lens-lr 0.01]]]]
                                [--smooth LAMBDA]
 
@@ -55,6 +56,14 @@ every ``--registration-every`` map steps it renders the current maps under the s
 of the image from looking like progress), and rectifies again.  The mean corner error is printed at every stage and both
 final map errors at the end.  Whether alternating with maps that are still wrong converges is not known in general: the
 tool records what it does.  Not with ``--steps-per-launch``.
+
+``--fused-registration`` (with ``--fit-registration``): a third fit whose registration stage takes the FUSED loss instead of
+the composition above: ``PhotoLoss(renderer, eps=Registration.EPS, normalize="weights", differentiable_photos=True)(
+maps.detach(), rect, scenes, w)`` -- loss and d loss / d rect from ONE launch of the forward-only photo-gradient kernel
+(the maps are constants of the stage: no K1, no torch ops of the definition), handed to ``capture.rectify``'s backward by
+autograd.  It is the loss the maps are fitted with; unlike the composition it has NO clamp of the rendering at 1.  Its
+corner error and map error are printed beside the composed stage's; nothing about the alternation's convergence is
+asserted.  Without the flag the tool's output is unchanged.
 
 ``--lens K1[,K2]`` (only with ``--captured``): the camera has a lens.  ``ingest`` bends every camera image with the lens
 ``capture.pinhole_lens(sensor)`` + (k1, k2) on the host before quantisation -- a float64 ``capture.undistort_points`` grid per
@@ -125,6 +134,9 @@ def main():
     ap.add_argument("--clip", type=int, default=250, help="with --captured: codes of this value or more are clipped highlights")
     ap.add_argument("--fit-registration", action="store_true",
                     help="with --captured: the patch corners are given a few pixels off and refined against renderings of the maps")
+    ap.add_argument("--fused-registration", action="store_true",
+                    help="with --fit-registration: one more fit whose registration stage takes the fused photo loss and its "
+                         "gradient towards the photographs (no clamp of the rendering at 1)")
     ap.add_argument("--corner-noise", type=float, default=2.0, metavar="PX", help="with --fit-registration: source pixels per coordinate")
     ap.add_argument("--registration-every", type=int, default=20, help="map steps between two registration stages")
     ap.add_argument("--registration-steps", type=int, default=5, help="Adam steps on the corners per stage")
@@ -153,6 +165,8 @@ def main():
                  "a launch, from a gradient summed over all pixels (a grid barrier) -- use --fused-step without it")
     if args.fit_registration and (not args.captured or args.steps_per_launch is not None):
         ap.error("--fit-registration refines the corners of --captured photographs between single map steps")
+    if args.fused_registration and not args.fit_registration:
+        ap.error("--fused-registration is a form of the registration stage: it needs --fit-registration")
     if args.lens is not None and not args.captured:
         ap.error("--lens bends the camera images of --captured")
     if args.fit_lens and (args.lens is None or not args.fit_registration):
@@ -225,6 +239,14 @@ def main():
     print("final mean |d,r,s - truth|: true corners %.5f; corners %g px off, as given %.5f (corner error %.3f px), refined %.5f "
           "(corner error %.3f px)%s" % (captured, args.corner_noise, results[0][0], results[0][1], results[1][0], results[1][1],
                                         reg.lens_text()))
+    if args.fused_registration:
+        reg = Registration(args, images, corners, corners + noise, H, lens, (ideal, beyond) if args.fit_lens else None, fused=True)
+        print("--- the same refined fit with the registration stage on the FUSED photo loss (one launch: loss and its gradient "
+              "towards the rectified photographs; eps %g, weighted mean, no clamp of the rendering at 1)" % Registration.EPS)
+        shifted, w = reg.rectify()
+        error = fit(args, dev, truth, shifted, table, hidden, w, cameras, reg)
+        print("final mean |d,r,s - truth|: refined with the composed stage %.5f (corner error %.3f px), with the fused stage %.5f "
+              "(corner error %.3f px)%s" % (results[1][0], results[1][1], error, reg.error(), reg.lens_text()))
 
 
 class Registration:
@@ -232,13 +254,18 @@ class Registration:
 
     EPS = 0.01
 
-    def __init__(self, args, images, true_corners, start_corners, H, lens=None, unknown=None):
+    def __init__(self, args, images, true_corners, start_corners, H, lens=None, unknown=None, fused=False):
         """`lens`: float64 [9] of the camera, or None.  `unknown` None: the lens is known and the corners are ideal
         coordinates.  `unknown` = (ideal, beyond), --fit-lens: the corners are the CLICKED, distorted ones, k1 starts at 0 as a
         parameter of its own Adam group, and the ideal corners follow from both at every step (`ideal_of`); `ideal` [B,S,4,2]
         are the true corners' ideal positions, which the corners marked in `beyond` (no Newton from where the polynomial
-        throws them) keep, moved by what their parameter has moved."""
+        throws them) keep, moved by what their parameter has moved.  `fused`: --fused-registration, the stage's loss is the
+        fused photo loss with its gradient towards the photographs."""
         self.args, self.images, self.H = args, images, H
+        self.fused_loss = None
+        if fused:
+            self.fused_loss = losses.PhotoLoss(renderers.LocalRenderer(), eps=self.EPS, normalize="weights",
+                                               differentiable_photos=True)
         self.lens = None if lens is None else torch.from_numpy(np.array(lens, np.float64))
         self.true = torch.from_numpy(true_corners)
         self.corners = torch.from_numpy(start_corners).clone().requires_grad_(True)
@@ -292,6 +319,16 @@ class Registration:
 
     def refine(self, maps, scenes):
         """one stage: a few Adam steps on the corners against the rendering of `maps` under `scenes` -> (photos, weights)"""
+        if self.fused_loss is not None:
+            # ONE launch per step for the loss and d loss / d rect (the forward-only photo-gradient kernel: the maps are
+            # constants here); no clamp of the rendering at 1
+            maps, scenes = maps.detach().contiguous(), scenes.detach().contiguous()
+            for _ in range(self.args.registration_steps):
+                self.opt.zero_grad(set_to_none=True)
+                rect, w = self.rectify(grad=True)
+                self.fused_loss(maps, rect, scenes, w).backward()
+                self.opt.step()
+            return self.rectify()
         with torch.no_grad():
             log_r = (_native.render_fwd(maps.detach().contiguous(), scenes.detach().contiguous()).clamp_(0.0, 1.0) + self.EPS).log()
         for _ in range(self.args.registration_steps):
