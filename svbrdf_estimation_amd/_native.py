@@ -771,39 +771,35 @@ def mix_materials(svbrdf0, svbrdf1, alpha):
     return out
 
 
-def rectify_grad_matrices(src, fmt, P, Hs, Ws, matrices, Hd, Wd, k, lut, lo, hi, grad_values):
-    """svbrdf_rectify_photos_grad_matrices, ONE launch: the gradient of ``capture.rectify``'s values towards its float32
-    ``[P,9]`` device matrices, from ``grad_values`` float32 ``[P,3,Hd,Wd]`` contiguous on the device of ``src``; the other
-    arguments as ``capture.rectify`` hands them to the forward.  The scratch is the loss entries' (one buffer per device
-    and stream, zeroed once, left zeroed by every call).  -> float32 ``[P,9]``"""
+def _rectify_grad(entry, query, src, fmt, P, Hs, Ws, matrices, lens, Hd, Wd, k, lut, lo, hi, grad_values):
+    """the one launch of a rectify gradient entry, float32 ``[P,9]`` rows out: towards the matrices, and with ``lens`` towards
+    the lens rows too.  The scratch is the loss entries' (one buffer per device and stream, zeroed once, left zeroed by every
+    call)."""
     _require_device_f32(grad_values, "grad_values")
     if tuple(grad_values.shape) != (P, 3, Hd, Wd) or not grad_values.is_contiguous() or grad_values.device != src.device:
         raise ValueError("grad_values must be contiguous [%d,3,%d,%d] on %s" % (P, Hd, Wd, src.device))
-    nbytes = _load().svbrdf_rectify_grad_workspace_bytes(P, Hd, Wd)
-    ws = _workspace(src.device, nbytes)
-    out = torch.empty((P, 9), dtype=torch.float32, device=src.device)
-    _call("svbrdf_rectify_photos_grad_matrices", src.device, src.data_ptr(), fmt, P, Hs, Ws, matrices.data_ptr(), Hd, Wd, k,
-          None if lut is None else lut.data_ptr(), lo, hi, grad_values.data_ptr(), out.data_ptr(), ws.data_ptr(),
-          ws.numel() * 8)
-    return out
+    ws = _workspace(src.device, getattr(_load(), query)(P, Hd, Wd))
+    outs = tuple(torch.empty((P, 9), dtype=torch.float32, device=src.device) for _ in range(1 if lens is None else 2))
+    _call(entry, src.device, src.data_ptr(), fmt, P, Hs, Ws, matrices.data_ptr(), *(() if lens is None else (lens.data_ptr(),)),
+          Hd, Wd, k, None if lut is None else lut.data_ptr(), lo, hi, grad_values.data_ptr(), *(o.data_ptr() for o in outs),
+          ws.data_ptr(), ws.numel() * 8)
+    return outs
+
+
+def rectify_grad_matrices(src, fmt, P, Hs, Ws, matrices, Hd, Wd, k, lut, lo, hi, grad_values):
+    """svbrdf_rectify_photos_grad_matrices, ONE launch: the gradient of ``capture.rectify``'s values towards its float32
+    ``[P,9]`` device matrices, from ``grad_values`` float32 ``[P,3,Hd,Wd]`` contiguous on the device of ``src``; the other
+    arguments as ``capture.rectify`` hands them to the forward.  -> float32 ``[P,9]``"""
+    return _rectify_grad("svbrdf_rectify_photos_grad_matrices", "svbrdf_rectify_grad_workspace_bytes", src, fmt, P, Hs, Ws,
+                         matrices, None, Hd, Wd, k, lut, lo, hi, grad_values)[0]
 
 
 def rectify_lens_grad(src, fmt, P, Hs, Ws, matrices, lens, Hd, Wd, k, lut, lo, hi, grad_values):
     """svbrdf_rectify_photos_lens_grad, ONE launch: the gradient of ``capture.rectify(..., lens=)``'s values towards its
     float32 ``[P,9]`` device matrices (through the lens's Jacobian) and towards its float32 ``[P,9]`` device lens rows, from
-    ``grad_values`` float32 ``[P,3,Hd,Wd]`` contiguous on the device of ``src``.  The scratch is ``rectify_grad_matrices``'
-    (one buffer per device and stream, zeroed once, left zeroed by every call).  -> (float32 ``[P,9]``, float32 ``[P,9]``)"""
-    _require_device_f32(grad_values, "grad_values")
-    if tuple(grad_values.shape) != (P, 3, Hd, Wd) or not grad_values.is_contiguous() or grad_values.device != src.device:
-        raise ValueError("grad_values must be contiguous [%d,3,%d,%d] on %s" % (P, Hd, Wd, src.device))
-    nbytes = _load().svbrdf_rectify_lens_grad_workspace_bytes(P, Hd, Wd)
-    ws = _workspace(src.device, nbytes)
-    gm = torch.empty((P, 9), dtype=torch.float32, device=src.device)
-    gl = torch.empty((P, 9), dtype=torch.float32, device=src.device)
-    _call("svbrdf_rectify_photos_lens_grad", src.device, src.data_ptr(), fmt, P, Hs, Ws, matrices.data_ptr(), lens.data_ptr(),
-          Hd, Wd, k, None if lut is None else lut.data_ptr(), lo, hi, grad_values.data_ptr(), gm.data_ptr(), gl.data_ptr(),
-          ws.data_ptr(), ws.numel() * 8)
-    return gm, gl
+    ``grad_values`` as above.  -> (float32 ``[P,9]``, float32 ``[P,9]``)"""
+    return _rectify_grad("svbrdf_rectify_photos_lens_grad", "svbrdf_rectify_lens_grad_workspace_bytes", src, fmt, P, Hs, Ws,
+                         matrices, lens, Hd, Wd, k, lut, lo, hi, grad_values)
 
 
 def clock_probe(out, ticks=300000, stream=None):

@@ -287,34 +287,38 @@ def undistort_points(points, lens):
 
 # ------------------------------------------------------------------------------------------------ the launch
 
+def _as_tensor(t):
+    return t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t)))
+
+
+def _device_rows(rows, lead, device, shape_error, lead_error):
+    """``rows`` (tensor, [...,9] with the photos' leading dimensions, or one [9] for all) -> contiguous float32 [P,9] on
+    ``device``; the two messages are the caller's"""
+    P = int(np.prod(lead)) if lead else 1
+    if rows.shape[-1:] != (9,):
+        raise ValueError(shape_error % (tuple(rows.shape),))
+    if rows.dim() == 1:
+        rows = rows.expand(P, 9)
+    elif tuple(rows.shape[:-1]) != tuple(lead):
+        raise ValueError(lead_error % (tuple(rows.shape), tuple(lead)))
+    return rows.reshape(P, 9).to(device=device, dtype=torch.float32).contiguous()
+
+
 def _device_matrices(matrices, lead, device):
     """``matrices`` (tensor or array, [...,3,3] or [...,9] with the photos' leading dimensions, or one [3,3] for all) ->
     contiguous float32 [P,9] on ``device``"""
-    P = int(np.prod(lead)) if lead else 1
-    m = matrices if isinstance(matrices, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(matrices)))
+    m = _as_tensor(matrices)
     if m.shape[-2:] == (3, 3):
         m = m.reshape(m.shape[:-2] + (9,))
-    if m.shape[-1:] != (9,):
-        raise ValueError("matrices must be [...,3,3] or [...,9], got %s" % (tuple(m.shape),))
-    if m.dim() == 1:
-        m = m.expand(P, 9)
-    elif tuple(m.shape[:-1]) != tuple(lead):
-        raise ValueError("matrices %s do not match the photos' leading dimensions %s" % (tuple(m.shape), tuple(lead)))
-    return m.reshape(P, 9).to(device=device, dtype=torch.float32).contiguous()
+    return _device_rows(m, lead, device, "matrices must be [...,3,3] or [...,9], got %s",
+                        "matrices %s do not match the photos' leading dimensions %s")
 
 
 def _device_lens(lens, lead, device):
     """``lens`` (tensor or array, [...,9] with the photos' leading dimensions, or one [9] for all) -> contiguous float32 [P,9]
     on ``device``"""
-    P = int(np.prod(lead)) if lead else 1
-    t = lens if isinstance(lens, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(lens)))
-    if t.shape[-1:] != (9,):
-        raise ValueError("lens must be [...,9] (fx, fy, cx, cy, k1, k2, p1, p2, k3), got %s" % (tuple(t.shape),))
-    if t.dim() == 1:
-        t = t.expand(P, 9)
-    elif tuple(t.shape[:-1]) != tuple(lead):
-        raise ValueError("lens %s does not match the photos' leading dimensions %s" % (tuple(t.shape), tuple(lead)))
-    return t.reshape(P, 9).to(device=device, dtype=torch.float32).contiguous()
+    return _device_rows(_as_tensor(lens), lead, device, "lens must be [...,9] (fx, fy, cx, cy, k1, k2, p1, p2, k3), got %s",
+                        "lens %s does not match the photos' leading dimensions %s")
 
 
 def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights=True, lens=None):
@@ -379,87 +383,43 @@ def rectify(photos, matrices, size, lut=None, clip=None, samples=1, want_weights
         raise ValueError("photos must not be empty, got %s" % (tuple(photos.shape),))
     src = photos.contiguous()
     args = (fmt, P, int(Hs), int(Ws), Hd, Wd, int(samples), lo, hi)
-    if lens is not None:
-        wants = [isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled() for t in (matrices, lens)]
-        if any(wants):
-            as_tensor = [t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(t)))
-                         for t in (matrices, lens)]
-            return _RectifyLens.apply(as_tensor[0], as_tensor[1], src, lut, args, lead, want_weights)
-        return _launch_rectify_lens(src, _device_matrices(matrices, lead, photos.device),
-                                    _device_lens(lens, lead, photos.device), lut, args, lead, want_weights)
-    if isinstance(matrices, torch.Tensor) and matrices.requires_grad and torch.is_grad_enabled():
-        return _RectifyMatrices.apply(matrices, src, lut, args, lead, want_weights)
-    return _launch_rectify(src, _device_matrices(matrices, lead, photos.device), lut, args, lead, want_weights)
+    if any(isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled() for t in (matrices, lens)):
+        return _Rectify.apply(_as_tensor(matrices), None if lens is None else _as_tensor(lens), src, lut, args, lead,
+                              want_weights)
+    return _launch_rectify(src, _device_matrices(matrices, lead, photos.device), lut, args, lead, want_weights,
+                           None if lens is None else _device_lens(lens, lead, photos.device))
 
 
-def _launch_rectify(src, mats, lut, args, lead, want_weights):
-    """the forward's one launch on checked arguments -> (values, weights or None)"""
+def _launch_rectify(src, mats, lut, args, lead, want_weights, lens=None):
+    """the forward's one launch on checked arguments -> (values, weights or None): svbrdf_rectify_photos, or with the
+    ``lens`` rows svbrdf_rectify_photos_lens"""
     fmt, P, Hs, Ws, Hd, Wd, k, lo, hi = args
     out = torch.empty(lead + (3, Hd, Wd), dtype=torch.float32, device=src.device)
     weights = torch.empty(lead + (Hd, Wd), dtype=torch.float32, device=src.device) if want_weights else None
-    _native._call("svbrdf_rectify_photos", src.device, src.data_ptr(), fmt, P, Hs, Ws, mats.data_ptr(), Hd, Wd, k,
+    name, rows = ("svbrdf_rectify_photos", ()) if lens is None else ("svbrdf_rectify_photos_lens", (lens.data_ptr(),))
+    _native._call(name, src.device, src.data_ptr(), fmt, P, Hs, Ws, mats.data_ptr(), *rows, Hd, Wd, k,
                   None if lut is None else lut.data_ptr(), lo, hi, out.data_ptr(),
                   None if weights is None else weights.data_ptr())
     return out, weights
 
 
-class _RectifyMatrices(torch.autograd.Function):
-    """``rectify`` for matrices that require grad.  forward: the same launch.  backward: ONE launch of
-    svbrdf_rectify_photos_grad_matrices on ``grad_output.contiguous()`` with the forward's saved arguments; the gradient
-    comes back in the shape, dtype and device of ``matrices`` (one matrix for all: the sum over the photos, added in
-    float64).  Nothing towards the photos; the weights are non-differentiable; no double backward."""
-
-    @staticmethod
-    def forward(ctx, matrices, src, lut, args, lead, want_weights):
-        mats = _device_matrices(matrices.detach(), lead, src.device)
-        out, weights = _launch_rectify(src, mats, lut, args, lead, want_weights)
-        ctx.save_for_backward(src, mats, lut)
-        ctx.args, ctx.like = args, (matrices.shape, matrices.device, matrices.dtype)
-        ctx.shared = matrices.dim() == (2 if matrices.shape[-2:] == (3, 3) else 1)
-        if weights is not None:
-            ctx.mark_non_differentiable(weights)
-        return out, weights
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_out, _grad_weights=None):
-        src, mats, lut = ctx.saved_tensors
-        fmt, P, Hs, Ws, Hd, Wd, k, lo, hi = ctx.args
-        g = grad_out.to(torch.float32).contiguous().reshape(P, 3, Hd, Wd)
-        gm = _native.rectify_grad_matrices(src, fmt, P, Hs, Ws, mats, Hd, Wd, k, lut, lo, hi, g)
-        shape, device, dtype = ctx.like
-        if ctx.shared:
-            gm = gm.to(torch.float64).sum(dim=0)
-        return gm.reshape(shape).to(device=device, dtype=dtype), None, None, None, None, None
-
-
-def _launch_rectify_lens(src, mats, lens, lut, args, lead, want_weights):
-    """the lens forward's one launch on checked arguments -> (values, weights or None)"""
-    fmt, P, Hs, Ws, Hd, Wd, k, lo, hi = args
-    out = torch.empty(lead + (3, Hd, Wd), dtype=torch.float32, device=src.device)
-    weights = torch.empty(lead + (Hd, Wd), dtype=torch.float32, device=src.device) if want_weights else None
-    _native._call("svbrdf_rectify_photos_lens", src.device, src.data_ptr(), fmt, P, Hs, Ws, mats.data_ptr(), lens.data_ptr(),
-                  Hd, Wd, k, None if lut is None else lut.data_ptr(), lo, hi, out.data_ptr(),
-                  None if weights is None else weights.data_ptr())
-    return out, weights
-
-
-class _RectifyLens(torch.autograd.Function):
-    """``rectify(..., lens=)`` for matrices and/or a lens that require grad.  forward: the same launch.  backward: ONE launch
-    of svbrdf_rectify_photos_lens_grad on ``grad_output.contiguous()`` with the forward's saved arguments; each gradient
-    comes back in the shape, dtype and device of its input (one matrix or one lens for all: the sum over the photos, added
-    in float64), None for an input that did not ask.  Nothing towards the photos; the weights are non-differentiable; no
+class _Rectify(torch.autograd.Function):
+    """``rectify`` for matrices and/or a lens that require grad (``lens`` may be None: the pinhole entries).  forward: the
+    same launch.  backward: ONE launch of svbrdf_rectify_photos_grad_matrices, or with a lens of
+    svbrdf_rectify_photos_lens_grad, on ``grad_output.contiguous()`` with the forward's saved arguments; each gradient comes
+    back in the shape, dtype and device of its input (one matrix or one lens for all: the sum over the photos, added in
+    float64), None for an input that did not ask.  Nothing towards the photos; the weights are non-differentiable; no
     double backward."""
 
     @staticmethod
     def forward(ctx, matrices, lens, src, lut, args, lead, want_weights):
         mats = _device_matrices(matrices.detach(), lead, src.device)
-        rows = _device_lens(lens.detach(), lead, src.device)
-        out, weights = _launch_rectify_lens(src, mats, rows, lut, args, lead, want_weights)
+        rows = None if lens is None else _device_lens(lens.detach(), lead, src.device)
+        out, weights = _launch_rectify(src, mats, lut, args, lead, want_weights, rows)
         ctx.save_for_backward(src, mats, rows, lut)
         ctx.args = args
-        ctx.like = tuple((t.shape, t.device, t.dtype) for t in (matrices, lens))
-        ctx.shared = (matrices.dim() == (2 if matrices.shape[-2:] == (3, 3) else 1), lens.dim() == 1)
+        ctx.like = tuple(None if t is None else (t.shape, t.device, t.dtype) for t in (matrices, lens))
+        ctx.shared = (matrices.dim() == (2 if matrices.shape[-2:] == (3, 3) else 1), lens is not None and lens.dim() == 1)
         if weights is not None:
             ctx.mark_non_differentiable(weights)
         return out, weights
@@ -470,12 +430,16 @@ class _RectifyLens(torch.autograd.Function):
         src, mats, rows, lut = ctx.saved_tensors
         fmt, P, Hs, Ws, Hd, Wd, k, lo, hi = ctx.args
         g = grad_out.to(torch.float32).contiguous().reshape(P, 3, Hd, Wd)
-        grads = _native.rectify_lens_grad(src, fmt, P, Hs, Ws, mats, rows, Hd, Wd, k, lut, lo, hi, g)
+        if rows is None:
+            grads = (_native.rectify_grad_matrices(src, fmt, P, Hs, Ws, mats, Hd, Wd, k, lut, lo, hi, g), None)
+        else:
+            grads = _native.rectify_lens_grad(src, fmt, P, Hs, Ws, mats, rows, Hd, Wd, k, lut, lo, hi, g)
         back = []
-        for n, (grad, (shape, device, dtype), shared) in enumerate(zip(grads, ctx.like, ctx.shared)):
-            if not ctx.needs_input_grad[n]:
+        for grad, like, shared, asked in zip(grads, ctx.like, ctx.shared, ctx.needs_input_grad):
+            if not asked:
                 back.append(None)
                 continue
+            shape, device, dtype = like
             if shared:
                 grad = grad.to(torch.float64).sum(dim=0)
             back.append(grad.reshape(shape).to(device=device, dtype=dtype))

@@ -38,96 +38,39 @@
 // per workgroup (1 KiB).  Neighbouring destination pixels hit neighbouring source texels, so the gather leans on L2: the
 // source is not tiled through LDS.  No atomics, no scratch, no second pass.  It includes svbrdf_host.h for the
 // host-side helpers (fail, aligned, launch_status).
-// The tap rule, the launch shape and the argument checks are in svbrdf_capture_device.h, shared with svbrdf_capture_grad.hip
-// (the gradient towards the matrices).
+//
+// Where each statement lives.  svbrdf_capture_device.h holds every statement above once, as functions that k_rectify and
+// k_lens_grad call: xs, ys (rectify_sub); X .. v (rectify_point); valid (rectify_pinhole_cell); the clamp, x0 .. y1 and the
+// fractions (rectify_cell); the taps and the tap rule (rectify_taps, rectify_tap, rectify_index); top, bot, val and the sum
+// (rectify_accumulate); the 1/K^2 and the four stores (rectify_store); the tile set-up, the launch shape, the dispatch and
+// the argument checks.  k_rectify below is the sub-sample loop around them.
 #include "svbrdf_host.h"
 #include "svbrdf_capture_device.h"
 
 namespace {
 
 template <bool U8, int K>
-__global__ __launch_bounds__(kRectifyTileW * kRectifyTileH) void k_rectify(
+__global__ __launch_bounds__(kRectifyBlock) void k_rectify(
     const void *__restrict__ src, const float *__restrict__ matrices, const float *__restrict__ lut, RectifyClip clip,
     float *__restrict__ out, float *__restrict__ weights_out, int Hs, int Ws, int Hd, int Wd)
 {
     __shared__ float s_lut[U8 ? 256 : 1];
-    if (U8) {
-        s_lut[threadIdx.x] = lut[threadIdx.x];      // 256 threads, 256 entries
-        __syncthreads();
-    }
-    const int p = blockIdx.z;
-    const int x = blockIdx.x * kRectifyTileW + (threadIdx.x & (kRectifyTileW - 1));
-    const int y = blockIdx.y * kRectifyTileH + (threadIdx.x / kRectifyTileW);
-    if (x >= Wd || y >= Hd) return;                 // (behind the barrier)
-    const float *m = matrices + (size_t)p * 9;
-    const float m0 = m[0], m1 = m[1], m2 = m[2], m3 = m[3], m4 = m[4], m5 = m[5], m6 = m[6], m7 = m[7], m8 = m[8];
-    const float wmax = (float)(Ws - 1), hmax = (float)(Hs - 1);
-    const size_t plane = (size_t)Hs * Ws;
-    const size_t base = (size_t)p * 3 * plane;      // first element of photo p in either layout
+    const RectifyTile t = rectify_tile<U8>(lut, s_lut, Hd, Wd);
+    if (!t.live) return;                            // (behind the barrier)
+    float m[9];
+    rectify_matrix_row(matrices, t.p, m);
+    const RectifySource s = rectify_source(src, s_lut, clip, t.p, Hs, Ws);
     float acc[3] = {0.0f, 0.0f, 0.0f};
     bool ok = true;
 #pragma unroll
     for (int j = 0; j < K; ++j) {
 #pragma unroll
         for (int i = 0; i < K; ++i) {
-            const float xs = (float)x + ((i + 0.5f) / K - 0.5f);        // the offset is a compile-time constant, exact
-            const float ys = (float)y + ((j + 0.5f) / K - 0.5f);
-            const float X = (m0 * xs + m1 * ys) + m2;
-            const float Y = (m3 * xs + m4 * ys) + m5;
-            const float Z = (m6 * xs + m7 * ys) + m8;
-            float u = X / Z, v = Y / Z;
-            const bool valid = Z > 0.0f && u >= 0.0f && u <= wmax && v >= 0.0f && v <= hmax;
-            ok = ok && valid;
-            u = valid ? u : 0.0f;
-            v = valid ? v : 0.0f;
-            u = fminf(fmaxf(u, 0.0f), wmax);        // in float, before the conversion: NaN and +-inf cannot reach it
-            v = fminf(fmaxf(v, 0.0f), hmax);
-            const float x0f = floorf(u), y0f = floorf(v);
-            const float fx = u - x0f, fy = v - y0f;
-            const int x0 = (int)x0f, y0 = (int)y0f;
-            const int x1 = min(x0 + 1, Ws - 1), y1 = min(y0 + 1, Hs - 1);
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) {
-                size_t ia, ib, ic, id;
-                if (U8) {       // [P,Hs,Ws,3]
-                    ia = base + ((size_t)y0 * Ws + x0) * 3 + ch;
-                    ib = base + ((size_t)y0 * Ws + x1) * 3 + ch;
-                    ic = base + ((size_t)y1 * Ws + x0) * 3 + ch;
-                    id = base + ((size_t)y1 * Ws + x1) * 3 + ch;
-                } else {        // [P,3,Hs,Ws]
-                    const size_t cb = base + ch * plane;
-                    ia = cb + (size_t)y0 * Ws + x0;
-                    ib = cb + (size_t)y0 * Ws + x1;
-                    ic = cb + (size_t)y1 * Ws + x0;
-                    id = cb + (size_t)y1 * Ws + x1;
-                }
-                const float a = rectify_tap<U8>(src, ia, s_lut, clip, ok);
-                const float b = rectify_tap<U8>(src, ib, s_lut, clip, ok);
-                const float c = rectify_tap<U8>(src, ic, s_lut, clip, ok);
-                const float d = rectify_tap<U8>(src, id, s_lut, clip, ok);
-                const float top = a + fx * (b - a);
-                const float bot = c + fx * (d - c);
-                const float val = top + fy * (bot - top);
-                acc[ch] = (i == 0 && j == 0) ? val : acc[ch] + val;
-            }
+            const RectifyPoint q = rectify_point(m, rectify_sub<K>(t.x, i), rectify_sub<K>(t.y, j));
+            rectify_accumulate<U8>(s, rectify_pinhole_cell(q, Hs, Ws), i == 0 && j == 0, ok, acc);
         }
     }
-    const size_t dplane = (size_t)Hd * Wd;
-    const size_t pix = (size_t)y * Wd + x;
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch)
-        out[((size_t)p * 3 + ch) * dplane + pix] = ok ? acc[ch] * (1.0f / (K * K)) : 0.0f;
-    if (weights_out) weights_out[(size_t)p * dplane + pix] = ok ? 1.0f : 0.0f;
-}
-
-template <bool U8>
-void launch_rectify(int k, dim3 grid, hipStream_t st, const void *src, const float *matrices, const float *lut,
-                    RectifyClip clip, float *out, float *weights_out, int Hs, int Ws, int Hd, int Wd)
-{
-    const dim3 block(kRectifyTileW * kRectifyTileH);
-    if (k == 1) k_rectify<U8, 1><<<grid, block, 0, st>>>(src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
-    else if (k == 2) k_rectify<U8, 2><<<grid, block, 0, st>>>(src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
-    else k_rectify<U8, 4><<<grid, block, 0, st>>>(src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+    rectify_store<K>(t, ok, acc, out, weights_out, Hd, Wd);
 }
 
 }  // namespace
@@ -142,12 +85,13 @@ int svbrdf_rectify_photos(const void *src, int src_format, int P, int Hs, int Ws
     const int rc = rectify_check(who, "out", src, src_format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi, out,
                                  weights_out);
     if (rc) return rc;
-    const bool u8 = src_format == SVBRDF_RECTIFY_U8_INTERLEAVED;
     const RectifyClip clip = rectify_clip(clip_lo, clip_hi);
     const dim3 grid = rectify_grid(P, Hd, Wd);
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (u8) launch_rectify<true>(k, grid, st, src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
-    else launch_rectify<false>(k, grid, st, src, matrices, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+    rectify_dispatch(src_format, k, [&](auto u8, auto kk) {
+        k_rectify<decltype(u8)::value, decltype(kk)::value><<<grid, kRectifyBlock, 0, st>>>(src, matrices, lut, clip, out,
+                                                                                            weights_out, Hs, Ws, Hd, Wd);
+    });
     return launch_status(who);
 }
 

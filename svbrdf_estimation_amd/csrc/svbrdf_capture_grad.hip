@@ -31,30 +31,49 @@
 //      zeroed once by the caller and left zeroed by every completed call.
 // SVBRDF_RECTIFY_GRAD_DEPTH = 24 (include/svbrdf_hip.h) bounds the float32 additions any single term passes through: K^2 - 1 <= 15, 6 and 2 make 23.
 // No float32 sum crosses a workgroup.  Which workgroup finishes depends on timing; what it computes does not.
+// svbrdf_capture_grad_device.h holds du .. gv and steps 2 to 5 as functions (rectify_grad_taps, rectify_grad_reduce<N>), which
+// k_lens_grad calls, and the host side of both gradient entries: the workspace's size and split and the second-stage checks.
 #include "svbrdf_host.h"
 #include "svbrdf_capture_device.h"
+#include "svbrdf_capture_grad_device.h"
 
 namespace {
 
-static_assert(4 * 4 - 1 + 6 + 2 <= SVBRDF_RECTIFY_GRAD_DEPTH, "float32 additions a term passes through: thread, wave, waves");
-constexpr int kRectifyGradTicketBytes = 256;        // the counters' block is padded to a multiple of this
+// k_homography_grad keeps the body it had before the capture units were put on shared device functions, with its own cell and
+// reduction: on the shared ones its uint8 k = 1 launch was 0.28 us above the criterion of profiles/r27_capture_refactor.txt.
+// A change to rectify_cell or rectify_grad_reduce (the shared headers) has to be made here as well.
+//
+// One sub-sample at (xs, ys) through m0..m8: the forward's statements from X to the tap cell, one rounded float32 operation
+// each, in its order.  u and v are the quotients as they are; the cell and the fractions come from their clamped copies, so
+// every index lies in the source whatever the matrix holds.
+struct HomographyCell {
+    float Z, u, v, fx, fy;
+    int x0, y0, x1, y1;
+    bool valid;
+};
 
-inline size_t rectify_grad_ticket_bytes(int P)
+__device__ __forceinline__ HomographyCell homography_cell(const float m[9], float xs, float ys, int Hs, int Ws)
 {
-    return ((size_t)P * sizeof(unsigned) + kRectifyGradTicketBytes - 1) / kRectifyGradTicketBytes * kRectifyGradTicketBytes;
-}
-
-inline size_t rectify_grad_tiles(int Hd, int Wd)
-{
-    return (size_t)((Wd + kRectifyTileW - 1) / kRectifyTileW) * (size_t)((Hd + kRectifyTileH - 1) / kRectifyTileH);
-}
-
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask)
-{
-    const unsigned long long bits = __builtin_bit_cast(unsigned long long, v);
-    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)bits, mask, 64);
-    const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(bits >> 32), mask, 64);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+    const float wmax = (float)(Ws - 1), hmax = (float)(Hs - 1);
+    HomographyCell g;
+    const float X = (m[0] * xs + m[1] * ys) + m[2];
+    const float Y = (m[3] * xs + m[4] * ys) + m[5];
+    g.Z = (m[6] * xs + m[7] * ys) + m[8];
+    g.u = X / g.Z;
+    g.v = Y / g.Z;
+    g.valid = g.Z > 0.0f && g.u >= 0.0f && g.u <= wmax && g.v >= 0.0f && g.v <= hmax;
+    float u = g.valid ? g.u : 0.0f;
+    float v = g.valid ? g.v : 0.0f;
+    u = fminf(fmaxf(u, 0.0f), wmax);        // in float, before the conversion: NaN and +-inf cannot reach it
+    v = fminf(fmaxf(v, 0.0f), hmax);
+    const float x0f = floorf(u), y0f = floorf(v);
+    g.fx = u - x0f;
+    g.fy = v - y0f;
+    g.x0 = (int)x0f;
+    g.y0 = (int)y0f;
+    g.x1 = min(g.x0 + 1, Ws - 1);
+    g.y1 = min(g.y0 + 1, Hs - 1);
+    return g;
 }
 
 template <bool U8, int K>
@@ -94,7 +113,7 @@ __global__ __launch_bounds__(kRectifyTileW * kRectifyTileH) void k_homography_gr
         for (int i = 0; i < K; ++i) {
             const float xs = (float)x + ((i + 0.5f) / K - 0.5f);        // the offset is a compile-time constant, exact
             const float ys = (float)y + ((j + 0.5f) / K - 0.5f);
-            const RectifyCell c = rectify_cell(m, xs, ys, Hs, Ws);
+            const HomographyCell c = homography_cell(m, xs, ys, Hs, Ws);
             ok = ok && c.valid;
             float du[3], dv[3];
 #pragma unroll
@@ -175,32 +194,11 @@ __global__ __launch_bounds__(kRectifyTileW * kRectifyTileH) void k_homography_gr
     }
 }
 
-template <bool U8>
-void launch_rectify_grad(int k, dim3 grid, hipStream_t st, const void *src, const float *matrices, const float *lut,
-                         RectifyClip clip, const float *grad_values, float *grad_matrices, unsigned *tickets,
-                         float *partials, int Hs, int Ws, int Hd, int Wd)
-{
-    const dim3 block(kRectifyTileW * kRectifyTileH);
-    if (k == 1)
-        k_homography_grad<U8, 1><<<grid, block, 0, st>>>(src, matrices, lut, clip, grad_values, grad_matrices, tickets, partials,
-                                                      Hs, Ws, Hd, Wd);
-    else if (k == 2)
-        k_homography_grad<U8, 2><<<grid, block, 0, st>>>(src, matrices, lut, clip, grad_values, grad_matrices, tickets, partials,
-                                                      Hs, Ws, Hd, Wd);
-    else
-        k_homography_grad<U8, 4><<<grid, block, 0, st>>>(src, matrices, lut, clip, grad_values, grad_matrices, tickets, partials,
-                                                      Hs, Ws, Hd, Wd);
-}
-
 }  // namespace
 
 extern "C" {
 
-size_t svbrdf_rectify_grad_workspace_bytes(int P, int Hd, int Wd)
-{
-    if (P < 1 || Hd < 1 || Wd < 1 || P > 65535 || Hd > kRectifyMaxDim || Wd > kRectifyMaxDim) return 0;
-    return rectify_grad_ticket_bytes(P) + (size_t)P * rectify_grad_tiles(Hd, Wd) * 9 * sizeof(float);
-}
+size_t svbrdf_rectify_grad_workspace_bytes(int P, int Hd, int Wd) { return rectify_grad_workspace_bytes(P, Hd, Wd, 9); }
 
 int svbrdf_rectify_photos_grad_matrices(const void *src, int src_format, int P, int Hs, int Ws, const float *matrices,
                                         int Hd, int Wd, int k, const float *lut, float clip_lo, float clip_hi,
@@ -208,30 +206,21 @@ int svbrdf_rectify_photos_grad_matrices(const void *src, int src_format, int P, 
                                         size_t workspace_bytes, void *stream)
 {
     const char *who = "svbrdf_rectify_photos_grad_matrices";
-    const int rc = rectify_check(who, "grad_matrices", src, src_format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi,
-                                 grad_matrices, grad_values);
+    int rc = rectify_check(who, "grad_matrices", src, src_format, P, Hs, Ws, matrices, Hd, Wd, k, lut, clip_lo, clip_hi,
+                           grad_matrices, grad_values);
     if (rc) return rc;
-    char text[200];
-    const auto bad = [&](int code, const char *what) {
-        std::snprintf(text, sizeof(text), "%s: %s", who, what);
-        return fail(code, text);
-    };
-    if (!grad_values || !workspace) return bad(SVBRDF_ERR_NULL, "grad_values and workspace are required");
-    if (!aligned(workspace, 8)) return bad(SVBRDF_ERR_ALIGN, "workspace must be 8-byte aligned");
-    if (workspace_bytes < svbrdf_rectify_grad_workspace_bytes(P, Hd, Wd))
-        return bad(SVBRDF_ERR_WORKSPACE, "workspace is smaller than svbrdf_rectify_grad_workspace_bytes(P, Hd, Wd)");
-    const bool u8 = src_format == SVBRDF_RECTIFY_U8_INTERLEAVED;
+    rc = rectify_grad_check(who, "svbrdf_rectify_grad_workspace_bytes", false, P, Hd, Wd, 9, grad_values, nullptr, workspace,
+                            workspace_bytes);
+    if (rc) return rc;
     const RectifyClip clip = rectify_clip(clip_lo, clip_hi);
     const dim3 grid = rectify_grid(P, Hd, Wd);
-    unsigned *tickets = static_cast<unsigned *>(workspace);
-    float *partials = reinterpret_cast<float *>(static_cast<char *>(workspace) + rectify_grad_ticket_bytes(P));
+    unsigned *tickets = rectify_grad_tickets(workspace);
+    float *partials = rectify_grad_partials(workspace, P);
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (u8)
-        launch_rectify_grad<true>(k, grid, st, src, matrices, lut, clip, grad_values, grad_matrices, tickets, partials, Hs, Ws,
-                                  Hd, Wd);
-    else
-        launch_rectify_grad<false>(k, grid, st, src, matrices, lut, clip, grad_values, grad_matrices, tickets, partials, Hs,
-                                   Ws, Hd, Wd);
+    rectify_dispatch(src_format, k, [&](auto u8, auto kk) {
+        k_homography_grad<decltype(u8)::value, decltype(kk)::value><<<grid, kRectifyBlock, 0, st>>>(
+            src, matrices, lut, clip, grad_values, grad_matrices, tickets, partials, Hs, Ws, Hd, Wd);
+    });
     return launch_status(who);
 }
 

@@ -28,6 +28,64 @@
 
 namespace {
 
+// k_lens_rectify keeps the body it had before the capture units were put on shared device functions, with its own cell: on
+// the shared ones its uint8 k = 1 launch was 0.32 us above the criterion of profiles/r27_capture_refactor.txt.  A change to
+// rectify_point, rectify_lens_map or rectify_cell (the shared headers) has to be made here as well.
+//
+// One sub-sample at (xs, ys) through m0..m8 and the lens: the forward's statements from X to the quotients, the lens map, and
+// the tap cell at (ud, vd); one rounded float32 operation each.  Z, u, v are the pinhole quantities as they are; xn .. vd the
+// lens map's; the cell and the fractions come from the clamped copies of ud, vd, so every index lies in the source whatever
+// the matrix and the lens hold.
+struct RectifyLensCell {
+    float Z, u, v;
+    float xn, yn, xx, yy, r2, rad, t, xd, yd, ud, vd;
+    float fx, fy;                   // the bilinear fractions
+    int x0, y0, x1, y1;
+    bool valid;
+};
+
+__device__ __forceinline__ RectifyLensCell rectify_lens_cell(const float m[9], const RectifyLens &L, float xs, float ys, int Hs,
+                                                             int Ws)
+{
+    const float wmax = (float)(Ws - 1), hmax = (float)(Hs - 1);
+    RectifyLensCell g;
+    const float X = (m[0] * xs + m[1] * ys) + m[2];
+    const float Y = (m[3] * xs + m[4] * ys) + m[5];
+    g.Z = (m[6] * xs + m[7] * ys) + m[8];
+    g.u = X / g.Z;
+    g.v = Y / g.Z;
+    g.xn = (g.u - L.cx) / L.fx;
+    g.yn = (g.v - L.cy) / L.fy;
+    g.xx = g.xn * g.xn;
+    g.yy = g.yn * g.yn;
+    const float xy = g.xn * g.yn;
+    g.r2 = g.xx + g.yy;
+    g.rad = 1.0f + g.r2 * (L.k1 + g.r2 * (L.k2 + g.r2 * L.k3));
+    const float mono = 1.0f + g.r2 * (L.k1_3 + g.r2 * (L.k2_5 + g.r2 * L.k3_7));
+    g.t = 2.0f * xy;
+    const float tx = (L.p1 * g.t) + (L.p2 * (g.r2 + 2.0f * g.xx));
+    const float ty = (L.p1 * (g.r2 + 2.0f * g.yy)) + (L.p2 * g.t);
+    g.xd = (g.xn * g.rad) + tx;
+    g.yd = (g.yn * g.rad) + ty;
+    g.ud = (g.xd * L.fx) + L.cx;
+    g.vd = (g.yd * L.fy) + L.cy;
+    // (`&`, not `&&`: a wave-uniform operand of `&&` becomes a branch per sub-sample, and behind it the taps of all K^2
+    // sub-samples are held in registers to the kernel's end)
+    g.valid = L.focal & (g.Z > 0.0f) & (mono > 0.0f) & (g.ud >= 0.0f) & (g.ud <= wmax) & (g.vd >= 0.0f) & (g.vd <= hmax);
+    float u = g.valid ? g.ud : 0.0f;
+    float v = g.valid ? g.vd : 0.0f;
+    u = fminf(fmaxf(u, 0.0f), wmax);        // in float, before the conversion: NaN and +-inf cannot reach it
+    v = fminf(fmaxf(v, 0.0f), hmax);
+    const float x0f = floorf(u), y0f = floorf(v);
+    g.fx = u - x0f;
+    g.fy = v - y0f;
+    g.x0 = (int)x0f;
+    g.y0 = (int)y0f;
+    g.x1 = min(g.x0 + 1, Ws - 1);
+    g.y1 = min(g.y0 + 1, Hs - 1);
+    return g;
+}
+
 template <bool U8, int K>
 __global__ __launch_bounds__(kRectifyTileW * kRectifyTileH) void k_lens_rectify(
     const void *__restrict__ src, const float *__restrict__ matrices, const float *__restrict__ lens,
@@ -80,19 +138,6 @@ __global__ __launch_bounds__(kRectifyTileW * kRectifyTileH) void k_lens_rectify(
     if (weights_out) weights_out[(size_t)p * dplane + pix] = ok ? 1.0f : 0.0f;
 }
 
-template <bool U8>
-void launch_rectify_lens(int k, dim3 grid, hipStream_t st, const void *src, const float *matrices, const float *lens,
-                         const float *lut, RectifyClip clip, float *out, float *weights_out, int Hs, int Ws, int Hd, int Wd)
-{
-    const dim3 block(kRectifyTileW * kRectifyTileH);
-    if (k == 1)
-        k_lens_rectify<U8, 1><<<grid, block, 0, st>>>(src, matrices, lens, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
-    else if (k == 2)
-        k_lens_rectify<U8, 2><<<grid, block, 0, st>>>(src, matrices, lens, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
-    else
-        k_lens_rectify<U8, 4><<<grid, block, 0, st>>>(src, matrices, lens, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
-}
-
 }  // namespace
 
 extern "C" {
@@ -106,12 +151,13 @@ int svbrdf_rectify_photos_lens(const void *src, int src_format, int P, int Hs, i
     if (rc) return rc;
     rc = rectify_lens_check(who, lens);
     if (rc) return rc;
-    const bool u8 = src_format == SVBRDF_RECTIFY_U8_INTERLEAVED;
     const RectifyClip clip = rectify_clip(clip_lo, clip_hi);
     const dim3 grid = rectify_grid(P, Hd, Wd);
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (u8) launch_rectify_lens<true>(k, grid, st, src, matrices, lens, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
-    else launch_rectify_lens<false>(k, grid, st, src, matrices, lens, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+    rectify_dispatch(src_format, k, [&](auto u8, auto kk) {
+        k_lens_rectify<decltype(u8)::value, decltype(kk)::value><<<grid, kRectifyBlock, 0, st>>>(
+            src, matrices, lens, lut, clip, out, weights_out, Hs, Ws, Hd, Wd);
+    });
     return launch_status(who);
 }
 

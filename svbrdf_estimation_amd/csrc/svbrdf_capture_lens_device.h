@@ -1,9 +1,10 @@
 // svbrdf_capture_lens_device.h -- what the two lens units share: svbrdf_capture_lens.hip (k_lens_rectify) and
 // svbrdf_capture_lens_grad.hip (k_lens_grad).  The forward distortion model (ideal pixel -> distorted pixel, OpenCV's
-// fx, fy, cx, cy, k1, k2, p1, p2, k3: a closed-form polynomial, nothing to iterate) between the homography's quotient and the
-// tap cell, and the cell taken at the distorted coordinates.  include/svbrdf_hip.h has the definition in full.  The tap rule,
-// the tap index, the launch shape and the argument checks are svbrdf_capture_device.h's, which the including unit has in
-// front together with svbrdf_host.h.  No kernel and no entry point.
+// fx, fy, cx, cy, k1, k2, p1, p2, k3: a closed-form polynomial, nothing to iterate) between the homography's quotients and
+// the tap cell: the lens row, the polynomial with mono, and the lens pointer's checks.  include/svbrdf_hip.h has the
+// definition in full.  Everything else of the gather -- the quotients, the cell, the taps, the launch shape and the argument
+// checks -- is svbrdf_capture_device.h's, which the including unit has in front together with svbrdf_host.h.  No kernel and
+// no entry point.
 #ifndef SVBRDF_CAPTURE_LENS_DEVICE_H
 #define SVBRDF_CAPTURE_LENS_DEVICE_H
 
@@ -36,30 +37,20 @@ __device__ __forceinline__ RectifyLens rectify_lens_row(const float *__restrict_
     return L;
 }
 
-// One sub-sample at (xs, ys) through m0..m8 and the lens: the forward's statements from X to the quotients, the lens map, and
-// the tap cell at (ud, vd); one rounded float32 operation each.  Z, u, v are the pinhole quantities as they are; xn .. vd the
-// lens map's; the cell and the fractions come from the clamped copies of ud, vd, so every index lies in the source whatever
-// the matrix and the lens hold.
-struct RectifyLensCell {
-    float Z, u, v;
+// The lens map of one sub-sample, between the quotients (svbrdf_capture_device.h: rectify_point) and the tap cell, one rounded
+// float32 operation each: xn .. vd, and `valid` with mono's sign in it.  The cell is rectify_cell's at (ud, vd), so every
+// index lies in the source whatever the matrix and the lens hold.
+struct RectifyLensPoint {
     float xn, yn, xx, yy, r2, rad, t, xd, yd, ud, vd;
-    float fx, fy;                   // the bilinear fractions
-    int x0, y0, x1, y1;
     bool valid;
 };
 
-__device__ __forceinline__ RectifyLensCell rectify_lens_cell(const float m[9], const RectifyLens &L, float xs, float ys, int Hs,
-                                                             int Ws)
+__device__ __forceinline__ RectifyLensPoint rectify_lens_map(const RectifyPoint &q, const RectifyLens &L, int Hs, int Ws)
 {
     const float wmax = (float)(Ws - 1), hmax = (float)(Hs - 1);
-    RectifyLensCell g;
-    const float X = (m[0] * xs + m[1] * ys) + m[2];
-    const float Y = (m[3] * xs + m[4] * ys) + m[5];
-    g.Z = (m[6] * xs + m[7] * ys) + m[8];
-    g.u = X / g.Z;
-    g.v = Y / g.Z;
-    g.xn = (g.u - L.cx) / L.fx;
-    g.yn = (g.v - L.cy) / L.fy;
+    RectifyLensPoint g;
+    g.xn = (q.u - L.cx) / L.fx;
+    g.yn = (q.v - L.cy) / L.fy;
     g.xx = g.xn * g.xn;
     g.yy = g.yn * g.yn;
     const float xy = g.xn * g.yn;
@@ -75,18 +66,7 @@ __device__ __forceinline__ RectifyLensCell rectify_lens_cell(const float m[9], c
     g.vd = (g.yd * L.fy) + L.cy;
     // (`&`, not `&&`: a wave-uniform operand of `&&` becomes a branch per sub-sample, and behind it the taps of all K^2
     // sub-samples are held in registers to the kernel's end)
-    g.valid = L.focal & (g.Z > 0.0f) & (mono > 0.0f) & (g.ud >= 0.0f) & (g.ud <= wmax) & (g.vd >= 0.0f) & (g.vd <= hmax);
-    float u = g.valid ? g.ud : 0.0f;
-    float v = g.valid ? g.vd : 0.0f;
-    u = fminf(fmaxf(u, 0.0f), wmax);        // in float, before the conversion: NaN and +-inf cannot reach it
-    v = fminf(fmaxf(v, 0.0f), hmax);
-    const float x0f = floorf(u), y0f = floorf(v);
-    g.fx = u - x0f;
-    g.fy = v - y0f;
-    g.x0 = (int)x0f;
-    g.y0 = (int)y0f;
-    g.x1 = min(g.x0 + 1, Ws - 1);
-    g.y1 = min(g.y0 + 1, Hs - 1);
+    g.valid = L.focal & (q.Z > 0.0f) & (mono > 0.0f) & (g.ud >= 0.0f) & (g.ud <= wmax) & (g.vd >= 0.0f) & (g.vd <= hmax);
     return g;
 }
 

@@ -260,6 +260,48 @@ def measure_grad(dev, native, P=8, src_size=(480, 640), dst_size=(256, 256), k=1
     return out
 
 
+# ------------------------------------------------------------------------------------------------ the bits of the four entries
+
+BITS_P, BITS_SRC, BITS_DST = 3, (37, 53), (9, 70)      # two tile columns (the second ragged) x three tile rows (the last ragged)
+BITS_CASES = tuple((fmt, k) for fmt in ("uint8", "float32") for k in (1, 2, 4))
+
+
+def record_bits(native, dev):
+    """The four rectify entries of the loaded library on seeded inputs, 24 launches (and each gradient launch once more on
+    the workspace its first call left): P = 3, source 37 x 53, destination 9 x 70 -- six tiles per photo, so a photo's last
+    workgroup adds more than one partial; `outside` matrices, `barrel` lens rows with photo 2's replaced by a hostile one
+    (k1 = NaN), uint8 sources under clip (5, 250) and float32 sources without a clip, k = 1, 2, 4.
+    -> (bits, facts): bits maps "<fmt>_k<k>_<values|weights|grad_matrices|lens_values|lens_weights|lens_grad>" to float32
+    arrays (lens_grad: [P,18], matrices then lens); facts maps the same case names to
+    (canaries intact, one launch each, workspace zero after both calls, the second call's bits equal the first's)."""
+    import capture_lens_checks as lc
+    import synth
+    from svbrdf_estimation_amd import capture
+    M = cc.matrices("outside", BITS_SRC, BITS_DST, BITS_P)
+    L = lc.lenses("barrel", BITS_SRC, BITS_P)
+    L[2] = lc.hostile_lenses(BITS_SRC)["k1 = NaN"]
+    G = synth.uniform01(71, (BITS_P, 3) + BITS_DST).astype(np.float32) * 2.0 - 1.0
+    bits, facts = {}, {}
+    for fmt, k in BITS_CASES:
+        u8 = fmt == "uint8"
+        src = cc.u8_source(72, BITS_P, *BITS_SRC, blobs=True) if u8 else cc.float_source(73, BITS_P, *BITS_SRC)
+        kw = dict(k=k, lut=capture.gamma_lut().numpy() if u8 else None, clip=(5, 250) if u8 else None)
+        name = "%s_k%d_" % (fmt, k)
+        fwd = cc.abi_rectify(native, dev, src, M, BITS_DST, **kw)
+        lens = lc.abi_rectify_lens(native, dev, src, M, L, BITS_DST, **kw)
+        grad = abi_grad(native, dev, src, M, BITS_DST, G, **kw)
+        grad2 = abi_grad(native, dev, src, M, BITS_DST, G, workspace=grad["workspace"], **kw)
+        lgrad = lc.abi_lens_grad(native, dev, src, M, L, BITS_DST, G, **kw)
+        lgrad2 = lc.abi_lens_grad(native, dev, src, M, L, BITS_DST, G, workspace=lgrad["workspace"], **kw)
+        bits.update({name + "values": fwd["values"], name + "weights": fwd["weights"], name + "grad_matrices": grad["grad"],
+                     name + "lens_values": lens["values"], name + "lens_weights": lens["weights"], name + "lens_grad": lgrad["grad"]})
+        runs = (fwd, lens, grad, grad2, lgrad, lgrad2)
+        facts[name] = (all(r["canaries_intact"] for r in runs), all(r["launches"] == 1 for r in runs),
+                       all(r["workspace_zero"] for r in runs[2:]),
+                       cc.same_bits(grad2["grad"], grad["grad"]) and cc.same_bits(lgrad2["grad"], lgrad["grad"]))
+    return bits, facts
+
+
 # ------------------------------------------------------------------------------------------------ registration
 
 REG_SRC, REG_GRID, REG_STEPS, REG_LR, REG_OFF, REG_EPS = (96, 128), (32, 32), 150, 0.2, 3.0, 0.01

@@ -272,11 +272,14 @@ def test_makefile_builds_the_unit_into_the_library_and_earlier_kernels_kept_thei
 
 
 def test_source_holds_no_inline_assembly_and_no_fma():
-    src = unit_build.read_csrc("svbrdf_capture.hip")       # (the unit owns no header)
+    src = unit_build.read_csrc("svbrdf_capture.hip", "svbrdf_capture_device.h")     # the unit and the capture header it includes
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert not re.search(r"\basm\b|\b(__builtin_)?fmaf?\(|\bfma_\(|\brcp_\(|\bdiv_rn\(|atomic", code)
-    assert code.count("fminf(fmaxf(") == 2 and code.index("fminf(fmaxf(") < code.index("(int)x0f")
+    assert code.count("fminf(fmaxf(") == 1 and code.index("fminf(fmaxf(") < code.index("(int)x0f")     # one clamp, for u and v
     assert "int fail(" in unit_build.assert_includes_shared_header("svbrdf_capture", "svbrdf_host.h")
+    text = unit_build.assert_includes_shared_header("svbrdf_capture", "svbrdf_capture_device.h")
+    assert "rectify_cell" in text and "rectify_accumulate" in text and "rectify_store" in text and "rectify_dispatch" in text
+    assert re.findall(r'#include "(svbrdf_capture\w*\.h)"', unit_build.read_csrc("svbrdf_capture.hip")) == ["svbrdf_capture_device.h"]
 
 
 @needs_hipcc

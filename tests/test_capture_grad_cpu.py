@@ -8,8 +8,9 @@ k_homography_grad; svbrdf_rectify_photos_grad_matrices), everything that needs n
   * capture.corner_matrices: patch_homography in float64 to 1e-12, and torch.autograd.gradcheck;
   * the autograd wrapper's argument handling: no CPU path, and matrices without grad take the old path;
   * header, binding and library agree on the two new entries and on D; bad arguments are refused before any launch;
-  * the six kernels, compiled with the Makefile's flags: no scratch, IEEE division, an integer atomic only, and every earlier
-    kernel's machine code as the parent commit's (profiles/r23_capture_grad_codehash.txt).
+  * the six kernels, compiled with the Makefile's flags: no scratch, IEEE division, an integer atomic only; every earlier
+    kernel's machine code was the parent commit's when they came (profiles/r23_capture_grad_codehash.txt), and the library
+    holds the code recorded in profiles/r27_capture_refactor_codehash.txt.
 """
 import ctypes
 import os
@@ -149,7 +150,8 @@ def test_wrapper_has_no_cpu_path_and_leaves_the_old_path_alone(monkeypatch):
     # matrices without grad (and any matrices under no_grad) take the launch that existed before: no autograd node
     seen = []
 
-    def launch(src, mats, lut, args, lead, want_weights):
+    def launch(src, mats, lut, args, lead, want_weights, lens=None):
+        assert lens is None
         seen.append((tuple(mats.shape), mats.dtype, args))
         return torch.zeros(lead + (3, 4, 4)), torch.zeros(lead + (4, 4))
 
@@ -240,30 +242,43 @@ def test_makefile_builds_the_unit_and_earlier_kernels_kept_their_code():
         text = unit_build.assert_includes_shared_header(unit, "svbrdf_capture_device.h")
         assert "int fail(" in unit_build.assert_includes_shared_header(unit, "svbrdf_host.h")
     assert "rectify_cell" in text and "fminf(fmaxf(" in text and "rectify_tap" in text
+    text = unit_build.assert_includes_shared_header("svbrdf_capture_grad", "svbrdf_capture_grad_device.h")
+    assert "rectify_grad_reduce" in text and "rectify_grad_taps" in text and "shfl_xor_f64" in text and "static_assert" in text
     # profiles/r23_capture_grad_codehash.txt: the diff against the parent's listing holds added lines only, the six kernels
     with open(os.path.join(ROOT, "profiles", "r23_capture_grad_codehash.txt")) as f:
         listing = f.read()
     diff = listing.split("## diff parent new")[1].split("## nm")[0]
     changed = [ln for ln in diff.splitlines() if ln[:1] in ("<", ">")]
     assert len(changed) == 6 and all(ln.startswith("> ") and "k_homography_grad" in ln for ln in changed), changed
-    # and the library as built here holds the six new kernels, and the forward's six with the recorded code
+    # and the library as built here holds the six kernels and the forward's six with the code recorded when the capture units
+    # were put on shared device functions (profiles/r27_capture_refactor_codehash.txt)
     from svbrdf_estimation_amd import _codehash, _native
-    new = listing.split("## new")[1]
+    with open(os.path.join(ROOT, "profiles", "r27_capture_refactor_codehash.txt")) as f:
+        new = f.read().split("## new")[1]
     for u8 in "01":
         for k in "124":
-            assert _codehash.kernel_code_sha256(_native.library_path(), ("k_homography_grad", "ILb%sELi%sE" % (u8, k)))["bytes"] > 1000
-            got = _codehash.kernel_code_sha256(_native.library_path(), ("9k_rectifyILb%sELi%sE" % (u8, k),))
-            assert re.search(r"9k_rectifyILb%sELi%sE\S*\s+%d\s+%s" % (u8, k, got["bytes"], got["sha256"]), new), (u8, k, got)
+            for name in ("17k_homography_gradILb%sELi%sE" % (u8, k), "9k_rectifyILb%sELi%sE" % (u8, k)):
+                got = _codehash.kernel_code_sha256(_native.library_path(), (name,))
+                assert got["bytes"] > 1000 and re.search(r"%s\S*\s+%d\s+%s" % (name, got["bytes"], got["sha256"]), new), (name, got)
 
 
 def test_source_holds_no_float_atomic_no_fma_and_the_clamp_before_the_conversion():
-    src = unit_build.read_csrc("svbrdf_capture_grad.hip", "svbrdf_capture_device.h")
+    src = unit_build.read_csrc("svbrdf_capture_grad.hip", "svbrdf_capture_device.h", "svbrdf_capture_grad_device.h")
+    assert re.findall(r'#include "(svbrdf_capture\w*\.h)"', src) == ["svbrdf_capture_device.h", "svbrdf_capture_grad_device.h"]
     code = "\n".join(line.split("//")[0] for line in src.splitlines())
     assert not re.search(r"\b(__builtin_)?fmaf?\(|\bfma_\(|\brcp_\(|\bdiv_rn\(|atomicAdd|unsafeAtomic", code)
     # one integer atomic, the ticket; the two atomic stores are plain write-through stores (the partial's words, the reset)
-    assert re.findall(r"__hip_atomic_\w+", code) == ["__hip_atomic_store", "__hip_atomic_fetch_add", "__hip_atomic_store"]
+    # (twice: k_homography_grad keeps its own reduction, profiles/r27_capture_refactor.txt, beside the shared one of the header)
+    assert re.findall(r"__hip_atomic_\w+", code) == ["__hip_atomic_store", "__hip_atomic_fetch_add", "__hip_atomic_store"] * 2
     assert [m for m in re.findall(r'asm\s+volatile\s*\(\s*"([^"]*)"', code) if m != "s_waitcnt vmcnt(0)"] == []
-    assert code.count("fminf(fmaxf(") == 2 and code.index("fminf(fmaxf(") < code.index("(int)x0f")
+    # the header's one clamp, and u's and v's of the cell k_homography_grad keeps
+    assert code.count("fminf(fmaxf(") == 3 and code.index("fminf(fmaxf(") < code.index("(int)x0f")
+    shared = "\n".join(line.split("//")[0] for line in unit_build.read_csrc("svbrdf_capture_device.h", "svbrdf_capture_grad_device.h").splitlines())
+    assert shared.count("fminf(fmaxf(") == 1 and shared.index("fminf(fmaxf(") < shared.index("(int)x0f")
+    assert re.findall(r"__hip_atomic_\w+", shared) == ["__hip_atomic_store", "__hip_atomic_fetch_add", "__hip_atomic_store"]
+    order = [shared.index(w) for w in ("__hip_atomic_store(reinterpret_cast<unsigned *>(mine)", 'asm volatile("s_waitcnt vmcnt(0)"',
+                                       "__hip_atomic_fetch_add", "__ATOMIC_ACQUIRE", "(double)all[")]
+    assert order == sorted(order) and "__ATOMIC_RELEASE" not in shared
     # the partial goes out write-through and is drained before the ticket; the acquire stands between the ticket and the
     # partials' loads
     order = [code.index(w) for w in ("__hip_atomic_store(reinterpret_cast<unsigned *>(mine)", 'asm volatile("s_waitcnt vmcnt(0)"',
@@ -296,3 +311,23 @@ def test_compiled_kernels_use_no_scratch_divide_in_ieee_and_add_no_float_atomica
         assert "buffer_inv" in mns and "buffer_wbl2" not in mns, k      # one agent-scope acquire, no L2 write-back
     # per kernel: the partial's write-through store and the ticket's reset, and the acquire
     assert asm.count("buffer_inv sc1") == 6 and len(re.findall(r"global_store_dword v\d+, v\d+, s\[\d+:\d+\] sc1", asm)) == 12
+
+
+def test_the_recorded_bits_are_the_file_the_manifest_lists(golden):
+    """tests/golden/g24_capture_bits.npz (the GPU suite's bit pin of the four entries): 36 float32 arrays of record_bits' shapes,
+    the manifest's checksum, and small"""
+    import hashlib
+    import json
+    path = os.path.join(ROOT, "tests", "golden", "g24_capture_bits.npz")
+    with open(os.path.join(ROOT, "tests", "golden", "MANIFEST_g24_capture.json")) as f:
+        entry = json.load(f)["fixtures"]["g24_capture_bits.npz"]
+    with open(path, "rb") as f:
+        assert hashlib.sha256(f.read()).hexdigest() == entry["sha256"]
+    assert os.path.getsize(path) < 256 * 1024 and "record_bits" in entry["generator"]
+    g = golden("g24_capture_bits.npz")
+    P, (Hd, Wd) = gc.BITS_P, gc.BITS_DST
+    shapes = {"values": (P, 3, Hd, Wd), "weights": (P, Hd, Wd), "grad_matrices": (P, 9), "lens_values": (P, 3, Hd, Wd),
+              "lens_weights": (P, Hd, Wd), "lens_grad": (P, 18)}
+    assert sorted(g.files) == sorted("%s_k%d_%s" % (fmt, k, what) for fmt, k in gc.BITS_CASES for what in shapes)
+    for name in g.files:
+        assert g[name].dtype == np.float32 and g[name].shape == shapes[name.split("_", 2)[2]], name

@@ -331,16 +331,15 @@ def test_wrapper_has_no_cpu_path_and_lens_none_is_the_old_launch(monkeypatch):
         capture.rectify(img, M, 4, lens=torch.from_numpy(lc.NULL).requires_grad_(True))
     old, new = [], []
 
-    def launch(src, mats, lut, args, lead, want_weights):
-        old.append((tuple(mats.shape), mats.dtype, args))
-        return torch.zeros(lead + (3, 4, 4)), torch.zeros(lead + (4, 4))
-
-    def launch_lens(src, mats, lens, lut, args, lead, want_weights):
-        new.append((tuple(mats.shape), tuple(lens.shape), lens.dtype, args))
+    def launch(src, mats, lut, args, lead, want_weights, lens=None):
+        """the one launcher: without lens rows it calls svbrdf_rectify_photos (`old`), with them svbrdf_rectify_photos_lens"""
+        if lens is None:
+            old.append((tuple(mats.shape), mats.dtype, args))
+        else:
+            new.append((tuple(mats.shape), tuple(lens.shape), lens.dtype, args))
         return torch.zeros(lead + (3, 4, 4)), torch.zeros(lead + (4, 4))
 
     monkeypatch.setattr(capture, "_launch_rectify", launch)
-    monkeypatch.setattr(capture, "_launch_rectify_lens", launch_lens)
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
     args = (cc.F32_PLANAR, 2, 8, 9, 4, 4, 2, -np.inf, np.inf)
     out, w = capture.rectify(img, M, 4, samples=2, lens=None)
@@ -359,6 +358,14 @@ def test_wrapper_has_no_cpu_path_and_lens_none_is_the_old_launch(monkeypatch):
         capture.rectify(img, M, 4, lens=np.zeros(8))
     with pytest.raises(ValueError):
         capture.rectify(img, M, 4, lens=np.zeros((3, 9)))
+    # and the launcher itself: the entry it names, and the lens pointer only behind the lens entry
+    monkeypatch.undo()
+    calls = []
+    monkeypatch.setattr(_native, "_call", lambda name, device, *a: calls.append((name, len(a))))
+    rows = torch.zeros(2, 9)
+    capture._launch_rectify(img, rows, None, args, (2,), True)
+    capture._launch_rectify(img, rows, None, args, (2,), True, rows)
+    assert calls == [("svbrdf_rectify_photos", 14), ("svbrdf_rectify_photos_lens", 15)]
 
 
 def test_backward_returns_each_gradient_in_its_inputs_shape_dtype_and_device(monkeypatch):
@@ -373,7 +380,7 @@ def test_backward_returns_each_gradient_in_its_inputs_shape_dtype_and_device(mon
         calls.append((tuple(mats.shape), tuple(lens.shape), tuple(g.shape), g.dtype, g.is_contiguous()))
         return rows
 
-    monkeypatch.setattr(capture, "_launch_rectify_lens", lambda src, mats, lens, lut, args, lead, ww: (
+    monkeypatch.setattr(capture, "_launch_rectify", lambda src, mats, lut, args, lead, ww, lens=None: (
         torch.zeros(lead + (3, 4, 4)), torch.zeros(lead + (4, 4))))
     monkeypatch.setattr(_native, "rectify_lens_grad", grad)
     monkeypatch.setattr(torch.Tensor, "is_cuda", property(lambda self: True))
@@ -505,9 +512,10 @@ def test_makefile_builds_the_units_and_earlier_kernels_kept_their_code():
     for unit in UNITS:
         unit_build.assert_makefile_builds(unit)             # HIPFLAGS and no scheduler option set
         text = unit_build.assert_includes_shared_header(unit, "svbrdf_capture_lens_device.h")
-        unit_build.assert_includes_shared_header(unit, "svbrdf_capture_device.h")
+        shared = unit_build.assert_includes_shared_header(unit, "svbrdf_capture_device.h")
         assert "int fail(" in unit_build.assert_includes_shared_header(unit, "svbrdf_host.h")
-    assert "rectify_lens_cell" in text and "fminf(fmaxf(" in text and "mono" in text
+    assert "rectify_lens_map" in text and "mono" in text and "rectify_cell" in shared and "fminf(fmaxf(" in shared
+    assert "rectify_grad_reduce" in unit_build.assert_includes_shared_header(UNITS[1], "svbrdf_capture_grad_device.h")
     # profiles/r25_capture_lens_codehash.txt: the diff against the parent's listing holds added lines only, the twelve kernels
     with open(os.path.join(ROOT, "profiles", "r25_capture_lens_codehash.txt")) as f:
         listing = f.read()
@@ -515,7 +523,20 @@ def test_makefile_builds_the_units_and_earlier_kernels_kept_their_code():
     changed = [ln for ln in diff.splitlines() if ln[:1] in ("<", ">")]
     assert len(changed) == 12 and all(ln.startswith("> ") for ln in changed), changed
     assert sum("k_lens_rectify" in ln for ln in changed) == 6 == sum("k_lens_grad" in ln for ln in changed)
-    # and the library as built here holds the twelve new kernels and the twelve capture kernels, with the recorded code
+    # profiles/r27_capture_refactor_codehash.txt, the capture units on shared device functions: the diff against the parent's
+    # listing touches only lines that name the four kernel templates -- the six k_rectify and the six k_lens_grad on both
+    # sides; k_homography_grad and k_lens_rectify got their old bodies back and keep the parent's code -- every other
+    # function of the library keeps symbol, size and sha256, and the exported symbols are the parent's
+    with open(os.path.join(ROOT, "profiles", "r27_capture_refactor_codehash.txt")) as f:
+        listing = f.read()
+    diff = listing.split("## diff parent new")[1].split("## nm")[0]
+    changed = [ln for ln in diff.splitlines() if ln[:1] in ("<", ">")]
+    templates = ("9k_rectifyIL", "17k_homography_gradIL", "14k_lens_rectifyIL", "11k_lens_gradIL")
+    assert len(changed) == 24 and all(sum(t in ln for t in templates) == 1 for ln in changed), changed
+    assert sum("9k_rectifyIL" in ln for ln in changed) == 12 == sum("11k_lens_gradIL" in ln for ln in changed)
+    assert sorted(ln.split()[1] for ln in changed if ln[0] == "<") == sorted(ln.split()[1] for ln in changed if ln[0] == ">")
+    assert [ln for ln in listing.split("## nm")[1].split("## new")[0].splitlines()[1:] if ln.strip()] == []
+    # and the library as built here holds the 24 capture kernels with the code recorded there
     from svbrdf_estimation_amd import _codehash, _native
     new = listing.split("## new")[1]
     for u8 in "01":
@@ -529,18 +550,21 @@ def test_makefile_builds_the_units_and_earlier_kernels_kept_their_code():
 def test_source_holds_no_float_atomic_no_fma_and_the_clamp_before_the_conversion():
     header = unit_build.read_csrc("svbrdf_capture_lens_device.h")
     for unit in UNITS:
-        src = unit_build.read_csrc(unit + ".hip", "svbrdf_capture_lens_device.h")
+        headers = re.findall(r'#include "(svbrdf_capture\w*\.h)"', unit_build.read_csrc(unit + ".hip"))
+        assert headers == ["svbrdf_capture_device.h"] + ["svbrdf_capture_grad_device.h"] * unit.endswith("_grad") + ["svbrdf_capture_lens_device.h"]
+        src = unit_build.read_csrc(unit + ".hip", *headers)     # the unit and every capture header it includes
         code = "\n".join(line.split("//")[0] for line in src.splitlines())
         assert not re.search(r"\b(__builtin_)?fmaf?\(|\bfma_\(|\brcp_\(|\bdiv_rn\(|atomicAdd|unsafeAtomic", code), unit
         assert [m for m in re.findall(r'asm\s+volatile\s*\(\s*"([^"]*)"', code) if m != "s_waitcnt vmcnt(0)"] == [], unit
         assert len(re.findall(r"\basm\b", code)) == (2 if unit.endswith("_grad") else 0), unit
-        assert code.count("fminf(fmaxf(") == 2 and code.index("fminf(fmaxf(") < code.index("(int)x0f"), unit
+        # one clamp in the shared header; k_lens_rectify keeps its own cell with u's and v's (profiles/r27_capture_refactor.txt)
+        assert code.count("fminf(fmaxf(") == (1 if unit.endswith("_grad") else 3) and code.index("fminf(fmaxf(") < code.index("(int)x0f"), unit
         assert "__ATOMIC_RELEASE" not in code
         atomics = re.findall(r"__hip_atomic_\w+", code)
         assert atomics == (["__hip_atomic_store", "__hip_atomic_fetch_add", "__hip_atomic_store"] if unit.endswith("_grad") else []), unit
     code = "\n".join(line.split("//")[0] for line in header.splitlines())
     assert "atomic" not in code and "asm" not in code
-    grad = unit_build.read_csrc("svbrdf_capture_lens_grad.hip")
+    grad = unit_build.read_csrc("svbrdf_capture_lens_grad.hip", "svbrdf_capture_grad_device.h")
     order = [grad.index(w) for w in ("__hip_atomic_store(reinterpret_cast<unsigned *>(mine)", 'asm volatile("s_waitcnt vmcnt(0)"',
                                      "__hip_atomic_fetch_add", "__ATOMIC_ACQUIRE", "(double)all[")]
     assert order == sorted(order)

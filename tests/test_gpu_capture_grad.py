@@ -311,3 +311,30 @@ def test_one_launch_is_no_slower_than_the_composed_backward(native, dev):
           "launch %.1f us (backward / forward %.2f); rounds %s" % (r["fused_us"], r["composed_us"], r["fused_us"] / r["composed_us"],
                                                                   r["forward_us"], r["fused_us"] / r["forward_us"], r["rounds"]))
     assert r["fused_us"] <= r["composed_us"]
+
+
+# ------------------------------------------------------------------------------------------------ the bits
+
+def test_the_four_entries_return_the_recorded_bits(native, dev, golden):
+    """tests/golden/g24_capture_bits.npz holds what the four rectify entries returned on the MI355X at the commit before the
+    capture units were put on shared device functions (capture_grad_checks.record_bits: P = 3, 37 x 53 -> 9 x 70, both
+    formats, k = 1, 2, 4, a hostile lens row).  The library under test returns exactly those bits for values, weights,
+    grad_matrices and grad_lens, leaves each workspace all zero, and a second call on the same workspace returns the same
+    bits.  The bits are stable because the source fixes every rounding and the whole order of the reduction -- a thread's
+    sub-samples in (j, i) order, the 64-lane butterfly, (w0 + w1) + (w2 + w3), the lane-strided float64 sum in index order,
+    one rounding to float32 -- and no operation may be fused or reassociated (-ffp-contract=off, IEEE division): they are a
+    property of the definition, not of the compiler's register allocation or schedule."""
+    want = golden("g24_capture_bits.npz")
+    bits, facts = gc.record_bits(native, dev)
+    assert sorted(bits) == sorted(want.files) and len(bits) == 6 * len(gc.BITS_CASES) == 36
+    for name, (intact, one_launch, zeroed, repeats) in facts.items():
+        assert intact and one_launch and zeroed and repeats, (name, intact, one_launch, zeroed, repeats)
+    for name in sorted(bits):
+        assert bits[name].dtype == np.float32 == want[name].dtype and bits[name].shape == want[name].shape, name
+        assert cc.same_bits(bits[name], want[name]), (name, cc.count_differing(bits[name], want[name]))
+    # the case is not empty: pixels of both kinds, non-zero gradients for the first two photos, zeros under the hostile lens
+    for fmt, k in gc.BITS_CASES:
+        name = "%s_k%d_" % (fmt, k)
+        assert 0 < want[name + "weights"].mean() < 1 and want[name + "lens_weights"][:2].any(), name
+        assert want[name + "grad_matrices"].all(axis=1).any() and want[name + "lens_grad"][:2].any(axis=1).all(), name
+        assert not want[name + "lens_weights"][2].any() and not want[name + "lens_grad"][2].any(), name
