@@ -132,6 +132,20 @@ SIGNATURES = {
     "svbrdf_render_bwd_f64": (_int, [_fp] * 5 + _DIMS),
     "svbrdf_render_bwd_jvp_f64": (_int, [_fp] * 7 + _DIMS),
 }
+# What differs between the modes of a photo entry (photo_loss), keyed by the extra output the entry produces:
+#   suffix       between "svbrdf_[head_]photo_loss" and "_fwd_bwd" (without an extra output the weighted entries have a
+#                name of their own, "_weighted", and the unweighted ones alone take no (weights, planes))
+#   workspace    the library function that sizes its scratch
+#   always_grad  the kernel always forms the map gradient, `want_grad` only decides whether it is returned; else
+#                `want_grad` picks the forward-only kernel
+#   by_value     a *_host_scenes form exists; else a host table is uploaded
+_PhotoMode = collections.namedtuple("_PhotoMode", "suffix workspace always_grad by_value")
+_PHOTO_MODES = {
+    None: _PhotoMode("", "svbrdf_rendering_loss_workspace_bytes", False, True),
+    "exposure": _PhotoMode("_exposure", "svbrdf_photo_exposure_workspace_bytes", True, False),
+    "scenes": _PhotoMode("_scene_grad", "svbrdf_photo_scene_grad_workspace_bytes", True, False),
+    "photos": _PhotoMode("_photo_grad", "svbrdf_rendering_loss_workspace_bytes", False, False),
+}
 
 
 def _load():
@@ -556,6 +570,25 @@ def _checked_weights(weights, device, B, S, H, W):
     return weights.contiguous()
 
 
+def _photo_operands(maps, photos, scenes, weights, channels=12):
+    """The operands every photo entry takes beside its maps (float32 device [B,channels,H,W], the caller's check), checked:
+    photos float32 [B,S,3,H,W] on the maps' device, the scene table by _PHOTO_TABLE's rule, weights as _checked_weights takes
+    them or None.  -> (table, B, S, H, W, on_host: the table is still on the host, small enough to go by value; photos and
+    weights contiguous, for the caller's frame to hold until the launch is enqueued; (weights pointer, planes) as the
+    weighted entries take them, (None, 0) without weights)"""
+    _require_device_f32(photos, "photos")
+    if photos.device != maps.device:
+        raise ValueError("input, photos and scenes must be on the same device")
+    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, maps, scenes, channels=channels)[:6]
+    if tuple(photos.shape) != (B, S, 3, H, W):
+        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
+                         % ((B, S, 3, H, W), tuple(photos.shape)))
+    if weights is None:
+        return scenes, B, S, H, W, on_host, photos.contiguous(), None, (None, 0)
+    weights = _checked_weights(weights, maps.device, B, S, H, W)
+    return scenes, B, S, H, W, on_host, photos.contiguous(), weights, (weights.data_ptr(), int(weights.shape[1]))
+
+
 def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weights=None, exposure=None,
                want_exposure_grad=False, want_scene_grad=False, want_photo_grad=False):
     """Fused photo loss (svbrdf_photo_loss_fwd_bwd*): mean |log(render(scenes[b,s], input[b]) + eps) - log(photos[b,s] + eps)|
@@ -589,57 +622,35 @@ def photo_loss(input, photos, scenes, eps=0.1, want_grad=True, head=False, weigh
     if want_photo_grad and (exposure is not None or want_scene_grad):
         raise ValueError("want_photo_grad takes neither an exposure nor want_scene_grad: those combinations are the composed "
                          "definition's (losses.composed_photo_loss); a constant gain multiplies the table's colour columns")
+    third = "photos" if want_photo_grad else "scenes" if want_scene_grad else "exposure" if exposure is not None else None
+    suffix, workspace, always_grad, by_value = _PHOTO_MODES[third]
     _require_device_f32(input, "input")
-    _require_device_f32(photos, "photos")
-    if photos.device != input.device:
-        raise ValueError("input, photos and scenes must be on the same device")
-    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, input, scenes, channels=9 if head else 12)[:6]
-    if tuple(photos.shape) != (B, S, 3, H, W):
-        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
-                         % ((B, S, 3, H, W), tuple(photos.shape)))
-    stem = "svbrdf_head_photo_loss" if head else "svbrdf_photo_loss"
-    extra = ()
-    if weights is not None:
-        weights = _checked_weights(weights, input.device, B, S, H, W)
-        stem, extra = stem + "_weighted", (weights.data_ptr(), int(weights.shape[1]))
-    if exposure is not None:
+    scenes, B, S, H, W, on_host, photos, weights, extra = _photo_operands(input, photos, scenes, weights, 9 if head else 12)
+    if third is None:
+        if weights is None:
+            extra = ()
+        else:
+            suffix = "_weighted"
+    elif third == "exposure":
         _require_device_f32(exposure, "exposure")
         if exposure.device != input.device:
             raise ValueError("input, photos and exposure must be on the same device")
         if tuple(exposure.shape) != (B, S, 3):
             raise ValueError("exposure must be [B,S,3] = %s for these maps and photos, got %s" % ((B, S, 3), tuple(exposure.shape)))
         exposure = exposure.contiguous()
-        if on_host:
-            scenes = upload_scene_table(scenes, input.device)
-        if weights is None:
-            extra = (None, 0)
-        grad_exposure = torch.empty_like(exposure) if want_exposure_grad else None
-        loss, grad = _fused_loss_call(
-            ("svbrdf_head_photo_loss" if head else "svbrdf_photo_loss") + "_exposure_fwd_bwd", input.contiguous(),
-            photos.contiguous(), scenes, (ctypes.c_float(eps),), True, B, S, H, W, extra + (exposure.data_ptr(),),
-            (grad_exposure.data_ptr() if want_exposure_grad else None,), "svbrdf_photo_exposure_workspace_bytes")
-        return loss, (grad if want_grad else None), grad_exposure
-    if want_scene_grad:
-        if on_host:
-            scenes = upload_scene_table(scenes, input.device)
-        grad_scenes = torch.empty_like(scenes)
-        loss, grad = _fused_loss_call(
-            ("svbrdf_head_photo_loss" if head else "svbrdf_photo_loss") + "_scene_grad_fwd_bwd", input.contiguous(),
-            photos.contiguous(), scenes, (ctypes.c_float(eps),), True, B, S, H, W, extra or (None, 0),
-            (grad_scenes.data_ptr(),), "svbrdf_photo_scene_grad_workspace_bytes")
-        return loss, (grad if want_grad else None), grad_scenes
-    if want_photo_grad:
-        if on_host:
-            scenes = upload_scene_table(scenes, input.device)
-        photos = photos.contiguous()
-        grad_photos = torch.empty_like(photos)
-        loss, grad = _fused_loss_call(
-            ("svbrdf_head_photo_loss" if head else "svbrdf_photo_loss") + "_photo_grad_fwd_bwd", input.contiguous(), photos,
-            scenes, (ctypes.c_float(eps),), want_grad, B, S, H, W, extra or (None, 0), (grad_photos.data_ptr(),))
-        return loss, grad, grad_photos
-    entry = stem + "_fwd_bwd" + ("_host_scenes" if on_host else "")
-    return _fused_loss_call(entry, input.contiguous(), photos.contiguous(), scenes, (ctypes.c_float(eps),), want_grad,
-                            B, S, H, W, extra)
+        extra += (exposure.data_ptr(),)
+    if on_host and not by_value:
+        scenes, on_host = upload_scene_table(scenes, input.device), False
+    out, more = None, ()
+    if third is not None:       # the mode's own output, like the operand it is the gradient of (the table: the device's)
+        like = photos if third == "photos" else scenes if third == "scenes" else exposure if want_exposure_grad else None
+        if like is not None:
+            out = torch.empty_like(like)
+        more = (None if out is None else out.data_ptr(),)
+    loss, grad = _fused_loss_call(
+        ("svbrdf_head_photo_loss" if head else "svbrdf_photo_loss") + suffix + "_fwd_bwd" + ("_host_scenes" if on_host else ""),
+        input.contiguous(), photos, scenes, (ctypes.c_float(eps),), want_grad or always_grad, B, S, H, W, extra, more, workspace)
+    return (loss, grad) if third is None else (loss, grad if want_grad else None, out)
 
 
 def photo_fit_adam_scalars(lr, beta1, beta2, step):
@@ -656,23 +667,13 @@ def _fit_operands(maps, exp_avg, exp_avg_sq, photos, scenes, weights):
     photos, scenes, weights as photo_loss takes them; a host table is uploaded (the entries take a device table).
     -> (the device table, (B, S, H, W), `extra`: what the entries take between exp_avg and the table, `keep`: the tensors
     behind extra's pointers, for the caller's frame to hold until the launch is enqueued)"""
-    for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq"), (photos, "photos")):
-        _require_device_f32(t, name)
     for t, name in ((maps, "maps"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _require_device_f32(t, name)
         if not t.is_contiguous() or t.shape != maps.shape or t.device != maps.device:
             raise ValueError("%s is updated in place: a contiguous tensor of the maps' shape on their device" % name)
-    if photos.device != maps.device:
-        raise ValueError("input, photos and scenes must be on the same device")
-    scenes, B, S, H, W, on_host = _scene_table(_PHOTO_TABLE, maps, scenes)[:6]
+    scenes, B, S, H, W, on_host, photos, weights, planes = _photo_operands(maps, photos, scenes, weights)
     if on_host:
         scenes = upload_scene_table(scenes, maps.device)
-    if tuple(photos.shape) != (B, S, 3, H, W):
-        raise ValueError("photos must be [B,S,3,H,W] = %s for these maps and scenes, got %s"
-                         % ((B, S, 3, H, W), tuple(photos.shape)))
-    if weights is not None:
-        weights = _checked_weights(weights, maps.device, B, S, H, W)
-    photos = photos.contiguous()
-    planes = (None, 0) if weights is None else (weights.data_ptr(), int(weights.shape[1]))
     return scenes, (B, S, H, W), (exp_avg_sq.data_ptr(), photos.data_ptr()) + planes, (photos, weights)
 
 

@@ -266,7 +266,7 @@ class PhotoFit:
         return self._spare
 
     def uses_fused_kernel(self):
-        return (losses.PhotoLoss(self.renderer).uses_fused_kernel() and self.maps.is_cuda
+        return (losses.RenderingLoss.uses_fused_kernel(self) and self.maps.is_cuda     # (its rule, on this renderer)
                 and self.maps.dtype == torch.float32)
 
     def _fused_inputs(self, x, photos, scenes, weights, exposure, constants):
@@ -290,7 +290,7 @@ class PhotoFit:
             # (_PhotoLossModule._forward), and autograd chains the table's gradient back through both
             table = table.to(x.device)
             if exposure is not None:
-                table = torch.cat((table[..., :6], table[..., 6:] * exposure), dim=-1)
+                table = losses.fold_exposure(table, exposure)
         return photos, weights, table, want
 
     def step(self, photos, scenes, weights=None, exposure=None):

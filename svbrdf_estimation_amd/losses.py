@@ -73,7 +73,8 @@ def _hand_over_gradients(ctx, grad_loss, second_time):
     they stay with the graph and every backward receives a scaled copy, so repeated backwards work as through the
     reference's plain-autograd loss (losses.py:29-52), and a second backward without it fails like autograd's own nodes
     do (``second_time``: the message).  The cached 1.0 of ``_UnitGradientLoss`` is recognised (once somebody has asked
-    for one): nothing to scale, nothing to launch.  -> the list of gradients, in ``ctx.grads``' order."""
+    for one): nothing to scale, nothing to launch.  -> the gradients, in ``ctx.grads``' order (that
+    tuple itself on the plain unit-gradient step, a list otherwise: callers unpack it)."""
     grads = ctx.grads
     if grads is None:
         raise RuntimeError(second_time)
@@ -81,6 +82,8 @@ def _hand_over_gradients(ctx, grad_loss, second_time):
     if not keep:
         ctx.grads = None
     unit = bool(_unit_gradients) and _is_unit_gradient(grad_loss)
+    if unit and not keep:
+        return grads        # the plain step: the buffers as they are
     scale = None if unit else grad_loss.detach().to(torch.float32).reshape(1)
     outs = []
     for g in grads:
@@ -124,13 +127,18 @@ def differentiable_loss_backward(input, target, scenes, eps, l1_weight, eps_l1, 
     """(d loss/d input, d loss/d target) x ``grad_loss`` for the fused loss, attached to the autograd graph: the answer
     to ``backward(create_graph=True)`` / ``torch.autograd.grad(..., create_graph=True)``.  Also the entry point the native
     host extension calls back into (csrc/host_ext.cpp)."""
+    return _composed_gradients(lambda: composed_loss(input, target, scenes, eps, l1_weight, eps_l1, head), (input, target),
+                               (need_in, need_tg), grad_loss)
+
+
+def _composed_gradients(composed, tensors, needs, grad_loss):
+    """What backward(create_graph=True) of a fused loss answers: the gradients of ``composed()`` -- the loss from
+    differentiable pieces, a float64 scalar, built here under grad mode -- towards those of ``tensors`` that ``needs``
+    marks, times ``grad_loss``, attached to the autograd graph, each in its tensor's dtype; None for the others."""
     with torch.enable_grad():
-        loss = composed_loss(input, target, scenes, eps, l1_weight, eps_l1, head)
-        wanted = [t for t, need in ((input, need_in), (target, need_tg)) if need]
-        grads = list(torch.autograd.grad(loss, wanted, grad_loss.to(torch.float64).reshape(()), create_graph=True))
-    g_in = grads.pop(0).to(input.dtype) if need_in else None
-    g_tg = grads.pop(0).to(target.dtype) if need_tg else None
-    return g_in, g_tg
+        wanted = [t for t, need in zip(tensors, needs) if need]
+        grads = iter(torch.autograd.grad(composed(), wanted, grad_loss.to(torch.float64).reshape(()), create_graph=True))
+    return tuple(next(grads).to(t.dtype) if need else None for t, need in zip(tensors, needs))
 
 
 class _UnitGradientLoss(torch.Tensor):
@@ -289,34 +297,24 @@ class _FusedPhotoLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, photos, scenes, eps, head, weights=None, exposure=None):
-        need_in = ctx.needs_input_grad[0]
-        need_s = ctx.needs_input_grad[2]            # the scene table's gradient: a device table, no exposure (_forward)
-        need_e = exposure is not None and ctx.needs_input_grad[6]
-        need_p = ctx.needs_input_grad[1]            # the photos' gradient: no exposure, no table gradient (_forward)
+        needs = ctx.needs_input_grad        # (read once: every access builds the tuple anew)
+        # the binding's mode, by the one extra gradient a launch can form: the photos' (no exposure, no table gradient:
+        # _forward), else the scene table's (a device table, no exposure: _forward), else the exposure's, else none
+        mode = "photos" if needs[1] else "scenes" if needs[2] else "exposure" if exposure is not None else None
+        need_s = mode == "scenes"
         # (for backward(create_graph=True) only: references, no copies)
         ctx.save_for_backward(input, photos, *(() if exposure is None else (exposure,)), *((scenes,) if need_s else ()))
         ctx.second_order = (None if need_s else scenes if scenes.is_cuda else scenes.detach().clone(), float(eps), bool(head),
                             weights)
-        if need_p:
-            # the photo-gradient kernels: map and photo gradient out of the ONE launch; a detached input runs the
-            # forward-only scene loop (loss + grad_photos)
-            loss, grad, grad_p = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights,
-                                                    want_photo_grad=True)
-            ctx.grads = (grad, None, None, grad_p)
-        elif need_s:
-            # the scene-gradient kernels: map and table gradient out of the ONE launch
-            loss, grad, grad_s = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights,
-                                                    want_scene_grad=True)
-            ctx.grads = (grad, None, grad_s)
-        elif exposure is None:
-            loss, grad = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights)
-            ctx.grads = None if grad is None else (grad,)
-        else:
-            # the exposure kernels: both gradients out of the ONE launch
-            loss, grad, grad_e = _native.photo_loss(input, photos, scenes, eps, want_grad=need_in, head=head, weights=weights,
-                                                    exposure=exposure, want_exposure_grad=need_e)
-            ctx.grads = None if grad is None and grad_e is None else (grad, grad_e)
-        return loss.view(())
+        # ONE launch in every mode: loss, map gradient (a detached input runs the photo-gradient kernels' forward-only
+        # scene loop) and the mode's own gradient.  (eps, want_grad, head, weights, exposure, want_exposure_grad,
+        # want_scene_grad, want_photo_grad)
+        out = _native.photo_loss(input, photos, scenes, eps, needs[0], head, weights, exposure if mode == "exposure" else None,
+                                 mode == "exposure" and needs[6], need_s, mode == "photos")
+        # always in the order (input, exposure, scenes, photos), None where a gradient was not produced
+        third = None if mode is None else out[2]
+        ctx.grads = (out[1], third if mode == "exposure" else None, third if need_s else None, third if mode == "photos" else None)
+        return out[0].view(())
 
     @staticmethod
     def backward(ctx, grad_loss):
@@ -326,26 +324,21 @@ class _FusedPhotoLoss(torch.autograd.Function):
             scenes, eps, head, weights = ctx.second_order
             input, photos, *rest = ctx.saved_tensors
             table = rest.pop() if scenes is None else None
-            exposure = rest
-            need = [ctx.needs_input_grad[0], bool(exposure) and ctx.needs_input_grad[6], table is not None,
-                    ctx.needs_input_grad[1]]
-            with torch.enable_grad():
+            exposure = rest[0] if rest else None
+
+            def composed():
                 x = input.to(torch.float64)
-                e = exposure[0].to(torch.float64) if exposure else None
-                loss = composed_photo_loss(decode_head(x) if head else x, photos, scenes if table is None else table, eps,
-                                           weights, e)
-                wanted = [t for t, n in zip((input, exposure[0] if exposure else None, table, photos), need) if n]
-                grads = list(torch.autograd.grad(loss, wanted, grad_loss.to(torch.float64).reshape(()), create_graph=True))
-            g_in = grads.pop(0).to(input.dtype) if need[0] else None
-            g_e = grads.pop(0).to(exposure[0].dtype) if need[1] else None
-            g_s = grads.pop(0) if need[2] else None
-            g_p = grads.pop(0) if need[3] else None
-            return g_in, g_p, g_s, None, None, None, g_e
-        grads = _hand_over_gradients(ctx, grad_loss, "Trying to backward through the fused photo loss a second time: its "
-                                     "gradient buffer was handed to the first backward.  Specify retain_graph=True for "
-                                     "the first one.")
-        return (grads[0], (grads[3] if len(grads) > 3 else None), (grads[2] if len(grads) > 2 else None), None, None, None,
-                (grads[1] if len(grads) > 1 else None))
+                return composed_photo_loss(decode_head(x) if head else x, photos, scenes if table is None else table, eps,
+                                           weights, None if exposure is None else exposure.to(torch.float64))
+            g_in, g_e, g_s, g_p = _composed_gradients(
+                composed, (input, exposure, table, photos),
+                (ctx.needs_input_grad[0], exposure is not None and ctx.needs_input_grad[6], table is not None,
+                 ctx.needs_input_grad[1]), grad_loss)
+        else:
+            g_in, g_e, g_s, g_p = _hand_over_gradients(
+                ctx, grad_loss, "Trying to backward through the fused photo loss a second time: its gradient buffer was "
+                "handed to the first backward.  Specify retain_graph=True for the first one.")
+        return g_in, g_p, g_s, None, None, None, g_e
 
 
 class _PhotoLossTensor(_UnitGradientLoss):
@@ -407,6 +400,14 @@ def composed_photo_loss(input, photos, scenes, eps, weights=None, exposure=None)
     if weights is not None:
         return weighted_log_l1(rendered, photos, eps, weights)
     return nn.functional.l1_loss(torch.log(rendered + eps), torch.log(photos.to(rendered.dtype) + eps))
+
+
+def fold_exposure(table, exposure):
+    """The scene table ``[B,S,9]`` with the gains ``exposure`` (broadcastable to ``[B,S,3]``) multiplied into its colour
+    columns, in the table's float32 when both are: THE expression behind "loss and map gradient equal, bit for bit, those
+    of a scene table whose colour columns were multiplied by the gains in float32" (PhotoLoss).  Stock torch ops:
+    autograd chains a gradient towards the folded table back to table and gains."""
+    return torch.cat((table[..., :6], table[..., 6:] * exposure), dim=-1)
 
 
 _NORMALIZE = ("count", "weights")
@@ -502,7 +503,7 @@ class _PhotoLossModule(nn.Module):
         self.differentiable_photos = bool(differentiable_photos)
 
     def uses_fused_kernel(self):
-        return RenderingLoss(self.renderer).uses_fused_kernel()
+        return RenderingLoss.uses_fused_kernel(self)     # its rule, on this module's renderer: no module is built per call
 
     def _forward_decoded(self, encoded9, photos, scenes, weights, exposure=None):
         """the head losses' composed definition: PhotoLoss, which normalises by itself, on the decoded maps"""
@@ -542,23 +543,18 @@ class _PhotoLossModule(nn.Module):
                 # differentiable in all of them (float32 K1 / K2, or render_table for the table)
                 loss = composed_photo_loss(decode_head(x) if head else x, photos, table.to(x.device), self.eps, weights, exposure)
             else:
-                if need_p and exposure is not None:
-                    # the photo-gradient kernel takes no exposure: a constant gain multiplies the colour columns
-                    table = table.to(x.device)
-                    table = torch.cat((table[..., :6], table[..., 6:] * exposure.detach()), dim=-1)
-                    exposure = None
-                if table.requires_grad and torch.is_grad_enabled():
-                    # the scene-gradient kernel takes a device table and no exposure: the gains multiply the colour columns
-                    # in front of it (the exposure kernels' one float32 multiply), and autograd chains the table's
-                    # gradient back to them and through the copy of a host table
-                    table = table.to(x.device)
-                    if exposure is not None:
-                        table = torch.cat((table[..., :6], table[..., 6:] * exposure), dim=-1)
-                        exposure = None
-                elif exposure is not None and not (torch.is_grad_enabled() and (x.requires_grad or exposure.requires_grad)):
-                    table = table.to(x.device)
-                    table = torch.cat((table[..., :6], table[..., 6:] * exposure.detach()), dim=-1)
-                    exposure = None
+                # An exposure goes to its own kernels only when the input's or its own gradient is what is wanted.  The
+                # photo-gradient and scene-gradient kernels take none, and there is no forward-only exposure kernel (a
+                # pure evaluation is not on the hot path): there the gains multiply the table's colour columns in front
+                # of the call -- the exposure kernels' one float32 multiply, the same loss bit for bit -- as constants,
+                # unless it is the table's gradient that is wanted: autograd then chains it back to the gains.
+                want_table = table.requires_grad and torch.is_grad_enabled()
+                fold = exposure is not None and (need_p or want_table or not (
+                    torch.is_grad_enabled() and (x.requires_grad or exposure.requires_grad)))
+                if want_table or fold:
+                    table = table.to(x.device)      # (the kernels behind both take a device table; autograd sees the copy)
+                if fold:
+                    table, exposure = fold_exposure(table, exposure if want_table else exposure.detach()), None
                 loss = _FusedPhotoLoss.apply(x, photos, table, float(self.eps), head, weights, exposure)
                 if (weights is None or self.normalize == "count") and loss.requires_grad:
                     return loss.as_subclass(_PhotoLossTensor)

@@ -187,7 +187,7 @@ def main():
         if args.noise:
             ap.error("--fit-exposure renders its photographs noise-free: not combined with --noise")
         hidden = 0.5 + 1.5 * torch.from_numpy(synth.uniform01(args.seed + 2000, (B, S, 3))).to(dev)
-        scaled = torch.cat((table[..., :6], table[..., 6:] * hidden), dim=-1)
+        scaled = losses.fold_exposure(table, hidden)
         photos = _native.render_fwd(truth, scaled).clamp_(0.0, 1.0)
     if not args.captured:
         return fit(args, dev, truth, photos, table, hidden)
@@ -478,7 +478,7 @@ def fit(args, dev, truth, photos, table, hidden, weights=None, cameras=None, reg
             with torch.no_grad():
                 scenes = table if pos is None else torch.cat((pos, colour), dim=-1)
                 if log_e is not None:
-                    scenes = torch.cat((scenes[..., :6], scenes[..., 6:] * log_e.exp()), dim=-1)
+                    scenes = losses.fold_exposure(scenes, log_e.exp())
             photos, weights = registration.refine(x, scenes)
             unseen = weights.amax(dim=1, keepdim=True) == 0
             print("step %4d  registration stage: mean corner error %.3f px%s" % (step, registration.error(), registration.lens_text()))
