@@ -13,6 +13,14 @@ namespace {
 
 inline int fail(int code, const char *what) { return svbrdf_internal_fail(code, what); }
 
+// the error reported as "<who>: <what>", who being the entry
+inline int fail_as(const char *who, int code, const char *what)
+{
+    char text[200];
+    std::snprintf(text, sizeof(text), "%s: %s", who, what);
+    return fail(code, text);
+}
+
 inline int check_dims(int B, int S, int H, int W)
 {
     if (B <= 0 || S <= 0 || H <= 0 || W <= 0) return fail(SVBRDF_ERR_DIMS, "B, S, H, W must be positive");

@@ -71,13 +71,9 @@ __device__ __forceinline__ void exposure_body(const float *__restrict__ input, c
         else
             lsum = photo_scene_loop<3, true, 3, WEIGHTED, true>(ps.mi, ps.x, ps.y, scp, nullptr, pp, plane, wi.pix, S, eps,
                                                                 inv_count, ps.acc, wp, wstride, ps.poison, &xl, gain);
-        // the item's gains, a lane each: one that is NaN, infinite or <= 0 makes the loss sum NaN, whatever the weights.
-        // (Behind the scene loop: in front of it these vector loads keep the loop's own loads of the gains from being
-        // scalar loads.)
-        for (int i = threadIdx.x & 63; i < n_sums; i += 64) {
-            const float e = gain[i];
-            if (!(e > 0.0f && e < __builtin_inff())) lsum = __builtin_nanf("");
-        }
+        // the item's gains.  (Behind the scene loop: in front of it these vector loads keep the loop's own loads of the gains
+        // from being scalar loads.)
+        positive_check(gain, 3, 0, S, lsum);
         if (wi.live) {
             if (HEAD) store_pixel_grad<true>(ps.head, ps.acc, grad_input, b, plane, wi.pix);
             else store_grads_k3(grad_input + (size_t)b * 12 * plane, plane, wi.pix, ps.acc);

@@ -27,8 +27,8 @@
 //   * the clamp is two compares and selects: a NaN stays a NaN (v_max / v_min would return the bound), +-inf bounds never
 //     select.
 // The three fit entries -- this unit's two and the joint unit's -- check their weights and turn (bounds, lr, betas, adam_eps,
-// step) into AdamArgs through one helper each (fit_weights_check, adam_args) and report through fit_bad.
-// The update, the step's body and those helpers are in svbrdf_photo_fit_device.h, which the joint and the smooth units
+// step) into AdamArgs through one helper each (weights_check of svbrdf_photo_loss_device.h, adam_args) and report through
+// fail_as.  The update, the step's body and adam_args are in svbrdf_photo_fit_device.h, which the joint and the smooth units
 // include too; this file holds the kernels of the single step and of several steps, and their entry points.
 #include "svbrdf_photo_fit_device.h"
 
@@ -117,16 +117,9 @@ __device__ __forceinline__ void fit_run_body(float *maps, float *exp_avg, float 
         for (int k = 0; k < 12; ++k) run_put(12 + k, first, plane_load(mb, k));
 #pragma unroll
         for (int k = 0; k < 12; ++k) run_put(24 + k, first, plane_load(vb, k));
-        // the pixel's coordinates, as wave_pixel_setup finds them
-        float x[1];
-        if ((W & (W - 1)) == 0) {
-            const unsigned p32 = (unsigned)pix, sh = (unsigned)__builtin_ctz((unsigned)W);
-            x[0] = xrow[p32 & (unsigned)(W - 1)];
-            y = -xrow[p32 >> sh];
-        } else {
-            pixel_coords<1>(xrow, pix, W, x, y);
-        }
-        run_put(36, first, x[0]);
+        float x;
+        pixel_xy(xrow, pix, W, (W & (W - 1)) == 0, x, y);
+        run_put(36, first, x);
     }
 #pragma clang loop unroll(disable)
     for (int step = 0; step < n_steps; ++step) {
@@ -154,12 +147,7 @@ __device__ __forceinline__ void fit_run_body(float *maps, float *exp_avg, float 
 #pragma unroll
             for (int k = 0; k < 3; ++k) mi.r4m[k] = 1.0f;
             float x = run_take(36, top);
-            const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
-            x += chk - chk;
-            if (WEIGHTED) {
-                const float ds = ((in.d[0] + in.d[1]) + (in.d[2] + in.s[0])) + (in.s[1] + in.s[2]);
-                poison = (chk - chk) + (ds - ds);
-            }
+            maps_guard<WEIGHTED>(in, x, poison);
             // The scene table through the CONSTANT address space -- no kernel writes it -- so that its wave-uniform loads are
             // scalar loads whatever stands around them.  Through the global one the compiler must first prove that nothing in
             // front of a load clobbers it; with the step loop around the scene loops it gives up, loads the rows of every pass
@@ -269,7 +257,7 @@ int svbrdf_photo_fit_adam_step(float *maps, float *exp_avg, float *exp_avg_sq, c
     // (grad_out may be null and the kernels are forward + adjoint whatever it is: the plan is the one with a gradient)
     if (int e = plan_loss(who, false, {maps, exp_avg, exp_avg_sq, photos, scenes, xrow, loss_out}, grad_out ? grad_out : maps,
                           workspace, workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    if (int e = fit_weights_check(who, weights, weight_planes, S)) return e;
+    if (int e = weights_check(who, weights, weight_planes, S)) return e;
     AdamArgs a;
     if (int e = adam_args(who, kStepRule, bounds_host, lr, beta1, beta2, adam_eps, step, &a)) return e;
     hipLaunchKernelGGL(weights ? k_fit_maps_weighted : k_fit_maps, p.grid, dim3(kLossThreads), 0,
@@ -296,16 +284,16 @@ int svbrdf_photo_fit_adam_steps(float *maps, float *exp_avg, float *exp_avg_sq, 
     // the single step's checks in its order (a workspace below ONE step's 65 words fails here already)
     if (int e = plan_loss(who, false, {maps, exp_avg, exp_avg_sq, photos, scenes, xrow, losses_out}, maps, workspace,
                           workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    if (int e = fit_weights_check(who, weights, weight_planes, S)) return e;
+    if (int e = weights_check(who, weights, weight_planes, S)) return e;
     if (n_steps < 1 || n_steps > SVBRDF_PHOTO_FIT_MAX_STEPS)
-        return fit_bad(who, SVBRDF_ERR_DIMS, "n_steps must lie in [1, SVBRDF_PHOTO_FIT_MAX_STEPS]");
+        return fail_as(who, SVBRDF_ERR_DIMS, "n_steps must lie in [1, SVBRDF_PHOTO_FIT_MAX_STEPS]");
     AdamArgs a;
     RunScalars run;
     float sc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     for (int k = 0; k < SVBRDF_PHOTO_FIT_MAX_STEPS; ++k) {
         // (first_step + k cannot wrap where it is used: k < n_steps <= 64, and a first_step that close to INT_MAX is no fit's)
         if (k < n_steps && (first_step > 0x7fffffff - k || !adam_scalars(lr, beta1, beta2, first_step + k, sc)))
-            return fit_bad(who, SVBRDF_ERR_DIMS, rule);
+            return fail_as(who, SVBRDF_ERR_DIMS, rule);
         run.step_size[k] = sc[2];       // (behind n_steps: the last step's, never read)
         run.rsb2[k] = sc[3];
     }
@@ -314,7 +302,7 @@ int svbrdf_photo_fit_adam_steps(float *maps, float *exp_avg, float *exp_avg_sq, 
     a.step_size = 0.0f;
     a.rsb2 = 0.0f;
     if (workspace_bytes < svbrdf_photo_fit_steps_workspace_bytes(n_steps, B, S, H, W))
-        return fit_bad(who, SVBRDF_ERR_WORKSPACE, "workspace too small for n_steps (svbrdf_photo_fit_steps_workspace_bytes)");
+        return fail_as(who, SVBRDF_ERR_WORKSPACE, "workspace too small for n_steps (svbrdf_photo_fit_steps_workspace_bytes)");
     hipLaunchKernelGGL(weights ? k_fit_run_weighted : k_fit_run, p.grid, dim3(kLossThreads), 0,
                        static_cast<hipStream_t>(stream), maps, exp_avg, exp_avg_sq, photos, weights, weight_planes, scenes,
                        xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, a, run, n_steps, p.ws, losses_out, S, H, W);

@@ -147,39 +147,23 @@ bool adam_scalars(float lr, float beta1, float beta2, int step, float out[4])
     return true;
 }
 
-// What the three fit entries check and fill alike, each in its own order -> 0, or the error reported as "<who>: <what>"
-int fit_bad(const char *who, int code, const char *what)
-{
-    char text[200];
-    std::snprintf(text, sizeof(text), "%s: %s", who, what);
-    return fail(code, text);
-}
-
-// (the joint entry's weights are checked by plan_sums)
-[[maybe_unused]] int fit_weights_check(const char *who, const float *weights, int weight_planes, int S)
-{
-    if (!aligned(weights, 4)) return fit_bad(who, SVBRDF_ERR_ALIGN, "pointers must be 4-byte aligned");
-    if (weights ? (weight_planes != 1 && weight_planes != S) : weight_planes != 0)
-        return fit_bad(who, SVBRDF_ERR_DIMS,
-                       "weight_planes must be 1 (one plane per item) or S (one per photo) with weights, 0 without");
-    return 0;
-}
-
+// What the fit entries check and fill alike, each in its own order -> 0, or the error reported (fail_as).  Their weights:
+// weights_check of svbrdf_photo_loss_device.h, called by the entry or by its plan_sums.
 // The update's arguments of Adam's step `step`: the scalars (`scalars_rule`: the entry's wording of what they require),
 // adam_eps, the seven scalars, then the 12 bounds -- +-inf without bounds_host
 int adam_args(const char *who, const char *scalars_rule, const float *bounds_host, float lr, float beta1, float beta2,
               float adam_eps, int step, AdamArgs *a)
 {
     float sc[4];
-    if (!adam_scalars(lr, beta1, beta2, step, sc)) return fit_bad(who, SVBRDF_ERR_DIMS, scalars_rule);
+    if (!adam_scalars(lr, beta1, beta2, step, sc)) return fail_as(who, SVBRDF_ERR_DIMS, scalars_rule);
     if (!(adam_eps >= 0.0f) || !std::isfinite(adam_eps))
-        return fit_bad(who, SVBRDF_ERR_DIMS, "adam_eps must be finite and >= 0");
+        return fail_as(who, SVBRDF_ERR_DIMS, "adam_eps must be finite and >= 0");
     a->beta1 = beta1; a->c1 = sc[0]; a->beta2 = beta2; a->c2 = sc[1]; a->step_size = sc[2]; a->rsb2 = sc[3]; a->adam_eps = adam_eps;
     for (int k = 0; k < 12; ++k) {
         a->lo[k] = bounds_host ? bounds_host[2 * k] : -__builtin_inff();
         a->hi[k] = bounds_host ? bounds_host[2 * k + 1] : __builtin_inff();
         if (!(a->lo[k] <= a->hi[k]))
-            return fit_bad(who, SVBRDF_ERR_DIMS, "bounds must hold lo <= hi for every channel, and no NaN");
+            return fail_as(who, SVBRDF_ERR_DIMS, "bounds must hold lo <= hi for every channel, and no NaN");
     }
     return 0;
 }

@@ -77,7 +77,7 @@ int svbrdf_photo_fit_adam_step_scene_grad(float *maps, float *exp_avg, float *ex
     // fit_stash's six words per thread stand beside the rows of sums: the workgroup's LDS stays inside what plan_sums
     // allows the scene-gradient kernels (60 KB of rows), S <= 383
     if (p.lds_bytes + 6 * kLossThreads * sizeof(float) > 60 * 1024)
-        return fit_bad(who, SVBRDF_ERR_DIMS, "too many scenes per item for the LDS sums (max 383)");
+        return fail_as(who, SVBRDF_ERR_DIMS, "too many scenes per item for the LDS sums (max 383)");
     AdamArgs a;
     if (int e = adam_args(who, kStepRule, bounds_host, lr, beta1, beta2, adam_eps, step, &a)) return e;
     hipLaunchKernelGGL(weights ? k_joint_fit_weighted : k_joint_fit, p.grid, dim3(kLossThreads), p.lds_bytes,

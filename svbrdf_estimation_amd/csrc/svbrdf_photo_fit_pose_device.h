@@ -48,11 +48,7 @@ __device__ __forceinline__ void joint_body(float *maps, float *exp_avg, float *e
         else
             lsum = pose_scene_loop<3, WEIGHTED>(ps.mi, ps.x, ps.y, scp, pp, plane, wi.pix, S, eps, inv_count, ps.acc, wp,
                                                 wstride, ps.poison, wi.row, wi.live);
-        // the item's light colours, a lane each (pose_body)
-        for (int i = threadIdx.x & 63; i < 3 * S; i += 64) {
-            const float c = scp[(i / 3) * 9 + 6 + i % 3];
-            if (!(c > 0.0f && c < __builtin_inff())) lsum = __builtin_nanf("");
-        }
+        positive_check(scp, 9, 6, S, lsum);         // the item's light colours
         if (wi.live) {
             // the fit step's update, for the lanes that own a pixel ONLY
             if constexpr (Update::in_place) {

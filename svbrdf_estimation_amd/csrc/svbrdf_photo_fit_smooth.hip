@@ -250,15 +250,15 @@ SVBRDF_SMOOTH_JOINT_KERNEL(k_smooth_joint_weighted, true)
 int smooth_args(const char *who, const float *smooth_host, const float *maps_in, const float *maps_out, int B, int H, int W,
                 SmoothArgs *s)
 {
-    if (!smooth_host) return fit_bad(who, SVBRDF_ERR_DIMS, "smooth_host (12 floats on the host) is required");
+    if (!smooth_host) return fail_as(who, SVBRDF_ERR_DIMS, "smooth_host (12 floats on the host) is required");
     for (int k = 0; k < 12; ++k)
         if (!(smooth_host[k] >= 0.0f) || !std::isfinite(smooth_host[k]))
-            return fit_bad(who, SVBRDF_ERR_DIMS, "smooth_host must hold 12 finite values >= 0");
+            return fail_as(who, SVBRDF_ERR_DIMS, "smooth_host must hold 12 finite values >= 0");
     if (maps_in && maps_out && B > 0 && H > 0 && W > 0) {
         const unsigned __int128 bytes = (unsigned __int128)B * 12u * (unsigned)H * (unsigned)W * sizeof(float);
         const unsigned long long a = (unsigned long long)(uintptr_t)maps_in, o = (unsigned long long)(uintptr_t)maps_out;
         if ((a > o ? a - o : o - a) < bytes)
-            return fit_bad(who, SVBRDF_ERR_DIMS, "maps_in and maps_out must not overlap (the step is out of place)");
+            return fail_as(who, SVBRDF_ERR_DIMS, "maps_in and maps_out must not overlap (the step is out of place)");
     }
     const double count = (double)B * (double)H * (double)W;
     for (int k = 0; k < 12; ++k) s->c[k] = count > 0.0 ? (float)((double)smooth_host[k] / count) : 0.0f;
@@ -283,7 +283,7 @@ int svbrdf_photo_fit_smooth_adam_step(const float *maps_in, float *maps_out, flo
     // svbrdf_photo_fit_adam_step's checks in its order
     if (int e = plan_loss(who, false, {maps_in, maps_out, exp_avg, exp_avg_sq, photos, scenes, xrow, loss_out},
                           grad_out ? grad_out : maps_in, workspace, workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    if (int e = fit_weights_check(who, weights, weight_planes, S)) return e;
+    if (int e = weights_check(who, weights, weight_planes, S)) return e;
     AdamArgs a;
     if (int e = adam_args(who, kStepRule, bounds_host, lr, beta1, beta2, adam_eps, step, &a)) return e;
     hipLaunchKernelGGL(weights ? k_smooth_step_weighted : k_smooth_step, p.grid, dim3(kLossThreads), 0,
@@ -311,7 +311,7 @@ int svbrdf_photo_fit_smooth_adam_step_scene_grad(const float *maps_in, float *ma
                           weight_planes, nullptr, eps, grad_out ? grad_out : maps_in, workspace, workspace_bytes, 9,
                           kPoseSpill, B, S, H, W, &p, &units)) return e;
     if (p.lds_bytes + 6 * kLossThreads * sizeof(float) > 60 * 1024)
-        return fit_bad(who, SVBRDF_ERR_DIMS, "too many scenes per item for the LDS sums (max 383)");
+        return fail_as(who, SVBRDF_ERR_DIMS, "too many scenes per item for the LDS sums (max 383)");
     AdamArgs a;
     if (int e = adam_args(who, kStepRule, bounds_host, lr, beta1, beta2, adam_eps, step, &a)) return e;
     hipLaunchKernelGGL(weights ? k_smooth_joint_weighted : k_smooth_joint, p.grid, dim3(kLossThreads), p.lds_bytes,

@@ -105,18 +105,9 @@ int photo_grad_impl(const char *who, bool head, const float *input, const float 
                     int W, void *stream)
 {
     LossPlan p;
-    char text[200];
     if (int e = plan_loss(who, false, {input, photos, scenes, xrow, loss_out, grad_photos}, grad_input, workspace,
                           workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    if (!aligned(weights, 4)) {
-        std::snprintf(text, sizeof(text), "%s: pointers must be 4-byte aligned", who);
-        return fail(SVBRDF_ERR_ALIGN, text);
-    }
-    if (weights ? (weight_planes != 1 && weight_planes != S) : weight_planes != 0) {
-        std::snprintf(text, sizeof(text),
-                      "%s: weight_planes must be 1 (one plane per item) or S (one per photo) with weights, 0 without", who);
-        return fail(SVBRDF_ERR_DIMS, text);
-    }
+    if (int e = weights_check(who, weights, weight_planes, S)) return e;
     const auto launch = [&](auto kernel) {
         hipLaunchKernelGGL(kernel, p.grid, dim3(kLossThreads), p.lds_bytes, static_cast<hipStream_t>(stream), input, photos,
                            weights, weight_planes, scenes, xrow, eps, p.inv_count, p.loss_scale, p.fixed_scale, grad_input,

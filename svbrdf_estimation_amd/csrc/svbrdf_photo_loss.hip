@@ -149,11 +149,9 @@ int photo_impl(const char *who, bool scenes_on_host, bool head, bool weighted, c
                           weighted ? Required{input, photos, weights, scenes, xrow, loss_out}
                                    : Required{input, photos, scenes, xrow, loss_out},
                           grad_input, workspace, workspace_bytes, "eps", eps, 0.0f, B, S, H, W, &p)) return e;
-    if (weighted && weight_planes != 1 && weight_planes != S) {
-        char text[200];
-        std::snprintf(text, sizeof(text), "%s: weight_planes must be 1 (one plane per item) or S (one per photo)", who);
-        return fail(SVBRDF_ERR_DIMS, text);
-    }
+    // (the weighted entries' weights passed plan_loss, non-null and aligned; the others pass none and 0 planes)
+    if (int e = weights_check(who, weights, weight_planes, S, "weight_planes must be 1 (one plane per item) or S (one per photo)"))
+        return e;
     static constexpr decltype(&launch_photo<false, false, false>) kLaunch[2][2][2] = {     // [weighted][head][gradient]
         {{launch_photo<false, false, false>, launch_photo<true, false, false>},
          {launch_photo<false, true, false>, launch_photo<true, true, false>}},

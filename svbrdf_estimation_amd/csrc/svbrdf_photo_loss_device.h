@@ -560,6 +560,79 @@ __device__ __forceinline__ float photo_scene_loop(const MapK &mi, float x, float
     return lsum;
 }
 
+// ---- The small pieces every photo body is made of, each written once. ----
+
+// The guard against non-finite maps, the numerics contract of every photo kernel: a NaN or infinite normal / roughness
+// value would vanish in the clamps (v_max returns the other operand), so t - t -- 0 for finite t and NaN otherwise -- is
+// added to the pixel's x coordinate (rendering_loss_body).  Diffuse, specular and the photo values propagate through the
+// arithmetic by themselves.  WEIGHTED: a zero weight deselects the shading's value, so the diffuse and specular planes are
+// guarded too and `poison` (+0 for finite maps, NaN otherwise) starts the pixel's loss sum: a weight does not excuse the
+// maps.
+template <bool WEIGHTED>
+__device__ __forceinline__ void maps_guard(const Maps &in, float &x, float &poison)
+{
+    const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
+    x += chk - chk;
+    if (WEIGHTED) {
+        const float ds = ((in.d[0] + in.d[1]) + (in.d[2] + in.s[0])) + (in.s[1] + in.s[2]);
+        poison = (chk - chk) + (ds - ds);
+    }
+}
+// HEAD: the same guard from the 9 encoded values, formed where they are loaded -> what head_guard_apply adds to x where
+// maps_guard stands.  The values that feed the normal and the roughness each on their own: a sum of large finite values
+// must not overflow into a NaN report.  WEIGHTED: the diffuse and specular planes too (their way through the arithmetic
+// ends at a select).
+template <bool WEIGHTED>
+__device__ __forceinline__ float head_guard(const float e[9], float &poison)
+{
+    const float head_chk = ((e[0] - e[0]) + (e[1] - e[1])) + (e[5] - e[5]);
+    if (WEIGHTED)
+        poison = (((e[2] - e[2]) + (e[3] - e[3])) + ((e[4] - e[4]) + (e[6] - e[6]))) + ((e[7] - e[7]) + (e[8] - e[8]));
+    return head_chk;
+}
+template <bool WEIGHTED>
+__device__ __forceinline__ void head_guard_apply(float head_chk, float &x, float &poison)
+{
+    x += head_chk;
+    if (WEIGHTED) poison += head_chk;
+}
+
+// The pixel's coordinates: a shift and a mask for a power-of-two width, pixel_coords' division otherwise.  `pow2`:
+// (W & (W - 1)) == 0, formed by the caller -- photo_loss_body forms it in front of its plane loads, for its early
+// coordinates, and formed here instead it moves the scalar code of six kernels of svbrdf_photo_loss.hip.
+__device__ __forceinline__ void pixel_xy(const float *xrow, size_t pix, int W, bool pow2, float &x, float &y)
+{
+    if (pow2) {
+        const unsigned p32 = (unsigned)pix, sh = (unsigned)__builtin_ctz((unsigned)W);
+        x = xrow[p32 & (unsigned)(W - 1)];
+        y = -xrow[p32 >> sh];
+    } else {
+        float xs[1];
+        pixel_coords<1>(xrow, pix, W, xs, y);
+        x = xs[0];
+    }
+}
+
+// (NOT among them: the item's base pointers scp, pp, wp, wstride, four lines that every body writes out.  As one function
+// that returns them, the same expressions in the same order, the compiler schedules the scalar address arithmetic otherwise:
+// loops with transcendentals of seven kernels carried other registers and the joint kernels gained an instruction --
+// profiles/r29_photo_shared_pieces.txt.  Nor the twelve-line loss tail of photo_loss_body, photo_grad_body and fit_body: as
+// one function it moved two instruction lines in each of the 28 kernels, and against the parent's library the photo-gradient
+// launch with both gradients then took 51.02 us where 50.68 + 0.06 were allowed, and PhotoFit(smooth=).step 84.52 us where
+// 82.06 + 0.66 were: the same record.)
+
+// The item's 3 S values p[stride s + first + k], a lane each: one that is NaN, infinite or <= 0 makes the loss sum NaN,
+// whatever the weights.  The light colours of the scene-gradient kernels (stride 9, from column 6: the colour gradient
+// divides by them) and the gains of the exposure kernels (stride 3, from 0: the compiler folds the index to i, and their
+// kernels keep their machine code).
+__device__ __forceinline__ void positive_check(const float *p, int stride, int first, int S, float &lsum)
+{
+    for (int i = threadIdx.x & 63; i < 3 * S; i += 64) {
+        const float v = p[(i / 3) * stride + first + i % 3];
+        if (!(v > 0.0f && v < __builtin_inff())) lsum = __builtin_nanf("");
+    }
+}
+
 // One thread = one pixel, all S renders of it; workgroup = 256 pixels of one batch item (as K3).
 // HEAD: `input` is the generator's [B,9,H,W] post-tanh output and `grad_input` its gradient: the network head
 // (decode_head / head_bwd, K3's own: svbrdf_head_loss_fwd_bwd) is folded in, 9 planes in and 9 out instead of 12 and 12.
@@ -587,13 +660,14 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
         __syncthreads();
     }
     if (active) {
-        // (the set-up of a pixel, down to the guards on x and `poison`, stands a second time in wave_pixel_setup below: a
-        // change to the loads or the guards is made in both)
+        // (the ORDER of a pixel's set-up -- loads, decode, prepare, coordinates, guard -- stands a second time in
+        // wave_pixel_setup below, which says why; the guard and the coordinates themselves are maps_guard's, head_guard's
+        // and pixel_xy's, once)
         Maps in;
         Grad acc;
         [[maybe_unused]] Head head;
         [[maybe_unused]] float head_chk = 0.0f;
-        [[maybe_unused]] float poison = 0.0f;       // WEIGHTED: +0 for finite maps, NaN otherwise; added to the loss sum
+        [[maybe_unused]] float poison = 0.0f;       // WEIGHTED: maps_guard's, added to the loss sum
         // pixel coordinates issued in front of the plane loads (by-value-table kernels, power-of-two width): see
         // rendering_loss_body
         [[maybe_unused]] float x_early = 0.0f, y_early = 0.0f;
@@ -611,60 +685,33 @@ __device__ __forceinline__ void photo_loss_body(const float *__restrict__ input,
 #pragma unroll
             for (int k = 0; k < 9; ++k) e[k] = plane_load(pb, k);
             head = decode_head(e, in);
-            // the guard below, from the encoded values that feed the normal and the roughness (each on its own: a sum
-            // of large finite values must not overflow into a NaN report)
-            head_chk = ((e[0] - e[0]) + (e[1] - e[1])) + (e[5] - e[5]);
-            if (WEIGHTED)       // the diffuse and specular planes too: their way through the arithmetic ends at a select
-                poison = (((e[2] - e[2]) + (e[3] - e[3])) + ((e[4] - e[4]) + (e[6] - e[6]))) + ((e[7] - e[7]) + (e[8] - e[8]));
+            head_chk = head_guard<WEIGHTED>(e, poison);
         } else {
             load_maps_k3(input + (size_t)b * 12 * plane, plane, pix, in);
         }
         zero_grad(acc);
         const bool tied = HEAD || tied_roughness(in);
         const MapK mi = prepare<WITH_GRAD>(in);
-        float x[1], y;
+        float x, y;
         if (early_coords) {
-            x[0] = x_early;
+            x = x_early;
             y = -y_early;
-        } else if (pow2) {
-            const unsigned p32 = (unsigned)pix, sh = (unsigned)__builtin_ctz((unsigned)W);
-            x[0] = xrow[p32 & (unsigned)(W - 1)];
-            y = -xrow[p32 >> sh];
         } else {
-            pixel_coords<1>(xrow, pix, W, x, y);
+            pixel_xy(xrow, pix, W, pow2, x, y);
         }
-        {
-            // a NaN or infinite normal / roughness value would vanish in the clamps (v_max returns the other operand):
-            // t - t is 0 for finite t and NaN otherwise, added to the pixel's x coordinate (rendering_loss_body).  Diffuse,
-            // specular and the photo values propagate through the arithmetic by themselves.
-            if (HEAD) {
-                x[0] += head_chk;
-                if (WEIGHTED) poison += head_chk;
-            } else {
-                const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
-                x[0] += chk - chk;
-                if (WEIGHTED) {
-                    const float ds = ((in.d[0] + in.d[1]) + (in.d[2] + in.s[0])) + (in.s[1] + in.s[2]);
-                    poison = (chk - chk) + (ds - ds);
-                }
-            }
-        }
+        if (HEAD) head_guard_apply<WEIGHTED>(head_chk, x, poison);
+        else maps_guard<WEIGHTED>(in, x, poison);
         const float *__restrict__ scp = scenes + (size_t)b * S * 9;
         const float *__restrict__ pp = photos + (size_t)b * S * 3 * plane;
+        const float *__restrict__ wp = WEIGHTED ? weights + (size_t)b * weight_planes * plane : nullptr;
+        const size_t wstride = weight_planes == 1 ? 0 : plane;
         constexpr int kDefer = WITH_GRAD ? 7 : 0;
-        if (WEIGHTED) {
-            const float *__restrict__ wp = weights + (size_t)b * weight_planes * plane;
-            const size_t wstride = weight_planes == 1 ? 0 : plane;
-            if (HEAD || __all(tied))
-                lsum = photo_scene_loop<1, WITH_GRAD, kDefer, true>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps,
-                                                                    inv_count, acc, wp, wstride, poison);
-            else
-                lsum = photo_scene_loop<3, WITH_GRAD, kDefer & 3, true>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps,
-                                                                        inv_count, acc, wp, wstride, poison);
-        } else if (HEAD || __all(tied))     // wave-uniform
-            lsum = photo_scene_loop<1, WITH_GRAD, kDefer>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc);
+        if (HEAD || __all(tied))        // wave-uniform
+            lsum = photo_scene_loop<1, WITH_GRAD, kDefer, WEIGHTED>(mi, x, y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc,
+                                                                    wp, wstride, poison);
         else
-            lsum = photo_scene_loop<3, WITH_GRAD, kDefer & 3>(mi, x[0], y, scp, sc_lds, pp, plane, pix, S, eps, inv_count, acc);
+            lsum = photo_scene_loop<3, WITH_GRAD, kDefer & 3, WEIGHTED>(mi, x, y, scp, sc_lds, pp, plane, pix, S, eps, inv_count,
+                                                                        acc, wp, wstride, poison);
         if (WITH_GRAD) {
             if (HEAD) store_pixel_grad<true>(head, acc, grad_input, b, plane, pix);
             else store_grads_k3(grad_input + (size_t)b * 12 * plane, plane, pix, acc);
@@ -710,9 +757,12 @@ struct WaveIndex {
 }
 
 // The set-up of a pixel: photo_loss_body<true, false, HEAD, WEIGHTED>'s statements from the plane loads to the guards on x
-// and `poison`, in its source order (the order the scheduler sees), where its comments are.  It stands TWICE: sharing this
-// function with photo_loss_body gave six of the eight head kernels of svbrdf_photo_loss.hip other machine code (same size, other
-// bytes).  A change to the loads or the guards is made here and there.
+// and `poison`, in its source order (the order the scheduler sees).  What is SHARED with that body: the guards (maps_guard,
+// head_guard) and the coordinates (pixel_xy), each written once above.  What is NOT: the order of the statements around them
+// stands twice.  photo_loss_body on a generalised wave_pixel_setup<HEAD, WEIGHTED, WITH_GRAD, EARLY> was tried (compiled
+// only, profiles/r29_photo_shared_pieces.txt): all 16 kernels of svbrdf_photo_loss.hip moved, 7 with altered scene loops, and the by-value forward +
+// adjoint kernels gained 11-12 instructions and 3 VALU; round 16's decision stands.  A change to the order of the loads
+// is made here and there.
 struct PixelSetup {
     MapK mi;
     Grad acc;       // zeroed
@@ -734,35 +784,16 @@ __device__ __forceinline__ PixelSetup wave_pixel_setup(const float *__restrict__
 #pragma unroll
         for (int k = 0; k < 9; ++k) e[k] = plane_load(pb, k);
         ps.head = decode_head(e, in);
-        head_chk = ((e[0] - e[0]) + (e[1] - e[1])) + (e[5] - e[5]);
-        if (WEIGHTED)
-            ps.poison = (((e[2] - e[2]) + (e[3] - e[3])) + ((e[4] - e[4]) + (e[6] - e[6]))) + ((e[7] - e[7]) + (e[8] - e[8]));
+        head_chk = head_guard<WEIGHTED>(e, ps.poison);
     } else {
         load_maps_k3(input + (size_t)b * 12 * plane, plane, pix, in);
     }
     zero_grad(ps.acc);
     ps.tied = HEAD || tied_roughness(in);
     ps.mi = prepare<true>(in);
-    float x[1];
-    if ((W & (W - 1)) == 0) {
-        const unsigned p32 = (unsigned)pix, sh = (unsigned)__builtin_ctz((unsigned)W);
-        x[0] = xrow[p32 & (unsigned)(W - 1)];
-        ps.y = -xrow[p32 >> sh];
-    } else {
-        pixel_coords<1>(xrow, pix, W, x, ps.y);
-    }
-    if (HEAD) {
-        x[0] += head_chk;
-        if (WEIGHTED) ps.poison += head_chk;
-    } else {
-        const float chk = ((in.n[0] + in.n[1]) + (in.n[2] + in.r[0])) + (in.r[1] + in.r[2]);
-        x[0] += chk - chk;
-        if (WEIGHTED) {
-            const float ds = ((in.d[0] + in.d[1]) + (in.d[2] + in.s[0])) + (in.s[1] + in.s[2]);
-            ps.poison = (chk - chk) + (ds - ds);
-        }
-    }
-    ps.x = x[0];
+    pixel_xy(xrow, pix, W, (W & (W - 1)) == 0, ps.x, ps.y);
+    if (HEAD) head_guard_apply<WEIGHTED>(head_chk, ps.x, ps.poison);
+    else maps_guard<WEIGHTED>(in, ps.x, ps.poison);
     return ps;
 }
 
@@ -829,27 +860,36 @@ __device__ __forceinline__ void photo_sums_finish(float lsum, int b, int n_sums,
     const size_t sums = (B > 0 && S > 0) ? (size_t)B * (size_t)S * per_scene : 0;
     return svbrdf_rendering_loss_workspace_bytes(B, S, H, W) + sums * sizeof(unsigned long long);
 }
+// The weights of every photo and fit entry, behind plan_loss: an optional pointer (4-byte aligned), `weight_planes` 1 or S
+// with it and 0 without.  (`rule`: the eight oldest entries, whose weights are among plan_loss's required pointers, word it
+// shorter.  kAlignRule is the sentence for the pointers plan_loss does not see -- plan_loss's own, in svbrdf_host.h, names
+// the workspace too and is another text.)
+constexpr const char *kAlignRule = "pointers must be 4-byte aligned";
+constexpr const char *kWeightsRule = "weight_planes must be 1 (one plane per item) or S (one per photo) with weights, 0 without";
+[[maybe_unused]] int weights_check(const char *who, const float *weights, int weight_planes, int S,
+                                   const char *rule = kWeightsRule)
+{
+    if (!aligned(weights, 4)) return fail_as(who, SVBRDF_ERR_ALIGN, kAlignRule);
+    if (weights ? (weight_planes != 1 && weight_planes != S) : weight_planes != 0) return fail_as(who, SVBRDF_ERR_DIMS, rule);
+    return 0;
+}
 [[maybe_unused]] int plan_sums(const char *who, std::initializer_list<const void *> required, const float *weights,
                                int weight_planes, const float *optional_out, float eps, const float *grad_input,
                                void *workspace, size_t workspace_bytes, int per_scene, int spill, int B, int S, int H, int W,
                                LossPlan *p, double *units)
 {
     constexpr size_t kRowBytes = kLossThreads / 64 * sizeof(float), kLdsMax = 60 * 1024;
-    char text[200], lds_text[80];
-    const auto bad = [&](int code, const char *what) {
-        std::snprintf(text, sizeof(text), "%s: %s", who, what);
-        return fail(code, text);
-    };
+    char lds_text[80];
     if (!grad_input) return fail(SVBRDF_ERR_NULL, who);      // forward + adjoint only
     if (int e = plan_loss(who, false, required, grad_input, workspace, workspace_bytes, "eps", eps, 0.0f, B, S, H, W, p)) return e;
-    if (!aligned(weights, 4) || !aligned(optional_out, 4)) return bad(SVBRDF_ERR_ALIGN, "pointers must be 4-byte aligned");
-    if (weights ? (weight_planes != 1 && weight_planes != S) : weight_planes != 0)
-        return bad(SVBRDF_ERR_DIMS, "weight_planes must be 1 (one plane per item) or S (one per photo) with weights, 0 without");
-    if (workspace_bytes < sums_workspace_bytes(per_scene, B, S, H, W)) return bad(SVBRDF_ERR_WORKSPACE, "workspace too small");
+    if (!aligned(optional_out, 4)) return fail_as(who, SVBRDF_ERR_ALIGN, kAlignRule);
+    if (int e = weights_check(who, weights, weight_planes, S)) return e;
+    if (workspace_bytes < sums_workspace_bytes(per_scene, B, S, H, W))
+        return fail_as(who, SVBRDF_ERR_WORKSPACE, "workspace too small");
     p->lds_bytes = kRowBytes * (spill + (size_t)S * per_scene);
     std::snprintf(lds_text, sizeof(lds_text), "too many scenes per item for the LDS sums (max %d)",
                   (int)((kLdsMax / kRowBytes - spill) / per_scene));
-    if (p->lds_bytes > kLdsMax) return bad(SVBRDF_ERR_DIMS, lds_text);
+    if (p->lds_bytes > kLdsMax) return fail_as(who, SVBRDF_ERR_DIMS, lds_text);
     *units = (double)B * S * 3.0 * (double)H * W * (double)kExpoFixedScale;
     return 0;
 }

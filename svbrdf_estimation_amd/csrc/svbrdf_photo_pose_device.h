@@ -127,12 +127,7 @@ __device__ __forceinline__ void pose_body(const float *__restrict__ input, const
         else
             lsum = pose_scene_loop<3, WEIGHTED>(ps.mi, ps.x, ps.y, scp, pp, plane, wi.pix, S, eps, inv_count, ps.acc, wp,
                                                 wstride, ps.poison, wi.row, wi.live);
-        // the item's light colours, a lane each: one that is NaN, infinite or <= 0 makes the loss sum NaN (the rule of the
-        // exposure gains: the colour gradient divides by it)
-        for (int i = threadIdx.x & 63; i < 3 * S; i += 64) {
-            const float c = scp[(i / 3) * 9 + 6 + i % 3];
-            if (!(c > 0.0f && c < __builtin_inff())) lsum = __builtin_nanf("");
-        }
+        positive_check(scp, 9, 6, S, lsum);         // the item's light colours
         if (wi.live) {
             if (HEAD) store_pixel_grad<true>(ps.head, ps.acc, grad_input, b, plane, wi.pix);
             else store_grads_k3(grad_input + (size_t)b * 12 * plane, plane, wi.pix, ps.acc);

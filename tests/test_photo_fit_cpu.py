@@ -300,4 +300,6 @@ def test_source_holds_no_inline_assembly_with_instructions_and_no_fma():
     assert code.count("adam_channel(") == 3
     # and so do the checks of the weights and of the Adam arguments: one definition, every entry calls it
     assert "const auto bad" not in code and code.count("bounds_host[2 * k]") == 1 and code.count("adam_eps must be") == 1
-    assert code.count("fit_weights_check(who,") == 2 and code.count("adam_args(who,") == 2
+    # (the weights' check is every photo entry's: svbrdf_photo_loss_device.h, tests/test_photo_loss_cpu.py)
+    assert code.count("weights_check(who,") == 2 and code.count("adam_args(who,") == 2 and "int weights_check(" not in code
+    assert "snprintf" not in code and "fail_as(who," in code

@@ -427,8 +427,8 @@ def test_source_reuses_the_two_flows_and_holds_one_update():
     joint = unit_build.assert_includes_shared_header(UNIT, "svbrdf_photo_fit_pose_device.h")
     assert "void joint_body(" in joint and '#include "svbrdf_photo_fit_device.h"' in joint
     assert "void fit_body(" in unit_build.assert_includes_shared_header("svbrdf_photo_fit", "svbrdf_photo_fit_device.h")
-    for used in ("fit_body<WEIGHTED>(", "joint_body<WEIGHTED>(", "adam_channel(", "adam_args(who,", "fit_weights_check(who,",
-                 "plan_sums(who,", "plan_loss(who,", "fit_bad(who,"):
+    for used in ("fit_body<WEIGHTED>(", "joint_body<WEIGHTED>(", "adam_channel(", "adam_args(who,", "weights_check(who,",
+                 "plan_sums(who,", "plan_loss(who,", "fail_as(who,"):
         assert used in code, used
     assert len(re.findall(r"\bvoid smooth_epilogue\(", code)) == 1 and code.count("smooth_epilogue(") == 2
     assert code.count("adam_channel(") == 1 and "photo_scene_loop" not in code and "pose_scene_loop" not in code

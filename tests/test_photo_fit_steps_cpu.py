@@ -246,9 +246,9 @@ def test_source_holds_no_inline_assembly_with_instructions_and_no_fma():
     # the steps entry checks and fills through the single step's helpers, in its own wording, and keeps what is its own: the
     # range of n_steps, the overflow guard on first_step + k, the scalars behind n_steps
     entry = code[code.index("int svbrdf_photo_fit_adam_steps("):]
-    for used in ("fit_weights_check(who,", "adam_args(who, rule,", '"first_step >= 1, a finite lr >= 0 and betas in [0, 1) are required"',
+    for used in ("weights_check(who,", "adam_args(who, rule,", '"first_step >= 1, a finite lr >= 0 and betas in [0, 1) are required"',
                  "first_step > 0x7fffffff - k", "n_steps < 1 || n_steps > SVBRDF_PHOTO_FIT_MAX_STEPS", "run.step_size[k] = sc[2]"):
         assert used in entry, used
-    assert entry.index("fit_weights_check(") < entry.index("n_steps < 1") < entry.index("first_step > 0x7fffffff") \
+    assert entry.index("weights_check(") < entry.index("n_steps < 1") < entry.index("first_step > 0x7fffffff") \
         < entry.index("adam_args(") < entry.index("svbrdf_photo_fit_steps_workspace_bytes(n_steps")
     assert "bounds_host[" not in entry and "aligned(" not in entry

@@ -257,6 +257,48 @@ def test_units_share_code_through_headers_only():
                 assert "__global__" not in text or name == "svbrdf_k3_kernels.h", name
 
 
+def test_photo_units_hold_each_shared_piece_once():
+    """the small pieces every photo body is made of -- the guards against non-finite maps (the numerics contract), the
+    pixel's coordinates, the positivity check, the weights' rule and the "<who>: <what>" reporter -- stand
+    once across the seven photo units, their headers and svbrdf_host.h"""
+    import re
+    files = sorted(n for n in os.listdir(CSRC) if n.startswith("svbrdf_photo_")) + ["svbrdf_host.h"]
+    assert len(files) == 7 + 4 + 1, files
+    code = "\n".join(line.split("//")[0] for line in unit_build.read_csrc(*files).splitlines())
+    shared = "\n".join(line.split("//")[0] for line in unit_build.read_csrc("svbrdf_photo_loss_device.h").splitlines())
+
+    def body(signature):        # the text of the one function whose definition starts with `signature`
+        assert code.count(signature) == 1 and signature in shared, signature
+        return code[code.index(signature):code.index("\n}\n", code.index(signature))]
+
+    # 1. the guards: `chk - chk` and `ds - ds` in maps_guard alone, the encoded planes' e[k] - e[k] in head_guard alone
+    assert code.count("chk - chk") == body("void maps_guard(const Maps &in,").count("chk - chk") == 2
+    assert code.count("ds - ds") == body("void maps_guard(const Maps &in,").count("ds - ds") == 1
+    assert len(re.findall(r"e\[(\d)\] - e\[\1\]", code)) == len(re.findall(r"e\[(\d)\] - e\[\1\]", body("float head_guard("))) == 9
+    assert code.count("poison += head_chk") == 1 and "poison += head_chk" in body("void head_guard_apply(")
+    # 2. the coordinates: the shift and mask in pixel_xy and in photo_loss_body's early branch, pixel_coords in pixel_xy alone
+    assert code.count("__builtin_ctz(") == 2 and "__builtin_ctz(" in body("void pixel_xy(") and code.count("pixel_coords<1>(") == 1
+    # 3. the loss tail: RELAXED, no once-only check.  photo_loss_body, photo_grad_body and fit_body write their twelve lines out
+    # (with fit_run_body's two-set tail and photo_sums_finish: five callers of loss_arrive).  As one function the tail moved
+    # two instruction lines in each of the 28 kernels, and on an MI355X, against the parent's library in the same call, two
+    # launch kinds then missed "median <= parent's median + parent's spread": the photo-gradient launch with both gradients,
+    # 51.02 us against 50.68 + 0.06, and PhotoFit(smooth=).step, 84.52 us against 82.06 + 0.66
+    # (profiles/r29_photo_shared_pieces.txt)
+    assert code.count("loss_arrive(t,") == 5 and code.count("float wave_part[") == 5 and "workgroup_loss_arrive" not in code
+    # 4. the item's base pointers: RELAXED, no once-only check.  The seven bodies write their four lines out: as one function
+    # the same expressions made the compiler schedule the scalar address arithmetic otherwise, loops with transcendentals of
+    # seven kernels carried other registers and the joint kernels gained an instruction (profiles/r29_photo_shared_pieces.txt)
+    assert code.count("weight_planes == 1 ? 0 : plane") == 7 and "item_ptrs" not in code
+    # 5. the positivity check of the light colours and of the gains
+    assert code.count("< __builtin_inff())") == 1 and code.count("positive_check(") == 1 + 3
+    # 6., 7. the host side: one reporter, one rule of the weights (its sentence, and the older entries' shorter one)
+    # (the second "%s: %s" is plan_loss's own reporter in svbrdf_host.h: K3's too, and not this layer's)
+    assert code.count('"%s: %s"') == 2 and code.count("int fail_as(") == 1
+    assert code.count("weight_planes != 1 && weight_planes != S") == 1 and code.count("int weights_check(") == 1
+    assert code.count("with weights, 0 without") == 1 and code.count('"pointers must be 4-byte aligned"') == 1
+    assert code.count("weight_planes must be 1 (one plane per item) or S (one per photo)") == 2
+
+
 @needs_hipcc
 def test_kernel_resources_and_scene_loops(photo_asm):
     isa_stats = _isa_stats()
